@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode-pass benchmark of the MI355X quant_cuda path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 7b-w4-s0]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 7b-w4-s0] [--full] [--dump-outputs DIR]
 
 A "step" is one batch-1 decode pass over ALL quantised linears of the model named by the config
 (LLaMA-7B: 32 layers x 7 = 224 QuantLinearLUT ops, each with its own synthetic weights, 3.3 GB in
@@ -10,9 +10,15 @@ libsqllm_hip.so and replayed as a HIP graph.  Inputs are resident in HBM before 
 `value` = tokens/s of the whole job = steps / wall time (barrier + synchronize on both sides, MAX
 over ranks), attention / norms / lm_head excluded exactly as in BASELINE.md section 2.
 
-The ONE JSON line answers every number BASELINE.json's metric asks for:
+A plain run sets up, warms up, times exactly --steps steps once and prints the JSON line (headline
+fields, `ms_per_step` = milliseconds of one timed step).  --dump-outputs DIR then writes what the timed
+pass hands its caller -- every linear's `mul` vector, float32, DIR/<linear name>.npy -- from inputs that
+are the same on every run with the same arguments, so two builds can be compared output for output.
+
+With --full the ONE JSON line answers every number BASELINE.json's metric asks for:
   * the headline fields: config 7b-w4-s0 (BASELINE.json configs[1]), timed for exactly --steps
-    steps; the same block is repeated (--repeats, default 5) and the median / min are reported too;
+    steps; the same block is repeated (--repeats, default 5 with --full, 1 without) and the median /
+    min are reported too;
   * `roofline`      every kernel dispatch of one pass bracketed by its own HIP start/stop events
                     (sqllm_profile_groups): achieved = algorithmic bytes per launch / average
                     kernel duration, against the 8 TB/s HBM peak; `per_layer_us` = the per-shape
@@ -22,7 +28,10 @@ The ONE JSON line answers every number BASELINE.json's metric asks for:
                     microseconds) and the 13B batch-{1,2,4,8} leg of configs[3] on the 13B shapes;
   * `cpu_baseline`  the reference-style CPU path on the host cores: torch dequant (codebook gather)
                     + torch.matmul, torch.matmul alone on pre-dequantised weights, and the OpenMP C
-                    port of the kernels' algorithm, each on a bounded sample of the same workload.
+                    port of the kernels' algorithm, each on a bounded sample of the same workload;
+  * `parity_spot`   the timed pass against the C port's fp64 results on the same weights and inputs;
+  * `drop_in`       (1-GPU default run) the same pass as one operator per linear, and through the
+                    QuantLinearLUT / fused-linear modules, eager and graph-replayed.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU, backend nccl = RCCL), two modes:
   * replicas (default when the model fits one GPU, i.e. every config but 65B): the unit of work is
@@ -68,7 +77,8 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="blocks of --steps steps timed for the median / min (the first is the contract's)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="blocks of --steps steps timed for the median / min (the first is the contract's); default 5 with --full, else 1")
     ap.add_argument("--config", default="7b-w4-s0", choices=sorted(CONFIGS))
     ap.add_argument("--layers", type=int, default=None, help="decoder layers to build (default: the model's)")
     ap.add_argument("--launch", default="graph", choices=["graph", "sequence"],
@@ -79,11 +89,19 @@ def parse_args():
     ap.add_argument("--parallel", default="auto", choices=["auto", "replicas", "pipeline", "columns"],
                     help="N > 1: independent replicas (weak scaling), layer-sharded ring pipeline, or every linear split by "
                          "output column with one all-gather per launch group (the latency split; opt-in)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-sub-records", action="store_true", help="skip the s45 / 13B-batch sub-records of the default run")
-    ap.add_argument("--per-shape", action="store_true", help="print the per-shape kernel table to stderr")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: repeated blocks, roofline and per-shape kernel times, "
+                         "parity spot, CPU baselines, drop-in paths and the s45 / 13B-batch sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the timed pass as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity spot")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline / per-shape kernel times")
+    ap.add_argument("--no-sub-records", action="store_true", help="with --full: skip the drop-in legs and the s45 / 13B-batch sub-records")
+    ap.add_argument("--per-shape", action="store_true", help="with --full: print the per-shape kernel table to stderr")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -251,6 +269,26 @@ def time_blocks(step, sync, steps, warmup, repeats):
         sync()
         out.append(time.perf_counter() - t0)
     return out
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6  # array data of one --dump-outputs directory (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(dirname, named):
+    """Write (name, tensor) pairs as dirname/<name>.npy in float32.  Beyond DUMP_BUDGET_BYTES in all, every array is
+    cut to the same fixed, seeded sample of its elements (flat indices sorted, the same on every run of these shapes)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = [(name, t.detach().float().cpu().numpy()) for name, t in named]
+    total = sum(a.nbytes for _, a in arrays)
+    keep = 1.0 if total <= DUMP_BUDGET_BYTES else DUMP_BUDGET_BYTES / total
+    for name, a in arrays:
+        if keep < 1.0:
+            n = max(1, int(a.size * keep))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return len(arrays)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -645,7 +683,7 @@ def measure_replica(config_name, dev, rank, args, steps, warmup, repeats, sync, 
         step = seq.launch
     blocks = time_blocks(step, sync, steps, warmup, repeats)
     out = dict(cfg=cfg, model_layers=model_layers, per_layer=len(spec["linears"]), layers=layers, seq=seq, xs=xs, ys=ys,
-               bytes_per_op=bytes_per_op, blocks=blocks, roofline=None, per_layer_us=None)
+               bytes_per_op=bytes_per_op, blocks=blocks, roofline=None, per_layer_us=None, step=step)
     if want_roofline:
         out["roofline"], out["per_layer_us"] = roofline_leg(seq, layers, bytes_per_op, cfg, config_name, not args.no_fuse)
     return out
@@ -752,10 +790,19 @@ def main():
     extra = {}
     if mode == "replicas":
         m = measure_replica(args.config, dev, rank, args, args.steps, args.warmup, args.repeats, sync,
-                            want_roofline=single and not args.no_roofline)
+                            want_roofline=single and args.full and not args.no_roofline)
         blocks, seq, layers = m["blocks"], m["seq"], m["layers"]
         bytes_per_op = m["bytes_per_op"]
         tokens_per_step = 1
+        if args.dump_outputs and rank == 0:
+            # the operator accumulates (mul += W x, the reference's semantics), so the buffers hold the sum of every pass run
+            # so far: zero them and run the timed step once more -- what every timed step computes, and what a caller of
+            # QuantLinearLUT.forward (which zeroes mul first) receives
+            for y in m["ys"]:
+                y.zero_()
+            m["step"]()
+            torch.cuda.synchronize(dev)  # (rank 0 alone: no barrier)
+            dump_outputs(args.dump_outputs, [(l["name"], y) for l, y in zip(layers, m["ys"])])
     elif mode == "columns":
         # every rank builds the same full operands (same seeds), keeps its column slices: 1 / world of every layer
         layers = build_layers(cfg, dev, 0, model_layers)
@@ -763,12 +810,17 @@ def main():
         gen = torch.Generator(device=dev).manual_seed(1234)  # the same activations on every rank
         xs, _ = decoder_inputs(layers, dev, gen)
         cpass = sharding.ColumnParallelPass(layers, xs, rank=rank, world_size=world, device=dev)
+        names = [(l["name"], l["N"]) for l in layers]
         del layers
         torch.cuda.empty_cache()
         layers = []
         blocks = time_blocks(cpass.step, sync, args.steps, args.warmup, args.repeats)
         tokens_per_step = 1
         seq, m = None, None
+        if args.dump_outputs and rank == 0:  # (the pass zeroes its arena itself: the buffers hold the last timed step)
+            torch.cuda.synchronize(dev)  # (rank 0 alone: no barrier)
+            dump_outputs(args.dump_outputs, [(names[i][0], cpass.result(gi, j, names[i][1]))
+                                             for gi, grp in enumerate(cpass.groups) for j, i in enumerate(grp)])
         extra["column_parallel"] = {"launch_groups": len(cpass.groups), "collectives_per_token": len(cpass.groups) if world > 1 else 0,
                                     "graph_captured": cpass.graph is not None}
     else:
@@ -792,6 +844,11 @@ def main():
         blocks = time_blocks(step, sync, args.steps, args.warmup, args.repeats)
         tokens_per_step = world
         seq, m = None, None
+        if args.dump_outputs and rank == 0:
+            # the last timed step as it left the buffers: every rank's hidden-state output of its last tick (gathered) and
+            # the `mul` of this rank's linears in that tick
+            torch.cuda.synchronize(dev)  # (rank 0 alone: no barrier)
+            dump_outputs(args.dump_outputs, [("hidden_gathered", pipe.buf)] + [(l["name"], y) for l, y in zip(layers, stage.ys)])
         extra["pipeline_tick_us"] = round(statistics.median(blocks) / args.steps / world * 1e6, 2)
 
     if use_dist:  # every block: MAX over ranks
@@ -858,9 +915,9 @@ def main():
         headline_default = args.config == "7b-w4-s0" and args.layers is None and not args.no_fuse and args.launch == "graph"
         # (the drop-in legs run first: the CPU legs leave 128-256 OpenMP / torch worker threads spinning for a while,
         # which slows the eager Python path of forward_eager several-fold)
-        if headline_default and not args.no_sub_records:
+        if args.full and headline_default and not args.no_sub_records:
             result["drop_in"] = drop_in_legs(layers, m["xs"], dev, args, sync, model_layers, per_layer)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # value = the C port of the kernels' algorithm on the host cores (kind "port"); the reference-style
             # torch paths BASELINE.json names (dequant + matmul, matmul alone) ride along in `paths`
             cp, ref_outs = cpu_baseline_c_port(layers, model_layers, xs=m["xs"])  # first: torch's OpenMP pool would spin beside it
@@ -882,7 +939,7 @@ def main():
         # release the headline model before the sub-records build theirs
         del m, seq, layers
         torch.cuda.empty_cache()
-        if headline_default and not args.no_sub_records:
+        if args.full and headline_default and not args.no_sub_records:
             sub = {}
             for name in SUB_RECORD_CONFIGS:
                 s = measure_replica(name, dev, rank, args, 20, 3, 3, sync, want_roofline=not args.no_roofline)

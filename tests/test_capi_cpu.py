@@ -262,18 +262,24 @@ def test_quantlinear_module_schema_matches_reference():
         QuantLinearLUT(2, 64, 64, False)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/squeezellm/quant.py"), reason="reference tree only exists in the dev container")
+# the reference's squeezellm/quant.py, byte for byte, as build() stages it (oracle/build_ref.sh) into the git-ignored oracle/_ref/
+REF_QUANT = os.path.join(H.ROOT, "oracle", "_ref", "reference_py", "quant.py")
+
+
+@pytest.mark.skipif(not os.path.exists(REF_QUANT), reason="oracle/_ref/reference_py/quant.py not staged (build() stages it only where the reference tree is present)")
 def test_unmodified_reference_quant_py_runs_on_this_quant_cuda():
     """`import quant_cuda` at squeezellm/quant.py:5 must resolve to this repo's module, and the
     reference's own QuantLinearLUT.forward must reach our operators with its own argument order
     (checked with a recording double; the real call needs a GPU and is covered by -m gpu)."""
     code = r'''
-import sys, contextlib, io
-sys.path.insert(0, %r); sys.path.insert(1, "/root/reference")
+import sys, contextlib, io, importlib.util
+sys.path.insert(0, %r)
 import torch, quant_cuda
 import squeezellm_amd.quant_cuda as impl
 assert quant_cuda.vecquant4matmul_nuq_perchannel is impl.vecquant4matmul_nuq_perchannel
-from squeezellm import quant as refquant          # the UNMODIFIED reference module
+spec = importlib.util.spec_from_file_location("reference_squeezellm_quant", %r)
+refquant = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(refquant)                 # the UNMODIFIED reference module
 assert refquant.quant_cuda is quant_cuda
 calls = []
 for name in impl.__all__:
@@ -289,7 +295,7 @@ assert calls == [("vecquant4matmul_nuq_perchannel", 4), ("vecquant4matmul_nuq_pe
                  ("vecquant3matmul_spmv_hybrid_nuq_perchannel", 10), ("vecquant3matmul_spmv_hybrid_nuq_perchannel_batched", 10),
                  ("vecquant4matmul_spmv_balanced_nuq_perchannel", 11)], calls
 print("OK")
-''' % H.ROOT
+''' % (H.ROOT, REF_QUANT)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.strip().endswith("OK"), out.stderr[-2000:]
 
