@@ -373,6 +373,33 @@ typedef struct sqllm_plan {
 } sqllm_plan;
 int sqllm_plan_query(const sqllm_op* op, sqllm_plan* plan);
 
+/* ---------------------------------------------------------------------------------------------
+ * Offline quantisation: the lookup tables of a checkpoint (the reference computes them with one
+ * sklearn KMeans per output channel on the CPU, quantization/nuq.py:50-58).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_nuq {
+  int32_t bits, N, K;    /* bits in {3, 4}; 2^bits <= K <= 65535; N >= 1 */
+  const float* values;   /* [N, K], each row ascending */
+  const float* weights;  /* [N, K], >= 0, same order; NULL = all ones */
+  float* centroids;      /* [N, 2^bits] out, ascending */
+  double* cost;          /* [N] out, may be NULL */
+} sqllm_nuq;
+
+/* Bytes of caller workspace sqllm_nuq_fit needs for these shapes (the pointers are not looked at; no GPU
+ * needed), or a negative SQLLM_E_* code for bad shapes.  Grows with min(N, 1024) x K. */
+int64_t sqllm_nuq_workspace_bytes(const sqllm_nuq* d);
+
+/* Exact weighted 1-D k-means of every row: the 2^bits centroids of the partition of the row into 2^bits
+ * contiguous ranges that minimises sum w (x - c)^2, each centroid the weighted mean of its range (fp64
+ * dynamic programming over prefix sums, divide and conquer per level: O(2^bits K log K) per row).  cost[r]
+ * (if given) is the minimum, summed in fp64 around the fp64 centroids.  A row whose weights sum to 0 is
+ * fitted with unit weights; a range of zero total weight gets the unweighted mean of its values; a row of
+ * fewer than 2^bits distinct values repeats its largest value.  Enqueues one kernel on `stream`, allocates
+ * nothing; `workspace` holds workspace_bytes >= sqllm_nuq_workspace_bytes(d) of device memory, contents
+ * irrelevant before and after, one call at a time.  SQLLM_E_BITS / SQLLM_E_SHAPE / SQLLM_E_NULL (a NULL
+ * descriptor, values, centroids or workspace) before the device is touched; a short workspace is SQLLM_E_SHAPE. */
+int sqllm_nuq_fit(const sqllm_nuq* d, void* workspace, int64_t workspace_bytes, sqllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,13 @@ class SqllmPlan(ctypes.Structure):
         "col_tiles", "k_slices", "groups_per_wave", "dense_blocks", "csr_blocks", "topx_blocks", "grid_x", "grid_y")]
 
 
+class SqllmNuq(ctypes.Structure):
+    """struct sqllm_nuq (include/sqllm_hip.h): one exact weighted k-means fit per row."""
+
+    _fields_ = [("bits", c_int32), ("N", c_int32), ("K", c_int32), ("values", c_void_p), ("weights", c_void_p),
+                ("centroids", c_void_p), ("cost", c_void_p)]
+
+
 P = c_void_p  # every device pointer crosses as void*
 
 _DENSE = [P, P, P, P, c_int, c_int, P]
@@ -80,6 +87,8 @@ SIGNATURES = {
     "sqllm_set_option": [c_char_p, c_int],
     "sqllm_get_option": [c_char_p, POINTER(c_int)],
     "sqllm_plan_query": [POINTER(SqllmOp), POINTER(SqllmPlan)],
+    "sqllm_nuq_workspace_bytes": [POINTER(SqllmNuq)],
+    "sqllm_nuq_fit": [POINTER(SqllmNuq), P, ctypes.c_int64, P],
 }
 for _b in (3, 4):
     SIGNATURES[f"sqllm_vecquant{_b}matmul_nuq_perchannel"] = _DENSE
@@ -114,7 +123,7 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = (c_char_p if name == "sqllm_error_string" else
-                      ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes") else c_int)
+                      ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes") else c_int)
     if lib.sqllm_abi_version() != 1:
         raise RuntimeError(f"libsqllm_hip.so ABI {lib.sqllm_abi_version()} != 1 expected by this package")
     _lib = lib
@@ -182,3 +191,11 @@ def plan_query(bits: int, K: int, N: int, batch: int = 0, nnz: int = 0, topX: in
     plan = SqllmPlan()
     check(load().sqllm_plan_query(ctypes.byref(op), ctypes.byref(plan)), "sqllm_plan_query")
     return {n: getattr(plan, n) for n, _ in SqllmPlan._fields_}
+
+
+def nuq_workspace_bytes(bits: int, N: int, K: int) -> int:
+    """Bytes of device workspace one sqllm_nuq_fit of these shapes needs (no GPU needed); raises on bad shapes."""
+    d = SqllmNuq(bits=bits, N=N, K=K)
+    n = int(load().sqllm_nuq_workspace_bytes(ctypes.byref(d)))
+    check(n if n < 0 else 0, "sqllm_nuq_workspace_bytes")
+    return n
