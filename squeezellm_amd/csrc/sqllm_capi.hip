@@ -1,5 +1,8 @@
 // sqllm_capi.hip -- the extern "C" surface declared in include/sqllm_hip.h: argument validation,
 // launch planning, and the reference operator names as thin adapters over sqllm_launch().
+// How a group of ops is launched is decided in ONE place -- route_of (which kernel family) and plan_group (its geometry);
+// the launch, sqllm_plan_query and sqllm_workspace_bytes all ask there.  tests/native/launch_recorder.cpp links this file
+// against recording launchers: a change to the planner can be diffed launch by launch on a machine without a GPU.
 // Replaces the reference's pybind11 layer squeezellm/quant_cuda.cpp:112-270 and the grid math of
 // its launchers squeezellm/quant_cuda_kernel.cu:132-738 (no torch types cross this boundary).
 #include <hip/hip_runtime.h>
@@ -28,6 +31,7 @@ int device_slot() {
 }
 
 Knobs& knobs() { return g_knobs[device_slot()]; }
+static int opt(std::atomic<int> Knobs::*field) { return (knobs().*field).load(std::memory_order_relaxed); }
 
 // The wide-batch paths take stream-ordered scratch (hipMallocAsync) per group of ops.  The default pool's
 // release threshold is 0: every synchronisation hands the block back to the OS and the next call pays
@@ -35,7 +39,7 @@ Knobs& knobs() { return g_knobs[device_slot()]; }
 // group needs (2048 rows x K = 22016: transposed vec 180 MB + bf16 planes 271 MB + slabs <= 32 MB).
 static void keep_scratch_in_pool() {
   static std::atomic<unsigned> done{0};
-  if (!knobs().scratch_pool_threshold.load(std::memory_order_relaxed)) return;  // opted out: the pool is left as the application set it
+  if (!opt(&Knobs::scratch_pool_threshold)) return;  // opted out: the pool is left as the application set it
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) { (void)hipGetLastError(); return; }
   const unsigned bit = 1u << dev;
@@ -53,7 +57,7 @@ static void keep_scratch_in_pool() {
 }
 
 int cu_count() {
-  int c = knobs().cu_count.load(std::memory_order_relaxed);
+  int c = opt(&Knobs::cu_count);
   if (c > 0) return c;
   int dev = 0;
   hipDeviceProp_t prop;
@@ -90,12 +94,32 @@ int validate(const sqllm_op* op) {
 
 // option "validate_csr": a value check of rows[] on the device (blocks the host; debugging aid)
 int validate_csr_values(const sqllm_op* op, sqllm_stream_t stream) {
-  if (!knobs().validate_csr.load(std::memory_order_relaxed) || !op->rows || op->nnz <= 0) return SQLLM_OK;
+  if (!opt(&Knobs::validate_csr) || !op->rows || op->nnz <= 0) return SQLLM_OK;
   int bad = 0;
   hipError_t e = sqllm::check_csr(op->rows, op->N, op->nnz, static_cast<hipStream_t>(stream), &bad);
   if (e != hipSuccess) return static_cast<int>(e);
   return bad ? SQLLM_E_SPARSE : SQLLM_OK;
 }
+
+constexpr int round8(int v) { return (v + 7) / 8 * 8; }
+
+// Workgroups of the fused batch-tile kernel (sqllm_fused_matvec<BITS, BT>) that one CU holds at once, by bit width and batch tile
+// (batch_tile_op): four at one row and on the 4-bit 2-row tile, three where the tile compiles to <= 80 VGPRs (4-bit: up to 6 rows; 3-bit:
+// up to 3), two beyond (sqllm_fused.h: fused_min_waves).  THE residency table of the host layer: make_plan's one-round cut,
+// widen_csr_chunks and set_role_priority all read it.
+int resident_per_cu(int bits, int bt) {
+  return (bt == 1 || (bt == 2 && bits == 4)) ? 4 : (bits == 4 ? (bt <= 6 ? 3 : 2) : (bt <= 3 ? 3 : 2));
+}
+
+// where an op's dense workgroups start, behind its CSR / top-X workgroups: at a multiple of 8 so that (dense id % 8) is the XCD of
+// the workgroup -- or right behind them with sparse_last (grid = dense + sparse)
+static void place_dense(sqllm::KernelGeom* gm) {
+  const int sparse = gm->csr_blocks + gm->topx_blocks;
+  gm->dense_block0 = (gm->sparse_last & 1) ? sparse : round8(sparse);
+}
+
+// workgroups of one op in a launch of several: padded to a multiple of 8 (dense ids keep their XCD alignment)
+static int padded_blocks(const sqllm::KernelGeom& gm) { return round8(gm.dense_block0 + gm.dense_blocks); }
 
 // Launch geometry.  The dense part is cut into 64-column tiles x K slices so that about `target`
 // workgroups exist (1-3 per CU, 8 waves each, of the 4 that fit: the 7B shapes hold only
@@ -110,9 +134,9 @@ void make_plan(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch, int
   gm->col_tiles = (op->N + sqllm::kTileN - 1) / sqllm::kTileN;
   gm->units_total = op->K / kK;
   const int step = waves * 4;  // units one workgroup step covers
-  int upw = knobs().groups_per_wave.load(std::memory_order_relaxed) * waves;
+  int upw = opt(&Knobs::groups_per_wave) * waves;
   if (upw <= 0) {
-    int target = knobs().target_wgs.load(std::memory_order_relaxed);
+    int target = opt(&Knobs::target_wgs);
     if (target <= 0) {
       // measured on MI355X (tools/sweep.py, bench.py): an op under ~12 MB of packed weights runs
       // best with one 8-wave workgroup per CU when it shares its launch with others (q/k/v) and
@@ -142,11 +166,11 @@ void make_plan(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch, int
     // take the K slices that fit beside the sparse workgroups.  Not at four per CU (batch 1: 7B down_proj 960 + 242 against 1024 is 3 % FASTER than
     // 768 + 242), not for launches that are several rounds anyway, not for groups (flat: r06_launch_geometry_cols.txt, last block).
     const int bt = sqllm::batch_tile_op(gm->batch);
-    const int per_cu = (bt == 1 || (bt == 2 && op->bits == 4)) ? 4 : (op->bits == 4 ? (bt <= 6 ? 3 : 2) : (bt <= 3 ? 3 : 2));
+    const int per_cu = resident_per_cu(op->bits, bt);
     // ... and, at four per CU, for a 3-BIT op alone in its batch-1 launch: a launch that fits gets the dense-wave priority (set_role_priority, rule 1) -- 65B
     // o_proj, 1024 + 359 against 1024: 11.8 -> 11.2 us with 512 (10.85 with 384; profiles/r06_launch_geometry_b1.txt)
     const bool w3_batch1 = per_cu == 4 && op->bits == 3 && gm->batch == 1;
-    if (ops_in_launch <= 1 && (per_cu <= 3 || w3_batch1) && knobs().target_wgs.load(std::memory_order_relaxed) <= 0) {
+    if (ops_in_launch <= 1 && (per_cu <= 3 || w3_batch1) && opt(&Knobs::target_wgs) <= 0) {
       const int slots = per_cu * cu_count();
       const int sparse = ((op->rows && op->nnz > 0) ? (op->nnz + sqllm::kCsrChunk - 1) / sqllm::kCsrChunk : 0) +
                          ((op->full_rows && op->topX > 0) ? (op->K + sqllm::kTopxRows - 1) / sqllm::kTopxRows : 0);
@@ -166,8 +190,8 @@ void make_plan(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch, int
   // 4-bit batch-1 waves work in chunks of four steps (128 units per workgroup, sqllm_fused.h: NBUF): a K slice of ONE chunk plus ONE step -- 160 units, the
   // 13B gate/up and down_proj under the size classes above -- pays a second round of loads for a quarter of a chunk.  One chunk per slice instead
   // (more slices): 13B s45 gate/up 22.2-22.8 -> 21.2-21.9 us, down_proj 12.85-13.5 -> 12.2-12.35 (profiles/r06_launch_geometry_b1.txt).
-  if (op->bits == 4 && gm->batch == 1 && waves == sqllm::kWaves && knobs().groups_per_wave.load(std::memory_order_relaxed) <= 0 &&
-      knobs().target_wgs.load(std::memory_order_relaxed) <= 0 && upw == 5 * step && (gm->units_total + 4 * step - 1) / (4 * step) <= max_slices)
+  if (op->bits == 4 && gm->batch == 1 && waves == sqllm::kWaves && opt(&Knobs::groups_per_wave) <= 0 &&
+      opt(&Knobs::target_wgs) <= 0 && upw == 5 * step && (gm->units_total + 4 * step - 1) / (4 * step) <= max_slices)
     upw = 4 * step;
   gm->units_per_wg = upw;
   gm->k_slices = (gm->units_total + upw - 1) / upw;
@@ -178,15 +202,13 @@ void make_plan(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch, int
   // top-X rows: a role of their own, one workgroup per kTopxRows k's (the fused linear folds them
   // into the dense tiles instead and drops these workgroups from its plan)
   gm->topx_blocks = gm->topX ? (op->K + sqllm::kTopxRows - 1) / sqllm::kTopxRows : 0;
-  // dense blocks start at a multiple of 8 so that (dense id % 8) is the XCD of the workgroup
-  gm->dense_block0 = (gm->csr_blocks + gm->topx_blocks + 7) / 8 * 8;
-  gm->sparse_last = knobs().sparse_last.load(std::memory_order_relaxed);
-  if (gm->sparse_last) gm->dense_block0 = gm->csr_blocks + gm->topx_blocks;  // grid = dense + sparse
+  gm->sparse_last = opt(&Knobs::sparse_last);
+  place_dense(gm);
   if (g_experimental.csr_ablation_bits) gm->sparse_last |= g_experimental.csr_ablation_bits() << 1;  // (measurement library)
 }
 
-// Whose waves win the issue arbitration in a BATCH-1 operator launch with sparse roles (round 6; `segs` = the launch's segments as
-// make_plan left them, `total` = its workgroups).  The CSR / top-X workgroups are chains of memory round trips in front of the grid; the dense
+// Whose waves win the issue arbitration in a BATCH-1 operator launch with sparse roles (round 6; `gm` = the geometry of the launch's
+// ops as make_plan left it, `total` = its workgroups).  The CSR / top-X workgroups are chains of memory round trips in front of the grid; the dense
 // workgroups are issue-bound.  Same-box A/Bs of variant builds, three alternating repetitions each, on two to three boxes per rule
 // (profiles/r06_dense_priority_ab.txt, r06_sparse_order_ab.txt, r06_final_ab.txt, r06_sparse_priority_ab.txt, r06_role_priority_ab.txt):
 //  1 (dense waves at s_setprio 1): 3-bit launches whose workgroups are all resident at once (four 8-wave workgroups per CU) -- the sparse
@@ -198,41 +220,40 @@ void make_plan(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch, int
 //    +3.3 %); NOT the smaller 3-bit multi-round launches (7B gate/up +1.3 % on both boxes).
 // Built on the way and dropped: the sparse workgroups LAST in the grid per launch (-3...-9 % per launch on one box, +3...+12 % on another;
 // as a global switch it costs o_proj +12 %, which is why option sparse_last measured as "no change" in rounds 3 and 5).
-void set_role_priority(sqllm::Segment* segs, int n, int bits, int batch, int total, bool widened) {
-  if (batch > 1 || (segs[0].gm.sparse_last & 1)) return;
+void set_role_priority(sqllm::KernelGeom* gm, int n, int bits, int batch, int total, bool widened) {
+  if (batch > 1 || (gm[0].sparse_last & 1)) return;
   int sparse = 0;
-  for (int i = 0; i < n; ++i) sparse += (segs[i].gm.csr_wide ? 2 : 1) * segs[i].gm.csr_blocks + segs[i].gm.topx_blocks;  // (counted in chunks of kCsrChunk)
+  for (int i = 0; i < n; ++i) sparse += (gm[i].csr_wide ? 2 : 1) * gm[i].csr_blocks + gm[i].topx_blocks;  // (counted in chunks of kCsrChunk)
   if (!sparse) return;
-  const bool fits = !widened && total <= 4 * cu_count();
+  const bool fits = !widened && total <= resident_per_cu(bits, 1) * cu_count();  // (batch-1 launches only: four per CU, as the table has it)
   int prio = 0;
   if (bits == 3) prio = fits ? 1 : (sparse >= 2 * cu_count() ? 2 : 0);
   else prio = 2;
-  for (int i = 0; i < n; ++i) segs[i].gm.dense_prio = prio;
+  for (int i = 0; i < n; ++i) gm[i].dense_prio = prio;
 }
 
 // CSR chunks of 2 * kCsrChunk non-zeros in operator launches of the fused kernel that exceed the resident slots AND carry many sparse workgroups (>= 1.25 x
 // CUs at kCsrChunk each): half as many workgroups in front of the grid, each with twice the non-zeros in the same chain of round trips.  A build with
 // 2048 everywhere (profiles/r06_sparse_granularity_ab.txt) showed both sides: gate/up -2.7...-6.4 % (7B 430 / 13B 702 sparse workgroups), 13B
 // down_proj -5.7 % (365), 13B q/k/v -3 % (408), against o_proj +13...+29 % (its fewer, longer sparse workgroups become the launch's tail), 7B q/k/v
-// +1-1.5 % (270) and the 7B 3-bit down_proj +13 % (fits: dense priority).  Returns true if it widened; `*total` is recomputed then.
+// +1-1.5 % (270) and the 7B 3-bit down_proj +13 % (fits: dense priority).  `total` = the launch's workgroups; returns true if it widened (the caller lays the ops out again).
 // The batch tiles of up to 5 rows take part (three workgroups per CU there, four in the 4-bit 2-row tile): 13B s45 layer at 2 / 4 / 5 rows -1.7 / -1.1 / -1.1 % (r06_wide_chunks_tiles.txt).
-bool widen_csr_chunks(sqllm::Segment* segs, int n, int bits, int batch, int* total) {
-  const int resident = (batch <= 1 || (batch == 2 && bits == 4)) ? 4 : 3;  // (workgroups per CU of the tile that serves `batch` rows: sqllm_fused.h, fused_min_waves)
-  if (batch > 5 || *total <= resident * cu_count() || (segs[0].gm.sparse_last & 1)) return false;
+bool widen_csr_chunks(sqllm::KernelGeom* gm, int n, int bits, int batch, int total) {
+  // Workgroups per CU of the tile that serves `batch` rows -- but never fewer than three.  This DIFFERS from resident_per_cu for the
+  // 3-bit 4- and 5-row tiles (88 VGPRs: two per CU there, three here): the rule was measured with three, and moving its threshold is a
+  // routing change that wants a same-box A/B of its own.
+  const int table = resident_per_cu(bits, sqllm::batch_tile_op(batch <= 0 ? 1 : batch));
+  const int resident = table > 3 ? table : 3;
+  if (batch > 5 || total <= resident * cu_count() || (gm[0].sparse_last & 1)) return false;
   int sparse = 0;
-  for (int i = 0; i < n; ++i) sparse += segs[i].gm.csr_blocks + segs[i].gm.topx_blocks;
+  for (int i = 0; i < n; ++i) sparse += gm[i].csr_blocks + gm[i].topx_blocks;
   if (4 * sparse < 5 * cu_count()) return false;
-  int t = 0;
-  for (int i = 0; i < n; ++i) {
-    sqllm::KernelGeom& gm = segs[i].gm;
-    if (gm.csr_blocks > 0) {
-      gm.csr_wide = 1;
-      gm.csr_blocks = (gm.nnz + 2 * sqllm::kCsrChunk - 1) / (2 * sqllm::kCsrChunk);
-      gm.dense_block0 = (gm.csr_blocks + gm.topx_blocks + 7) / 8 * 8;
+  for (int i = 0; i < n; ++i)
+    if (gm[i].csr_blocks > 0) {
+      gm[i].csr_wide = 1;
+      gm[i].csr_blocks = (gm[i].nnz + 2 * sqllm::kCsrChunk - 1) / (2 * sqllm::kCsrChunk);
+      place_dense(&gm[i]);
     }
-    t += (gm.dense_block0 + gm.dense_blocks + 7) / 8 * 8;
-  }
-  *total = t;
   return true;
 }
 
@@ -250,36 +271,25 @@ void fill_segment(const sqllm_op* op, sqllm::Segment* sg) {
   sg->out16 = nullptr;
 }
 
-// Geometry of the wide-batch (matrix-core) kernel: one pass covers 16 * mb batch rows (blockIdx.y
-// walks the passes).  The dense work of a pass is the FLATTENED (column tile, unit) space cut into
-// equal contiguous ranges, one per workgroup, as many as the chip holds at once (2 per CU; 1 for
-// the 64-row kernels, by their registers) divided by the number of passes: one round of
-// workgroups, none of them short (N / 64 is rarely a multiple of the CU count: cutting K slices per
-// column tile left the last round 27 % full on the 13B gate/up shape).  A range is a whole number
-// of workgroup steps (waves x 4 units); one that crosses a tile boundary costs a second piece.
-// `reserve`: workgroups of the launch that are not dense ranges (the fused small launch's top-X slabs) -- they hold
-// slots of the one round too.
-void make_plan_mfma(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch = 1, int row_blocks = 0, int wgs_per_cu = 0, int reserve = 0) {
-  make_plan(op, gm, 1);
-  const int mb = row_blocks > 0 ? row_blocks : sqllm::mfma_row_blocks(gm->batch);
-  const int grid_y = (gm->batch + 16 * mb - 1) / (16 * mb);
-  const int step = sqllm::kWaves * 4;
+// The range cut shared by the matrix-core kernel (tile form, fused small launch) and the column-lane kernel: the dense work of a
+// pass is the FLATTENED (column tile, unit) space cut into equal contiguous ranges, one per workgroup -- `target` workgroups for the
+// launch (option target_wgs overrides it), shared by its ops and its `grid_y` passes.  A range is a whole number of `step` units.
+static void cut_ranges(sqllm::KernelGeom* gm, int bits, int ops_in_launch, int step, int target, int grid_y) {
   const long long total_units = (long long)gm->col_tiles * gm->units_total;
-  long long upw = (long long)knobs().groups_per_wave.load(std::memory_order_relaxed) * step;
+  long long upw = (long long)opt(&Knobs::groups_per_wave) * step;
   bool aligned = false;
   if (upw <= 0) {
-    int target = knobs().target_wgs.load(std::memory_order_relaxed);
-    if (target <= 0) {
-      target = (wgs_per_cu > 0 ? wgs_per_cu : mb == 4 ? 1 : 2) * cu_count();
-      if (reserve > 0 && target - reserve >= target / 2) target -= reserve;
-    }
+    if (opt(&Knobs::target_wgs) > 0) target = opt(&Knobs::target_wgs);
     target = (target + ops_in_launch - 1) / ops_in_launch;  // the ops of a group share the launch's workgroups
     long long ranges = (target + grid_y - 1) / grid_y;
     if (ranges < 1) ranges = 1;
     upw = (total_units + ranges - 1) / ranges;
-    // tile-aligned ranges where a whole number per tile comes within 10 % of the wanted count (see make_plan_cols)
+    // A range that crosses a column-tile boundary is worked off as two pieces, each with its own table build.
+    // Where a whole number of ranges per tile comes within 10 % of the wanted count, cut the tiles that way
+    // instead (K = 5120: 640 units per tile against ranges of 200 -- two of three ranges crossed; the 5120-wide
+    // ops were the one family the column-lane kernel lost on, profiles/r03_tile_vs_cols_by_shape.txt).
     const long long upws = (upw + step - 1) / step * step;
-    const long long need = (gm->units_total + upws - 1) / upws;
+    const long long need = (gm->units_total + upws - 1) / upws;  // ranges of that length a tile needs
     for (long long per_tile = need; per_tile >= 1 && per_tile >= need - 1 && !aligned; --per_tile) {
       long long even = (gm->units_total + per_tile - 1) / per_tile;
       even = (even + step - 1) / step * step;
@@ -290,7 +300,7 @@ void make_plan_mfma(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch
     // UNEVEN ranges per tile (K = 5120: 216 / 216 / 208 units) is 5-7 % faster on two even ones -- 13B q/k/v at 3 / 4 rows 19.5 / 22.0 ->
     // 18.6 / 20.5 us (four per tile: 18.8 / 20.8; the 408 sparse workgroups hold half the slots first).  Not so dense-only, at 3 bits, or where
     // the cut is even already (7B, 65B: fewer ranges cost 5-17 % there).
-    if (aligned && ops_in_launch >= 3 && op->bits == 4 && gm->nnz > 0 && (gm->units_total + upw - 1) / upw == 3 &&
+    if (aligned && ops_in_launch >= 3 && bits == 4 && gm->nnz > 0 && (gm->units_total + upw - 1) / upw == 3 &&
         gm->units_total % upw != 0 && gm->units_total % (2 * sqllm::kWaves) == 0)
       upw = gm->units_total / 2;
   }
@@ -298,9 +308,28 @@ void make_plan_mfma(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch
   if (upw > 0x3fffffff) upw = 0x3fffffff / step * step;
   gm->units_per_wg = (int)upw;
   gm->k_slices = (int)((gm->units_total + upw - 1) / upw);  // pieces per column tile (reported by plan_query)
+  // (the kernels recognise the tile-aligned cut by dense_blocks == col_tiles * k_slices; a contiguous cut that happens
+  // to satisfy the same equation is then READ as tile-aligned -- ranges of units_per_wg units that restart at every
+  // tile -- which covers every unit exactly once as well: tests/test_capi_cpu.py fuzzes both readings)
   gm->dense_blocks = aligned ? gm->col_tiles * gm->k_slices : (int)((total_units + upw - 1) / upw);
   gm->sparse_last = 0;
-  gm->dense_block0 = (gm->csr_blocks + gm->topx_blocks + 7) / 8 * 8;
+  place_dense(gm);
+}
+
+// Geometry of the wide-batch (matrix-core) kernel: one pass covers 16 * mb batch rows (blockIdx.y
+// walks the passes).  The dense work of a pass is cut into equal ranges (cut_ranges), as many as the
+// chip holds at once (2 per CU; 1 for the 64-row kernels, by their registers) divided by the number
+// of passes: one round of workgroups, none of them short (N / 64 is rarely a multiple of the CU
+// count: cutting K slices per column tile left the last round 27 % full on the 13B gate/up shape).
+// A range is a whole number of workgroup steps (waves x 4 units); one that crosses a tile boundary costs a second piece.
+// `reserve`: workgroups of the launch that are not dense ranges (the fused small launch's top-X slabs) -- they hold
+// slots of the one round too.
+void make_plan_mfma(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch = 1, int row_blocks = 0, int wgs_per_cu = 0, int reserve = 0) {
+  make_plan(op, gm, 1);
+  const int mb = row_blocks > 0 ? row_blocks : sqllm::mfma_row_blocks(gm->batch);
+  int target = (wgs_per_cu > 0 ? wgs_per_cu : mb == 4 ? 1 : 2) * cu_count();
+  if (reserve > 0 && target - reserve >= target / 2) target -= reserve;
+  cut_ranges(gm, op->bits, ops_in_launch, sqllm::kWaves * 4, target, (gm->batch + 16 * mb - 1) / (16 * mb));
 }
 
 // Geometry of the WIDE matrix-core kernel (sqllm_mfma_wide.hip: sqllm_fused_wide).  A UNIT is a block of 64 rows x a
@@ -323,7 +352,7 @@ int make_plan_wide(const sqllm_op* op, sqllm::KernelGeom* gm) {  // returns full
   int s = rem > 0 ? (int)(cus / rem) : 1;
   if (s > max_s) s = max_s;
   if (s < 1) s = 1;
-  const int want = knobs().groups_per_wave.load(std::memory_order_relaxed) * 4;  // (option: units of K per slice, in groups of 4)
+  const int want = opt(&Knobs::groups_per_wave) * 4;  // (option: units of K per slice, in groups of 4)
   int upw = want > 0 ? want : ((gm->units_total + s - 1) / s + 3) / 4 * 4;
   if (upw > gm->units_total) upw = (gm->units_total + 3) / 4 * 4;
   gm->units_per_wg = upw;
@@ -331,7 +360,7 @@ int make_plan_wide(const sqllm_op* op, sqllm::KernelGeom* gm) {  // returns full
   const long long blocks = full + rem * gm->k_slices;
   gm->dense_blocks = blocks > 0x7fffffff ? 0x7fffffff : (int)blocks;
   gm->sparse_last = 0;
-  gm->dense_block0 = (gm->csr_blocks + gm->topx_blocks + 7) / 8 * 8;
+  place_dense(gm);
   return (int)full;
 }
 
@@ -343,8 +372,8 @@ int make_plan_wide(const sqllm_op* op, sqllm::KernelGeom* gm) {  // returns full
 // registers, slices add atomically) only once its units fill 80 % of the CUs (5120x13824: from 512 rows).  An explicit
 // mfma_wide_min_batch is taken at its word.
 bool takes_wide_path(const sqllm_op* op, bool with_scratch, bool capturing) {
-  if (!knobs().mfma_split.load(std::memory_order_relaxed)) return false;
-  const int from = knobs().mfma_wide_min_batch.load(std::memory_order_relaxed);
+  if (!opt(&Knobs::mfma_split)) return false;
+  const int from = opt(&Knobs::mfma_wide_min_batch);
   if (from > 0) return op->batch >= from;
   if (op->batch < 64) return false;
   if (with_scratch) {
@@ -360,7 +389,7 @@ bool takes_wide_path(const sqllm_op* op, bool with_scratch, bool capturing) {
 void fold_csr_into_dense(sqllm::KernelGeom* gm) {
   gm->fold_csr = gm->nnz > 0 ? 1 : 0;
   gm->csr_blocks = 0;
-  gm->dense_block0 = (gm->sparse_last & 1) ? gm->topx_blocks : (gm->topx_blocks + 7) / 8 * 8;
+  place_dense(gm);
 }
 
 // top-X workgroups of an op in the fused small launch: with the transposed vec at hand 8 (K <= 40 slabs) or 16 of them
@@ -378,13 +407,13 @@ int small_topx_blocks(const sqllm_op* op, bool with_xT, int ops_in_launch) {
 // dense workgroups per CU the fused small launch's planner aims at: as many as the kernel holds (two, by its registers:
 // capped at 80 for a third one, the dense role measured 10 % slower -- profiles/r05_small_split_register_cap.txt)
 int small_wgs_per_cu_of(const sqllm_op* op) {
-  const int v = knobs().small_wgs_per_cu.load(std::memory_order_relaxed);
+  const int v = opt(&Knobs::small_wgs_per_cu);
   return v > 0 ? v : 2;
 }
 
 // rows from which an op -- or, n_ops > 1, the group it leads -- leaves the batch tiles / the column-lane kernel for the matrix cores
 int mfma_min_batch_of(const sqllm_op* op, int n_ops = 1) {
-  const int v = knobs().mfma_min_batch.load(std::memory_order_relaxed);
+  const int v = opt(&Knobs::mfma_min_batch);
   if (v > 0) return v;  // (an explicit value is taken at its word, whatever the shape)
   // 3-bit: 17 until round 4 -- from 9 rows the fused small-batch launch of the split matrix-core kernel beats the
   // column-lane kernel (13B s45 layer 191-226 vs 270-286 us at 9-16 rows).
@@ -400,7 +429,7 @@ int mfma_min_batch_of(const sqllm_op* op, int n_ops = 1) {
   return 7;
 }
 int cols_max_batch_of(const sqllm_op* op) {
-  const int v = knobs().cols_max_batch.load(std::memory_order_relaxed);
+  const int v = opt(&Knobs::cols_max_batch);
   // 4-bit: up to 4 rows; single ops of >= 20 MB up to 6 (round 6, with the kernel's passes of exactly 5 / 6 rows: 13B down_proj 22.4 / 25.7 us against
   // 23.6 / 26.7 on the 5- / 6-row tiles, the layer -0.8 / -1.9 %; at 7 rows its 7-row pass beats the fused small launch by events, 29.6 against
   // 32.5 us, and loses by graph wall, the layer +1.1 %: profiles/r06_cols_single_ops_5_7.txt; groups are kept at 4 rows by cols_pays)
@@ -412,62 +441,23 @@ bool takes_mfma_path(const sqllm_op* op, int n_ops = 1) { return op->batch >= 1 
 // does this op (or the group it leads) run as the fused small launch of the split matrix-core kernel (sqllm_fused_small_split)?
 bool takes_small_split(const sqllm_op* op, int n_ops = 1) {
   if (op->K >= (1 << 26)) return false;  // (its folded CSR walk packs a local row beside the column)
-  return takes_mfma_path(op, n_ops) && op->batch <= sqllm::kSmallSplitRows && knobs().mfma_split.load(std::memory_order_relaxed) &&
-         knobs().mfma_fuse_small.load(std::memory_order_relaxed);
+  return takes_mfma_path(op, n_ops) && op->batch <= sqllm::kSmallSplitRows && opt(&Knobs::mfma_split) &&
+         opt(&Knobs::mfma_fuse_small);
 }
 
-// Geometry of the small-batch column-lane kernel: passes of batch_tile(batch) <= 8 rows
-// (blockIdx.y); the dense work of a pass is cut into equal ranges of the flattened
-// (column tile, unit) space like make_plan_mfma's, three workgroups per CU (the phases of a
+// Geometry of the small-batch column-lane kernel: passes of batch_tile_op(batch) <= 8 rows
+// (blockIdx.y: 1-8 rows in one pass, 8 per pass beyond); the dense work of a pass is cut into equal
+// ranges of the flattened (column tile, unit) space like make_plan_mfma's (cut_ranges; a range is a
+// whole number of waves here), three workgroups per CU (the phases of a
 // workgroup -- table build, decode, combine -- hide behind its neighbours').
 void make_plan_cols(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch = 1) {
   make_plan(op, gm, 1);
   const int bt = sqllm::batch_tile_op(gm->batch);
-  const int grid_y = (gm->batch + bt - 1) / bt;
-  const long long total_units = (long long)gm->col_tiles * gm->units_total;
-  long long upw = (long long)knobs().groups_per_wave.load(std::memory_order_relaxed) * sqllm::kWaves;
-  bool aligned = false;
-  if (upw <= 0) {
-    int target = knobs().target_wgs.load(std::memory_order_relaxed);
-    if (target <= 0) target = 3 * cu_count();
-    target = (target + ops_in_launch - 1) / ops_in_launch;  // the ops of a group share the launch's workgroups
-    long long ranges = (target + grid_y - 1) / grid_y;
-    if (ranges < 1) ranges = 1;
-    upw = (total_units + ranges - 1) / ranges;
-    // A range that crosses a column-tile boundary is worked off as two pieces, each with its own table build.
-    // Where a whole number of ranges per tile comes within 10 % of the wanted count, cut the tiles that way
-    // instead (K = 5120: 640 units per tile against ranges of 200 -- two of three ranges crossed; the 5120-wide
-    // ops were the one family the column-lane kernel lost on, profiles/r03_tile_vs_cols_by_shape.txt).
-    const long long upw8 = (upw + sqllm::kWaves - 1) / sqllm::kWaves * sqllm::kWaves;
-    const long long need = (gm->units_total + upw8 - 1) / upw8;  // ranges of that length a tile needs
-    for (long long per_tile = need; per_tile >= 1 && per_tile >= need - 1 && !aligned; --per_tile) {
-      long long even = (gm->units_total + per_tile - 1) / per_tile;
-      even = (even + sqllm::kWaves - 1) / sqllm::kWaves * sqllm::kWaves;
-      const long long n_even = (long long)gm->col_tiles * ((gm->units_total + even - 1) / even);
-      if (n_even <= ranges && 10 * n_even >= 9 * ranges) { upw = even; aligned = true; }
-    }
-    // Measured exception (profiles/r06_launch_geometry_cols.txt): a 4-bit group of three ops WITH sparse terms whose aligned cut is three
-    // UNEVEN ranges per tile (K = 5120: 216 / 216 / 208 units) is 5-7 % faster on two even ones -- 13B q/k/v at 3 / 4 rows 19.5 / 22.0 ->
-    // 18.6 / 20.5 us (four per tile: 18.8 / 20.8; the 408 sparse workgroups hold half the slots first).  Not so dense-only, at 3 bits, or where
-    // the cut is even already (7B, 65B: fewer ranges cost 5-17 % there).
-    if (aligned && ops_in_launch >= 3 && op->bits == 4 && gm->nnz > 0 && (gm->units_total + upw - 1) / upw == 3 &&
-        gm->units_total % upw != 0 && gm->units_total % (2 * sqllm::kWaves) == 0)
-      upw = gm->units_total / 2;
-  }
-  upw = (upw + sqllm::kWaves - 1) / sqllm::kWaves * sqllm::kWaves;
-  if (upw > 0x3fffffff) upw = 0x3fffffff / sqllm::kWaves * sqllm::kWaves;
-  gm->units_per_wg = (int)upw;
-  gm->k_slices = (int)((gm->units_total + upw - 1) / upw);
-  // (the kernel recognises the tile-aligned cut by dense_blocks == col_tiles * k_slices; a contiguous cut that happens
-  // to satisfy the same equation is then READ as tile-aligned -- ranges of units_per_wg units that restart at every
-  // tile -- which covers every unit exactly once as well: tests/test_capi_cpu.py fuzzes both readings)
-  gm->dense_blocks = aligned ? gm->col_tiles * gm->k_slices : (int)((total_units + upw - 1) / upw);
-  gm->sparse_last = 0;
-  gm->dense_block0 = (gm->csr_blocks + gm->topx_blocks + 7) / 8 * 8;
+  cut_ranges(gm, op->bits, ops_in_launch, sqllm::kWaves, 3 * cu_count(), (gm->batch + bt - 1) / bt);
 }
 
 int cols_min_batch_of() {
-  const int v = knobs().cols_min_batch.load(std::memory_order_relaxed);
+  const int v = opt(&Knobs::cols_min_batch);
   return v > 0 ? v : 2;
 }
 
@@ -479,7 +469,7 @@ int cols_min_batch_of() {
 // square ops stay on the tiles.  Applied only while the routing options are at their defaults: an explicit
 // cols_min_batch / cols_max_batch is taken at its word.
 bool cols_pays(const sqllm_op* op, int n_ops) {
-  if (knobs().cols_min_batch.load(std::memory_order_relaxed) > 0 || knobs().cols_max_batch.load(std::memory_order_relaxed) > 0) return true;
+  if (opt(&Knobs::cols_min_batch) > 0 || opt(&Knobs::cols_max_batch) > 0) return true;
   const double mb = (double)op->K * op->N * op->bits / 8e6;  // (of a group: the sum of its ops)
   // (round 6: the 4-bit 2-row tile went to four workgroups per CU -- a three-op group WITH sparse terms of >= 32 MB is then faster on the tiles at exactly
   // 2 rows: 13B q/k/v 17.1 -> 15.4 us, 65B 35 -> 32; 7B's 25 MB and every dense-only group stay here: profiles/r06_tile2_half.txt)
@@ -519,7 +509,7 @@ static bool op_has_sparse(const sqllm_op* op) { return (op->rows && op->nnz > 0)
 // the routing test shared by single ops and groups: `sum` = the op, or the group as the one op it is to the kernel (the sum of its columns)
 static bool cols_route(const sqllm_op* sum, int n_ops, bool sparse) {
   const int b = sum->batch <= 0 ? 1 : sum->batch;
-  const bool explicit_range = knobs().cols_min_batch.load(std::memory_order_relaxed) > 0 || knobs().cols_max_batch.load(std::memory_order_relaxed) > 0;
+  const bool explicit_range = opt(&Knobs::cols_min_batch) > 0 || opt(&Knobs::cols_max_batch) > 0;
   if (b == 1 && !explicit_range) return cols_pays_batch1(sum, n_ops, sparse);
   return b >= cols_min_batch_of() && b <= cols_max_batch_of(sum) && cols_pays(sum, n_ops);
 }
@@ -538,6 +528,175 @@ bool group_takes_cols_path(const sqllm_op* ops, int n) {
 }
 
 bool takes_cols_path(const sqllm_op* op) { return !takes_mfma_path(op) && cols_route(op, 1, op_has_sparse(op)); }
+
+// ---- the launch planner --------------------------------------------------------------------------------------------------
+// ONE place decides how a group of ops is launched: route_of picks the kernel family, plan_group the geometry.  The launch
+// (launch_group_with_events), sqllm_plan_query and sqllm_workspace_bytes all ask here.
+
+enum Route {
+  kFusedTiles,   // ONE launch of the fused batch-tile kernel over the group (batch 1 and the small batches the other routes leave)
+  kFusedLinear,  // ... as the fused fp16 linear (sqllm_linear_f16)
+  kColsGroup,    // ONE launch of the column-lane kernel, its workgroups divided between the ops
+  kFusedSmall,   // up to 16 rows on the split matrix-core kernel: ONE launch for the whole group, sparse roles included
+  kPerOpMfma,    // one launch per op (the members of a group only share their input) of the matrix-core kernel (wide batches)
+  kPerOpCols,    // a single op on the column-lane kernel (small batches)
+};
+
+// (small batches: a group whose summed columns pass the column-lane kernel's test takes that kernel as ONE launch --
+// make_plan_cols divides the workgroup target by the number of ops; other groups stay on the batch tiles, which beat
+// one column-lane launch per op -- 13B s45 decoder layer at 2 rows: 88 vs 101 us)
+static Route route_of(const sqllm_op* ops, int n, bool is_linear) {
+  if (is_linear) return kFusedLinear;
+  if (n > 1 && opt(&Knobs::cols_groups) && group_takes_cols_path(ops, n)) return kColsGroup;
+  if (takes_small_split(&ops[0], n)) return kFusedSmall;
+  if (takes_mfma_path(&ops[0], n)) return kPerOpMfma;
+  if (n == 1 && takes_cols_path(&ops[0])) return kPerOpCols;
+  return kFusedTiles;
+}
+
+// Every op of a group is valid and the ops share vec, K, bits and batch.  The batch-tile kernels read batch <= 0 as one row
+// (a matvec op and a one-row *_batched op may share a launch); the other kernels address vec with 32-bit row offsets.
+static int validate_group(const sqllm_op* ops, int n, sqllm_stream_t stream, Route route) {
+  const bool tiles = route == kFusedTiles || route == kFusedLinear;
+  for (int i = 0; i < n; ++i) {
+    const sqllm_op* op = &ops[i];
+    int rc = validate(op);
+    if (rc == SQLLM_OK) rc = validate_csr_values(op, stream);
+    if (rc != SQLLM_OK) return rc;
+    const bool same_batch = tiles ? (op->batch <= 0 ? 1 : op->batch) == (ops[0].batch <= 0 ? 1 : ops[0].batch) : op->batch == ops[0].batch;
+    if (op->vec != ops[0].vec || op->K != ops[0].K || op->bits != ops[0].bits || !same_batch) return SQLLM_E_GROUP;
+    if (!tiles && (uint64_t)op->batch * (uint64_t)op->K >= (1ull << 31)) return SQLLM_E_SHAPE;  // 32-bit row offsets into vec
+  }
+  return SQLLM_OK;
+}
+
+// what the plan depends on beside the ops and the options: the scratch the launch has obtained
+struct ScratchFacts {
+  bool xT = false;         // a transposed vec is at hand (fused small launch)
+  bool planes = false;     // vec split into bf16 planes is at hand (matrix-core kernel, wide form)
+  bool capturing = false;  // ... and the scratch had to be allocated inside a stream capture
+};
+
+struct LaunchPlan {
+  int first = 0, n_seg = 0;  // its segments are ops[first .. first + n_seg)
+  int block0[sqllm::kMaxSegments + 1] = {};
+  // matrix-core launches of one op:
+  bool wide = false;            // the wide form (make_plan_wide) ...
+  int wide_full_units = 0;      // ... with this many units over all of K
+  int row_blocks = 0;           // tile form: blocks of 16 rows per pass, 0 = mfma_row_blocks(batch)
+  bool split = true;            // bf16 matrix instructions on exactly split operands (option mfma_split)
+  bool sparse_in_grid = false;  // the op's CSR / top-X workgroups ride in the dense launch's grid ...
+  bool sparse_launch = false;   // ... or are a launch of their own in front of it
+};
+
+struct GroupPlan {
+  Route route = kFusedTiles;
+  int rc = SQLLM_OK;  // SQLLM_E_SHAPE: a fused linear whose columns would receive more than kMaxContrib contributions
+  int n_launches = 0;
+  LaunchPlan launch[sqllm::kMaxSegments];
+  sqllm::KernelGeom gm[sqllm::kMaxSegments];  // per op
+};
+
+// block0[]: workgroup ids [block0[s], block0[s + 1]) belong to segment s.  `pad`: every segment a multiple of 8 long (launches of several
+// ops: dense ids keep their XCD alignment); the one-op launches of the matrix-core and column-lane kernels end with their last workgroup.
+static int layout_blocks(const sqllm::KernelGeom* gm, int n, bool pad, int* block0) {
+  int at = 0;
+  for (int i = 0; i < n; ++i) {
+    block0[i] = at;
+    at += pad ? padded_blocks(gm[i]) : gm[i].dense_block0 + gm[i].dense_blocks;
+  }
+  for (int i = n; i <= sqllm::kMaxSegments; ++i) block0[i] = at;
+  return at;
+}
+
+// one op on the matrix-core kernel: wide or tile form, and where its sparse terms run
+static void plan_mfma_op(const sqllm_op* op, const ScratchFacts& f, LaunchPlan* lp, sqllm::KernelGeom* gm) {
+  lp->split = opt(&Knobs::mfma_split) != 0;
+  lp->wide = takes_wide_path(op, f.planes, f.capturing);
+  if (lp->wide) lp->wide_full_units = make_plan_wide(op, gm);
+  else make_plan_mfma(op, gm);
+  // the sparse terms first, as a launch of their own (see sqllm_sparse_batched), then the dense term
+  // (running the two on different streams was tried: they do not overlap -- the dense kernel holds
+  // every CU's registers -- and the two event waits cost 14 us per op)
+  const int sparse = gm->csr_blocks + gm->topx_blocks;
+  // tile form: the sparse terms ride in the dense launch's grid (sqllm_fused_batched_split_all) -- always up to 32 rows
+  // (two workgroups per CU: 13B shapes 59-69 -> 55-57 us, 5120x5120 35-46 -> 28-38); from 33 rows, where the kernel
+  // takes a whole CU per workgroup, only while the sparse workgroups are fewer than the CUs (5120x5120 at 64 rows
+  // 81 -> 54 us; with 331 of them, 5120x13824, 112 -> 117: profiles/r04_mid_rows_fused_sparse.txt)
+  const bool may_fuse = sparse > 0 && !lp->wide && lp->split && opt(&Knobs::mfma_fuse_sparse);
+  lp->sparse_in_grid = may_fuse && (op->batch <= 32 || sparse < cu_count());
+  if (may_fuse && !lp->sparse_in_grid && op->batch <= 64) {
+    // 33-64 rows with more sparse workgroups than CUs: two passes of 32 rows on the kernel that leaves room for two
+    // workgroups per CU, sparse terms in its grid, instead of one 64-row pass + their own launch
+    // (profiles/r04_mid_rows_fused_sparse.txt, "mb2")
+    lp->row_blocks = 2;
+    make_plan_mfma(op, gm, 1, 2);
+    lp->sparse_in_grid = true;
+  }
+  lp->sparse_launch = sparse > 0 && !lp->sparse_in_grid;
+}
+
+// Everything the launch of a (validated) group needs, from the ops, the options, the CU count and the scratch facts alone: touches no
+// stream, allocates nothing, launches nothing.
+static void plan_group(const sqllm_op* ops, int n, Route route, const ScratchFacts& f, GroupPlan* p) {
+  p->route = route;
+  const bool per_op = route == kPerOpMfma || route == kPerOpCols;
+  switch (route) {
+    case kColsGroup:
+    case kPerOpCols:
+      for (int i = 0; i < n; ++i) make_plan_cols(&ops[i], &p->gm[i], n);
+      break;
+    case kFusedSmall: {
+      // The dense ranges are ONE round of workgroups, as many as the chip holds at once: the top-X slabs (8 per op, padded)
+      // take their slots from the same count.  (Planned beside them, 20-50 dense workgroups of a 13B launch found no slot,
+      // started when the first ones left and ran as a second round of their own: 34 instead of 22 us per down_proj launch at
+      // 16 rows -- profiles/r05_small_split_timeline.txt.)
+      int reserve = 0;
+      if (f.xT || opt(&Knobs::small_reserve_topx))
+        for (int i = 0; i < n; ++i) reserve += round8(small_topx_blocks(&ops[i], f.xT, n));
+      for (int i = 0; i < n; ++i) {
+        make_plan_mfma(&ops[i], &p->gm[i], n, 0, small_wgs_per_cu_of(&ops[i]), reserve);
+        p->gm[i].topx_blocks = small_topx_blocks(&ops[i], f.xT, n);
+        fold_csr_into_dense(&p->gm[i]);
+      }
+      break;
+    }
+    case kPerOpMfma:
+      for (int i = 0; i < n; ++i) plan_mfma_op(&ops[i], f, &p->launch[i], &p->gm[i]);
+      break;
+    case kFusedLinear:
+      for (int i = 0; i < n; ++i) {
+        const sqllm_op* op = &ops[i];
+        sqllm::KernelGeom* gm = &p->gm[i];
+        // a column's K slices + the CSR chunks its row can be spread over must fit the 6-bit count
+        const int csr_bound = (op->rows && op->nnz > 0) ? op->K / sqllm::kCsrChunk + 2 : 0;
+        make_plan(op, gm, n, sqllm::kMaxContrib - csr_bound > 1 ? sqllm::kMaxContrib - csr_bound : 1);
+        // the top-X rows are always handled inside the dense workgroups: no top-X role in the grid
+        gm->topx_blocks = 0;
+        place_dense(gm);
+        // the 55-bit sum field holds at most kMaxContrib clamped contributions per column: the K
+        // slices and one per CSR chunk a row can be spread over
+        if (gm->k_slices + (gm->csr_blocks ? op->K / sqllm::kCsrChunk + 2 : 0) > sqllm::kMaxContrib) {
+          p->rc = SQLLM_E_SHAPE;
+          return;
+        }
+      }
+      break;
+    case kFusedTiles:
+      for (int i = 0; i < n; ++i) make_plan(&ops[i], &p->gm[i], n);
+      break;
+  }
+  p->n_launches = per_op ? n : 1;
+  for (int l = 0; l < p->n_launches; ++l) {
+    LaunchPlan* lp = &p->launch[l];
+    lp->first = per_op ? l : 0;
+    lp->n_seg = per_op ? 1 : n;
+    const int total = layout_blocks(&p->gm[lp->first], lp->n_seg, !per_op, lp->block0);
+    if (route != kFusedTiles) continue;
+    const bool widened = widen_csr_chunks(p->gm, n, ops[0].bits, ops[0].batch, total);
+    set_role_priority(p->gm, n, ops[0].bits, ops[0].batch, widened ? layout_blocks(p->gm, n, true, lp->block0) : total, widened);
+  }
+}
 
 }  // namespace sqllm_host
 
@@ -568,114 +727,82 @@ const char* sqllm_error_string(int code) {
 // (Until round 5 any non-negative value was stored as it came, and one of them -- sparse_transpose = 2 -- switched to a
 // timing-only mode that left the kernels reading an unwritten workspace; that experiment now lives behind the measurement
 // library's hook, ExperimentalHooks::skip_prepare_small.)
+struct Option { const char* name; std::atomic<int> Knobs::*field; int max; };
+static const Option kOptions[] = {
+    {"target_wgs", &Knobs::target_wgs, 1 << 24},
+    {"groups_per_wave", &Knobs::groups_per_wave, 1 << 24},
+    {"cu_count", &Knobs::cu_count, 1 << 16},  // for GPU-less planning tests
+    {"sparse_last", &Knobs::sparse_last, 1},
+    {"cols_groups", &Knobs::cols_groups, 1},
+    {"mfma_min_batch", &Knobs::mfma_min_batch, 0x7fffffff},  // (a huge value: never)
+    {"cols_min_batch", &Knobs::cols_min_batch, 0x7fffffff},
+    {"cols_max_batch", &Knobs::cols_max_batch, 0x7fffffff},
+    {"sparse_transpose", &Knobs::sparse_transpose, 1},
+    {"scratch_in_capture", &Knobs::scratch_in_capture, 1},
+    {"validate_csr", &Knobs::validate_csr, 1},
+    {"mfma_split", &Knobs::mfma_split, 1},
+    {"split_planes_min_batch", &Knobs::split_planes_min_batch, 0x7fffffff},
+    {"mfma_wide_min_batch", &Knobs::mfma_wide_min_batch, 0x7fffffff},
+    {"mfma_fuse_small", &Knobs::mfma_fuse_small, 1},
+    {"mfma_fuse_sparse", &Knobs::mfma_fuse_sparse, 1},
+    {"scratch_pool_threshold", &Knobs::scratch_pool_threshold, 1},
+    {"small_wgs_per_cu", &Knobs::small_wgs_per_cu, 8},
+    {"small_reserve_topx", &Knobs::small_reserve_topx, 1},
+    {"small_planes", &Knobs::small_planes, 1},
+};
+static const Option* find_option(const char* name) {
+  for (const Option& o : kOptions)
+    if (!strcmp(name, o.name)) return &o;
+  return nullptr;
+}
+
 int sqllm_set_option(const char* name, int value) {
   if (!name || value < 0) return SQLLM_E_OPTION;
-  struct Opt { const char* name; std::atomic<int> Knobs::*field; int max; };
-  static const Opt kOptions[] = {
-      {"target_wgs", &Knobs::target_wgs, 1 << 24},
-      {"groups_per_wave", &Knobs::groups_per_wave, 1 << 24},
-      {"cu_count", &Knobs::cu_count, 1 << 16},  // for GPU-less planning tests
-      {"sparse_last", &Knobs::sparse_last, 1},
-      {"cols_groups", &Knobs::cols_groups, 1},
-      {"mfma_min_batch", &Knobs::mfma_min_batch, 0x7fffffff},  // (a huge value: never)
-      {"cols_min_batch", &Knobs::cols_min_batch, 0x7fffffff},
-      {"cols_max_batch", &Knobs::cols_max_batch, 0x7fffffff},
-      {"sparse_transpose", &Knobs::sparse_transpose, 1},
-      {"scratch_in_capture", &Knobs::scratch_in_capture, 1},
-      {"validate_csr", &Knobs::validate_csr, 1},
-      {"mfma_split", &Knobs::mfma_split, 1},
-      {"split_planes_min_batch", &Knobs::split_planes_min_batch, 0x7fffffff},
-      {"mfma_wide_min_batch", &Knobs::mfma_wide_min_batch, 0x7fffffff},
-      {"mfma_fuse_small", &Knobs::mfma_fuse_small, 1},
-      {"mfma_fuse_sparse", &Knobs::mfma_fuse_sparse, 1},
-      {"scratch_pool_threshold", &Knobs::scratch_pool_threshold, 1},
-      {"small_wgs_per_cu", &Knobs::small_wgs_per_cu, 8},
-      {"small_reserve_topx", &Knobs::small_reserve_topx, 1},
-      {"small_planes", &Knobs::small_planes, 1},
-  };
-  for (const Opt& o : kOptions)
-    if (!strcmp(name, o.name)) {
-      if (value > o.max) return SQLLM_E_OPTION;
-      (knobs().*(o.field)).store(value);
-      return SQLLM_OK;
-    }
+  if (const Option* o = find_option(name)) {
+    if (value > o->max) return SQLLM_E_OPTION;
+    (knobs().*(o->field)).store(value);
+    return SQLLM_OK;
+  }
   if (g_experimental.set_option) return g_experimental.set_option(name, value);  // (measurement library)
   return SQLLM_E_OPTION;
 }
 
 int sqllm_get_option(const char* name, int* value) {
   if (!name || !value) return SQLLM_E_OPTION;
-  if (!strcmp(name, "target_wgs")) { *value = knobs().target_wgs.load(); return SQLLM_OK; }
-  if (!strcmp(name, "groups_per_wave")) { *value = knobs().groups_per_wave.load(); return SQLLM_OK; }
-  if (!strcmp(name, "cu_count")) { *value = knobs().cu_count.load(); return SQLLM_OK; }
-  if (!strcmp(name, "sparse_last")) { *value = knobs().sparse_last.load(); return SQLLM_OK; }
-  if (!strcmp(name, "cols_groups")) { *value = knobs().cols_groups.load(); return SQLLM_OK; }
-  if (!strcmp(name, "mfma_min_batch")) { *value = knobs().mfma_min_batch.load(); return SQLLM_OK; }
-  if (!strcmp(name, "cols_min_batch")) { *value = knobs().cols_min_batch.load(); return SQLLM_OK; }
-  if (!strcmp(name, "cols_max_batch")) { *value = knobs().cols_max_batch.load(); return SQLLM_OK; }
-  if (!strcmp(name, "sparse_transpose")) { *value = knobs().sparse_transpose.load(); return SQLLM_OK; }
-  if (!strcmp(name, "scratch_in_capture")) { *value = knobs().scratch_in_capture.load(); return SQLLM_OK; }
-  if (!strcmp(name, "validate_csr")) { *value = knobs().validate_csr.load(); return SQLLM_OK; }
-  if (!strcmp(name, "mfma_split")) { *value = knobs().mfma_split.load(); return SQLLM_OK; }
-  if (!strcmp(name, "split_planes_min_batch")) { *value = knobs().split_planes_min_batch.load(); return SQLLM_OK; }
-  if (!strcmp(name, "mfma_wide_min_batch")) { *value = knobs().mfma_wide_min_batch.load(); return SQLLM_OK; }
-  if (!strcmp(name, "mfma_fuse_small")) { *value = knobs().mfma_fuse_small.load(); return SQLLM_OK; }
-  if (!strcmp(name, "mfma_fuse_sparse")) { *value = knobs().mfma_fuse_sparse.load(); return SQLLM_OK; }
-  if (!strcmp(name, "scratch_pool_threshold")) { *value = knobs().scratch_pool_threshold.load(); return SQLLM_OK; }
-  if (!strcmp(name, "small_wgs_per_cu")) { *value = knobs().small_wgs_per_cu.load(); return SQLLM_OK; }
-  if (!strcmp(name, "small_reserve_topx")) { *value = knobs().small_reserve_topx.load(); return SQLLM_OK; }
-  if (!strcmp(name, "small_planes")) { *value = knobs().small_planes.load(); return SQLLM_OK; }
+  if (const Option* o = find_option(name)) {
+    *value = (knobs().*(o->field)).load();
+    return SQLLM_OK;
+  }
   if (g_experimental.get_option) return g_experimental.get_option(name, value);  // (measurement library)
   return SQLLM_E_OPTION;
 }
 
+// The plan of ONE op as launched alone through a `_ws` entry point with enough workspace, outside a stream capture: the scratch
+// its route can use is at hand (vec transposed where option sparse_transpose allows it, vec as bf16 planes).
 int sqllm_plan_query(const sqllm_op* op, sqllm_plan* plan) {
   if (!plan) return SQLLM_E_NULL;
   // planning needs shapes only; tolerate NULL data pointers here
   if (!op) return SQLLM_E_NULL;
   if (op->bits != 3 && op->bits != 4) return SQLLM_E_BITS;
   if (op->K <= 0 || op->N <= 0 || (op->K % 32) != 0 || (op->N % 4) != 0) return SQLLM_E_SHAPE;
-  sqllm::KernelGeom gm;
-  const bool mfma = takes_mfma_path(op);
-  const bool wide = mfma && takes_wide_path(op, true, false);  // (as launched outside a capture, scratch at hand)
-  int row_blocks = 0;
-  if (wide) (void)make_plan_wide(op, &gm);
-  else if (mfma) {
-    make_plan_mfma(op, &gm);
-    // (33-64 rows with more sparse workgroups than CUs: two 32-row passes, sparse terms in the grid -- launch_group_with_events)
-    if (op->batch > 32 && op->batch <= 64 && gm.csr_blocks + gm.topx_blocks >= cu_count() && knobs().mfma_split.load(std::memory_order_relaxed) &&
-        knobs().mfma_fuse_sparse.load(std::memory_order_relaxed)) {
-      row_blocks = 2;
-      make_plan_mfma(op, &gm, 1, 2);
-    }
-  }
-  const bool cols = !mfma && takes_cols_path(op);
-  if (cols) make_plan_cols(op, &gm);
-  else if (!mfma) {
-    make_plan(op, &gm);
-    sqllm::Segment one;  // (as launched alone: a batch-1 launch that exceeds the resident slots may take wide CSR chunks)
-    one.gm = gm;
-    int total = (gm.dense_block0 + gm.dense_blocks + 7) / 8 * 8;
-    (void)widen_csr_chunks(&one, 1, op->bits, op->batch, &total);
-    gm = one.gm;
-  }
-  const bool small_split = mfma && !wide && takes_small_split(op);
-  if (small_split) {  // the fused small launch: CSR term folded into the dense workgroups, top-X slabs in the grid
-    // (as launched with a workspace: vec transposed, 8-16 top-X workgroups, the dense ranges planned beside them)
-    const bool with_xT = knobs().sparse_transpose.load(std::memory_order_relaxed) != 0;
-    make_plan_mfma(op, &gm, 1, 0, small_wgs_per_cu_of(op),
-                   (with_xT || knobs().small_reserve_topx.load(std::memory_order_relaxed)) ? (small_topx_blocks(op, with_xT, 1) + 7) / 8 * 8 : 0);
-    gm.topx_blocks = small_topx_blocks(op, with_xT, 1);
-    fold_csr_into_dense(&gm);
-  }
+  ScratchFacts facts;
+  facts.xT = opt(&Knobs::sparse_transpose) != 0;
+  facts.planes = true;
+  GroupPlan p;
+  plan_group(op, 1, route_of(op, 1, false), facts, &p);
+  const sqllm::KernelGeom& gm = p.gm[0];
+  const LaunchPlan& lp = p.launch[0];
   plan->col_tiles = gm.col_tiles;
   plan->k_slices = gm.k_slices;
   plan->groups_per_wave = gm.units_per_wg;
   plan->dense_blocks = gm.dense_blocks;
   plan->csr_blocks = gm.csr_blocks;
   plan->topx_blocks = gm.topx_blocks;
-  plan->grid_x = (mfma && !small_split) ? gm.dense_blocks : gm.dense_block0 + gm.dense_blocks;  // (wide batches: the sparse terms are a launch of their own)
-  const int rows_per_pass = wide ? (gm.batch > 0 ? gm.batch : 1) : mfma ? 16 * (row_blocks ? row_blocks : sqllm::mfma_row_blocks(gm.batch)) : sqllm::batch_tile_op(gm.batch);
+  const bool mfma = p.route == kPerOpMfma;
+  plan->grid_x = mfma ? gm.dense_blocks : gm.dense_block0 + gm.dense_blocks;  // (wide batches: the dense workgroups; the sparse terms are counted in csr_blocks / topx_blocks)
+  const int rows_per_pass = lp.wide ? gm.batch
+                            : (mfma || p.route == kFusedSmall) ? 16 * (lp.row_blocks ? lp.row_blocks : sqllm::mfma_row_blocks(gm.batch))
+                                                               : sqllm::batch_tile_op(gm.batch);
   plan->grid_y = (gm.batch + rows_per_pass - 1) / rows_per_pass;
   return SQLLM_OK;
 }
@@ -724,8 +851,8 @@ struct WideScratch {
       const uint64_t b = sqllm::wide_slab_bytes(gm.dense_blocks, full, gm.k_slices);
       if (b > slab_bytes) slab_bytes = b;
     }
-    const bool want_xT = any_csr && knobs().sparse_transpose.load(std::memory_order_relaxed);
-    int from = knobs().split_planes_min_batch.load(std::memory_order_relaxed);
+    const bool want_xT = any_csr && opt(&Knobs::sparse_transpose);
+    int from = opt(&Knobs::split_planes_min_batch);
     if (from == 0) from = kSplitPlanesMinBatch;
     const uint64_t chunks = sqllm::split_planes_chunks(ops[0].batch, ops[0].K);
     const bool want_planes = any_wide && ops[0].batch >= from && chunks < (1ull << 31);  // (32-bit chunk numbers in the kernel)
@@ -754,7 +881,7 @@ struct WideScratch {
       p = static_cast<char*>(ws);  // nothing allocated, nothing to free: a capture stays free of memory nodes
     } else {
       capturing = in_capture;
-      if (capturing && !knobs().scratch_in_capture.load(std::memory_order_relaxed)) return SQLLM_OK;
+      if (capturing && !opt(&Knobs::scratch_in_capture)) return SQLLM_OK;
       L = layout(ops, n, capturing);
       if (L.total() == 0) return SQLLM_OK;
       keep_scratch_in_pool();
@@ -788,8 +915,75 @@ struct WideScratch {
   }
 };
 
-// One kernel over 1..kMaxSegments ops that share vec, K, bits and batch.  `lin` (optional) points at
-// the fused-linear descriptors the ops were taken from: `ops` is then lin[i].op.
+// Scratch of a fused small launch (up to 16 rows): vec TRANSPOSED (xT[k][rows]: the folded CSR walk and the top-X slabs then read
+// ONE line per k for all the batch rows) and behind it vec as bf16 planes for the dense term (option small_planes) --
+// sqllm_prepare_small writes both.  Without it the sparse terms gather from vec itself.
+struct SmallScratch {
+  void* own = nullptr;  // stream-ordered allocation of our own (freed by the destructor)
+  hipStream_t s = nullptr;
+  float* xT = nullptr;
+  void* planes = nullptr;
+  struct Layout { int64_t xt = 0, planes = 0; int64_t total() const { return xt + planes; } };
+  static Layout layout(const sqllm_op* ops, int n) {
+    Layout L;
+    bool any_sparse = false;
+    for (int i = 0; i < n; ++i) any_sparse = any_sparse || (ops[i].nnz > 0 && ops[i].rows) || (ops[i].full_rows && ops[i].topX > 0);
+    if (!any_sparse || ops[0].batch <= 0 || ops[0].K <= 0 || !opt(&Knobs::sparse_transpose)) return L;
+    L.xt = sqllm::transpose_small_bytes(ops[0].batch, ops[0].K);
+    L.planes = opt(&Knobs::small_planes) ? sqllm::small_planes_bytes(ops[0].K) : 0;
+    return L;
+  }
+  // The caller's workspace where it is large enough.  Otherwise, for the workspace-less names only, stream-ordered scratch as for
+  // the wider batches -- never inside a capture: its memory nodes cost more than the gathers (profiles/r04_small_batch_layer.txt);
+  // never for a `_ws` entry point: those allocate nothing up to 16 rows and leave the default pool alone -- the walk gathers.
+  void acquire(const sqllm_op* ops, int n, sqllm_stream_t stream, void* ws, int64_t ws_bytes, bool ws_entry) {
+    const Layout L = layout(ops, n);
+    if (!L.xt || !ops[0].vec || (reinterpret_cast<uintptr_t>(ops[0].vec) & 15u) != 0) return;  // (the transposition reads vec 16 bytes at a time)
+    if (ws && (reinterpret_cast<uintptr_t>(ws) & 15u) == 0 && ws_bytes >= L.total()) {
+      xT = static_cast<float*>(ws);
+    } else if (!ws_entry) {
+      s = static_cast<hipStream_t>(stream);
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+        keep_scratch_in_pool();
+        if (hipMallocAsync(&own, (size_t)L.total(), s) == hipSuccess && own) xT = static_cast<float*>(own);
+        else { (void)hipGetLastError(); own = nullptr; }
+      } else {
+        (void)hipGetLastError();
+      }
+    }
+    if (xT && L.planes) planes = reinterpret_cast<char*>(xT) + L.xt;
+  }
+  ~SmallScratch() {
+    if (own) (void)hipFreeAsync(own, s);
+  }
+};
+
+// The operands of launch `lp` of a planned group.  `lin` (optional): the fused-linear descriptors the ops were taken from.
+static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_linear* lin, const GroupPlan& plan, const LaunchPlan& lp) {
+  a->x = ops[0].vec;
+  a->linear = lin != nullptr;
+  a->wide = lp.wide;
+  a->wide_full_units = lp.wide_full_units;
+  a->row_blocks = lp.row_blocks;
+  a->ga.n_seg = lp.n_seg;
+  memcpy(a->ga.block0, lp.block0, sizeof(lp.block0));
+  memset(a->ga.seg, 0, sizeof(a->ga.seg));
+  for (int i = 0; i < lp.n_seg; ++i) {
+    sqllm::Segment& sg = a->ga.seg[i];
+    fill_segment(&ops[lp.first + i], &sg);
+    sg.gm = plan.gm[lp.first + i];
+    if (lin) {
+      // accumulate into the workspace plane; op->mul is the fp16 result
+      sg.y = reinterpret_cast<float*>(lin[lp.first + i].workspace);
+      sg.out16 = ops[lp.first + i].mul;
+      sg.bias = lin[lp.first + i].bias;
+    }
+  }
+}
+
+// One group of 1..kMaxSegments ops that share vec, K, bits and batch: validate -> obtain scratch -> plan -> fill the operands ->
+// call the launcher(s) the plan names.  `lin` (optional) points at the fused-linear descriptors: the ops are then lin[i].op.
 // `ws` / `ws_bytes`: the caller's workspace (sqllm_launch_*_ws; sqllm_workspace_bytes says how much a group can use), or null.
 // `ws_entry`: the call came through a `_ws` entry point -- up to 16 rows nothing is allocated then, workspace or not.
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
@@ -797,214 +991,6 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
                                     bool ws_entry = false) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
-  // (small batches: a group whose summed columns pass the column-lane kernel's test takes that kernel as ONE launch --
-  // make_plan_cols divides the workgroup target by the number of ops; other groups stay on the batch tiles, which beat
-  // one column-lane launch per op -- 13B s45 decoder layer at 2 rows: 88 vs 101 us)
-  if (!lin && n > 1 && knobs().cols_groups.load(std::memory_order_relaxed) && group_takes_cols_path(ops, n)) {
-    // a group on the column-lane kernel: ONE launch, the workgroups divided between the ops
-    sqllm::LaunchArgs a;
-    a.ev_start = e0;
-    a.ev_stop = e1;
-    a.x = ops[0].vec;
-    a.ga.n_seg = n;
-    memset(a.ga.seg, 0, sizeof(a.ga.seg));
-    int block = 0;
-    for (int i = 0; i < n; ++i) {
-      const sqllm_op* op = &ops[i];
-      int rc = validate(op);
-      if (rc == SQLLM_OK) rc = validate_csr_values(op, stream);
-      if (rc != SQLLM_OK) return rc;
-      if (op->vec != ops[0].vec || op->K != ops[0].K || op->bits != ops[0].bits || op->batch != ops[0].batch)
-        return SQLLM_E_GROUP;
-      if ((uint64_t)op->batch * (uint64_t)op->K >= (1ull << 31)) return SQLLM_E_SHAPE;  // 32-bit row offsets into vec
-      sqllm::Segment& sg = a.ga.seg[i];
-      sg.q = reinterpret_cast<const uint32_t*>(op->qweight);
-      sg.y = op->mul;
-      sg.lut = op->lookup_table;
-      sg.rows = op->rows;
-      sg.cols = op->cols;
-      sg.vals = op->vals;
-      sg.full_rows = op->topX > 0 ? op->full_rows : nullptr;
-      sg.full_idx = op->topX > 0 ? op->full_row_indices : nullptr;
-      make_plan_cols(op, &sg.gm, n);
-      a.ga.block0[i] = block;
-      block += (sg.gm.dense_block0 + sg.gm.dense_blocks + 7) / 8 * 8;
-    }
-    for (int i = n; i <= sqllm::kMaxSegments; ++i) a.ga.block0[i] = block;
-    return static_cast<int>(sqllm::launch_batched_cols(ops[0].bits, a, static_cast<hipStream_t>(stream)));
-  }
-  if (!lin && takes_small_split(&ops[0], n)) {
-    // up to 16 rows on the split matrix-core kernel: ONE launch for the whole group, sparse roles included
-    sqllm::LaunchArgs a;
-    a.ev_start = e0;
-    a.ev_stop = e1;
-    a.x = ops[0].vec;
-    a.ga.n_seg = n;
-    memset(a.ga.seg, 0, sizeof(a.ga.seg));
-    int block = 0;
-    // The dense ranges are ONE round of workgroups, as many as the chip holds at once: the top-X slabs (8 per op, padded)
-    // take their slots from the same count.  (Planned beside them, 20-50 dense workgroups of a 13B launch found no slot,
-    // started when the first ones left and ran as a second round of their own: 34 instead of 22 us per down_proj launch at
-    // 16 rows -- profiles/r05_small_split_timeline.txt.)
-    // With a workspace: vec transposed first (xT[k][rows]: the folded CSR walk and the top-X slabs then read ONE line per
-    // k for all the batch rows); without, they gather from vec itself.
-    bool any_sparse = false;
-    for (int i = 0; i < n; ++i) any_sparse = any_sparse || (ops[i].nnz > 0 && ops[i].rows) || (ops[i].full_rows && ops[i].topX > 0);
-    const bool want_xT = any_sparse && ops[0].batch > 0 && ops[0].K > 0 && ops[0].vec && (reinterpret_cast<uintptr_t>(ops[0].vec) & 15u) == 0 &&
-                         knobs().sparse_transpose.load(std::memory_order_relaxed);  // (the transposition reads vec 16 bytes at a time)
-    // (vec transposed for the sparse terms, then its bf16 planes for the dense term: sqllm_prepare_small writes both)
-    const int64_t xt_only = want_xT ? sqllm::transpose_small_bytes(ops[0].batch, ops[0].K) : 0;
-    const bool want_planes = want_xT && knobs().small_planes.load(std::memory_order_relaxed);
-    const int64_t xt_bytes = xt_only + (want_planes ? sqllm::small_planes_bytes(ops[0].K) : 0);
-    float* xT = nullptr;
-    struct Scratch {  // the workspace-less names only: stream-ordered scratch, as for the wider batches (never inside a capture:
-      void* p = nullptr;  // its memory nodes cost more than the gathers -- profiles/r04_small_batch_layer.txt; never for a `_ws`
-                          // entry point: those allocate nothing up to 16 rows and leave the default pool alone -- the walk gathers)
-      hipStream_t s = nullptr;
-      ~Scratch() { if (p) (void)hipFreeAsync(p, s); }
-    } own;
-    if (want_xT && ws && (reinterpret_cast<uintptr_t>(ws) & 15u) == 0 && ws_bytes >= xt_bytes) {
-      xT = static_cast<float*>(ws);
-    } else if (want_xT && !ws_entry) {
-      own.s = static_cast<hipStream_t>(stream);
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(own.s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
-        keep_scratch_in_pool();
-        if (hipMallocAsync(&own.p, (size_t)xt_bytes, own.s) == hipSuccess && own.p) xT = static_cast<float*>(own.p);
-        else { (void)hipGetLastError(); own.p = nullptr; }
-      } else {
-        (void)hipGetLastError();
-      }
-    }
-    const bool with_xT = xT != nullptr;
-    int reserve = 0;
-    if (with_xT || knobs().small_reserve_topx.load(std::memory_order_relaxed))
-      for (int i = 0; i < n; ++i) reserve += (small_topx_blocks(&ops[i], with_xT, n) + 7) / 8 * 8;
-    for (int i = 0; i < n; ++i) {
-      const sqllm_op* op = &ops[i];
-      int rc = validate(op);
-      if (rc == SQLLM_OK) rc = validate_csr_values(op, stream);
-      if (rc != SQLLM_OK) return rc;
-      if (op->vec != ops[0].vec || op->K != ops[0].K || op->bits != ops[0].bits || op->batch != ops[0].batch) return SQLLM_E_GROUP;
-      if ((uint64_t)op->batch * (uint64_t)op->K >= (1ull << 31)) return SQLLM_E_SHAPE;  // 32-bit row offsets into vec
-      sqllm::Segment& sg = a.ga.seg[i];
-      fill_segment(op, &sg);
-      make_plan_mfma(op, &sg.gm, n, 0, small_wgs_per_cu_of(op), reserve);
-      sg.gm.topx_blocks = small_topx_blocks(op, with_xT, n);
-      fold_csr_into_dense(&sg.gm);
-      a.ga.block0[i] = block;
-      block += (sg.gm.dense_block0 + sg.gm.dense_blocks + 7) / 8 * 8;
-    }
-    for (int i = n; i <= sqllm::kMaxSegments; ++i) a.ga.block0[i] = block;
-    if (with_xT) {
-      if (!(g_experimental.skip_prepare_small && g_experimental.skip_prepare_small())) {  // (measurement library only: what the kernel in front costs)
-        const hipError_t e = want_planes
-                                 ? sqllm::prepare_small(ops[0].vec, xT, reinterpret_cast<char*>(xT) + xt_only, ops[0].batch, ops[0].K, static_cast<hipStream_t>(stream), e0)
-                                 : sqllm::transpose_small(ops[0].vec, xT, ops[0].batch, ops[0].K, static_cast<hipStream_t>(stream), e0);
-        if (e != hipSuccess) return static_cast<int>(e);
-        a.ev_start = nullptr;
-      }
-      a.xT = xT;
-      if (want_planes) a.planes = reinterpret_cast<char*>(xT) + xt_only;
-    }
-    if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: timeline buffer)
-    return static_cast<int>(sqllm::launch_small_split(ops[0].bits, a, static_cast<hipStream_t>(stream)));
-  }
-  if (!lin && (takes_mfma_path(&ops[0], n) || (n == 1 && takes_cols_path(&ops[0])))) {
-    // batched operators: one launch per op (the members of a group only share their input) of the
-    // matrix-core kernel (wide batches) or of the column-lane kernel (small ones)
-    const bool mfma = takes_mfma_path(&ops[0], n);
-    WideScratch wsc;  // (transposed vec for the CSR role, planes + slabs for the wide form: see the struct)
-    if (mfma) {
-      int rc = validate(&ops[0]);  // (its kernels read vec by batch and K: shape errors first)
-      if (rc != SQLLM_OK) return rc;
-      rc = wsc.acquire(ops, n, stream, &e0, ws, ws_bytes);
-      if (rc != SQLLM_OK) return rc;
-    }
-    float* const xT = wsc.xT;
-    const int Bp = wsc.Bp;
-    for (int i = 0; i < n; ++i) {
-      const sqllm_op* op = &ops[i];
-      int rc = validate(op);
-      if (rc == SQLLM_OK) rc = validate_csr_values(op, stream);
-      if (rc != SQLLM_OK) return rc;
-      if (op->vec != ops[0].vec || op->K != ops[0].K || op->bits != ops[0].bits || op->batch != ops[0].batch)
-        return SQLLM_E_GROUP;
-      if ((uint64_t)op->batch * (uint64_t)op->K >= (1ull << 31)) return SQLLM_E_SHAPE;  // 32-bit row offsets into vec
-      sqllm::LaunchArgs a;
-      a.ev_start = i == 0 ? e0 : nullptr;
-      a.ev_stop = i == n - 1 ? e1 : nullptr;
-      a.x = op->vec;
-      a.xT = (op->nnz > 0 && op->rows && op->cols && op->vals) ? xT : nullptr;
-      a.Bp = Bp;
-      a.planes = wsc.planes;
-      a.plane_flags = wsc.flags;
-      a.wide_slabs = wsc.slabs;
-      a.ga.n_seg = 1;
-      memset(a.ga.seg, 0, sizeof(a.ga.seg));
-      sqllm::Segment& sg = a.ga.seg[0];
-      sg.q = reinterpret_cast<const uint32_t*>(op->qweight);
-      sg.y = op->mul;
-      sg.lut = op->lookup_table;
-      sg.rows = op->rows;
-      sg.cols = op->cols;
-      sg.vals = op->vals;
-      sg.full_rows = op->topX > 0 ? op->full_rows : nullptr;
-      sg.full_idx = op->topX > 0 ? op->full_row_indices : nullptr;
-      a.wide = mfma && takes_wide_path(op, wsc.planes != nullptr, wsc.capturing);
-      if (a.wide) a.wide_full_units = make_plan_wide(op, &sg.gm);
-      else if (mfma) make_plan_mfma(op, &sg.gm);
-      else make_plan_cols(op, &sg.gm);
-      a.ga.block0[0] = 0;
-      for (int j = 1; j <= sqllm::kMaxSegments; ++j) a.ga.block0[j] = sg.gm.dense_block0 + sg.gm.dense_blocks;
-      if (mfma) {
-        // the sparse terms first, as a launch of their own (see sqllm_sparse_batched), then the dense term
-        // (running the two on different streams was tried: they do not overlap -- the dense kernel holds
-        // every CU's registers -- and the two event waits cost 14 us per op)
-        const bool sparse = sg.gm.csr_blocks + sg.gm.topx_blocks > 0;
-        // tile form: the sparse terms ride in the dense launch's grid (sqllm_fused_batched_split_all) -- always up to 32 rows
-        // (two workgroups per CU: 13B shapes 59-69 -> 55-57 us, 5120x5120 35-46 -> 28-38); from 33 rows, where the kernel
-        // takes a whole CU per workgroup, only while the sparse workgroups are fewer than the CUs (5120x5120 at 64 rows
-        // 81 -> 54 us; with 331 of them, 5120x13824, 112 -> 117: profiles/r04_mid_rows_fused_sparse.txt)
-        const bool may_fuse = sparse && !a.wide && knobs().mfma_split.load(std::memory_order_relaxed) &&
-                              knobs().mfma_fuse_sparse.load(std::memory_order_relaxed);
-        bool fuse_sparse = may_fuse && (op->batch <= 32 || sg.gm.csr_blocks + sg.gm.topx_blocks < cu_count());
-        if (may_fuse && !fuse_sparse && op->batch <= 64) {
-          // 33-64 rows with more sparse workgroups than CUs: two passes of 32 rows on the kernel that leaves room for two
-          // workgroups per CU, sparse terms in its grid, instead of one 64-row pass + their own launch
-          // (profiles/r04_mid_rows_fused_sparse.txt, "mb2")
-          a.row_blocks = 2;
-          make_plan_mfma(op, &sg.gm, 1, 2);
-          for (int j = 1; j <= sqllm::kMaxSegments; ++j) a.ga.block0[j] = sg.gm.dense_block0 + sg.gm.dense_blocks;
-          fuse_sparse = true;
-        }
-        if (fuse_sparse) {
-          rc = static_cast<int>(sqllm::launch_batched_mfma_split_all(op->bits, a, static_cast<hipStream_t>(stream)));
-          if (rc != SQLLM_OK) return rc;
-          continue;
-        }
-        if (sparse) {
-          sqllm::LaunchArgs as = a;
-          as.ev_stop = nullptr;
-          if (g_experimental.decorate) g_experimental.decorate(&as);  // (measurement library: timeline probe, tools/timeline.py --batch)
-          rc = static_cast<int>(sqllm::launch_batched_sparse(as, static_cast<hipStream_t>(stream)));
-          if (rc != SQLLM_OK) return rc;
-          a.ev_start = nullptr;
-        }
-        rc = static_cast<int>(knobs().mfma_split.load(std::memory_order_relaxed)
-                                  ? sqllm::launch_batched_mfma_split(op->bits, a, static_cast<hipStream_t>(stream))
-                                  : sqllm::launch_batched_mfma(op->bits, a, static_cast<hipStream_t>(stream)));
-      } else {
-        rc = static_cast<int>(sqllm::launch_batched_cols(op->bits, a, static_cast<hipStream_t>(stream)));
-      }
-      if (rc != SQLLM_OK) return rc;
-    }
-    return SQLLM_OK;
-  }
-  if (!lin && g_experimental.route) {  // (measurement library: the measured-and-not-adopted batch-1 kernels)
-    int rc = SQLLM_OK;
-    if (g_experimental.route(ops, n, stream, e0, e1, &rc)) return rc;
-  }
   sqllm_op tmp[sqllm::kMaxSegments];
   if (lin) {
     for (int i = 0; i < n; ++i) {
@@ -1014,60 +1000,100 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
     }
     ops = tmp;
   }
-  sqllm::LaunchArgs a;
-  a.linear = lin != nullptr;
-  a.ev_start = e0;
-  a.ev_stop = e1;
-  a.x = ops[0].vec;
-  a.ga.n_seg = n;
-  int block = 0;
-  for (int i = 0; i < n; ++i) {
-    const sqllm_op* op = &ops[i];
-    int rc = validate(op);
-    if (rc == SQLLM_OK) rc = validate_csr_values(op, stream);
+  const Route route = route_of(ops, n, lin != nullptr);
+  if (route == kFusedTiles && g_experimental.route) {  // (measurement library: the measured-and-not-adopted batch-1 kernels)
+    int rc = SQLLM_OK;
+    if (g_experimental.route(ops, n, stream, e0, e1, &rc)) return rc;
+  }
+  int rc = validate_group(ops, n, stream, route);
+  if (rc != SQLLM_OK) return rc;
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  ScratchFacts facts;
+  WideScratch wide;    // (matrix-core kernel: transposed vec for the CSR role, planes + slabs for the wide form)
+  SmallScratch small;  // (fused small launch)
+  if (route == kPerOpMfma) {
+    rc = wide.acquire(ops, n, stream, &e0, ws, ws_bytes);
     if (rc != SQLLM_OK) return rc;
-    if (op->vec != ops[0].vec || op->K != ops[0].K || op->bits != ops[0].bits ||
-        (op->batch <= 0 ? 1 : op->batch) != (ops[0].batch <= 0 ? 1 : ops[0].batch))
-      return SQLLM_E_GROUP;
-    sqllm::Segment& sg = a.ga.seg[i];
-    fill_segment(op, &sg);
-    // fused linear: a column's K slices + the CSR chunks its row can be spread over must fit the 6-bit count
-    const int csr_bound = (op->rows && op->nnz > 0) ? op->K / sqllm::kCsrChunk + 2 : 0;
-    make_plan(op, &sg.gm, n, lin ? (sqllm::kMaxContrib - csr_bound > 1 ? sqllm::kMaxContrib - csr_bound : 1) : sqllm::kMaxSlices);
-    if (lin) {
-      // accumulate into the workspace plane; op->mul is the fp16 result
-      sg.y = reinterpret_cast<float*>(lin[i].workspace);
-      sg.out16 = op->mul;
-      sg.bias = lin[i].bias;
-      // the top-X rows are always handled inside the dense workgroups: no top-X role in the grid
-      sg.gm.topx_blocks = 0;
-      if (!(sg.gm.sparse_last & 1)) sg.gm.dense_block0 = (sg.gm.csr_blocks + 7) / 8 * 8;
-      else sg.gm.dense_block0 = sg.gm.csr_blocks;
-      // the 55-bit sum field holds at most kMaxContrib clamped contributions per column: the K
-      // slices and one per CSR chunk a row can be spread over
-      if (sg.gm.k_slices + (sg.gm.csr_blocks ? op->K / sqllm::kCsrChunk + 2 : 0) > sqllm::kMaxContrib)
-        return SQLLM_E_SHAPE;
-    }
-    a.ga.block0[i] = block;
-    // pad every segment to a multiple of 8 workgroups: dense ids keep their XCD alignment
-    block += (sg.gm.dense_block0 + sg.gm.dense_blocks + 7) / 8 * 8;
+    facts.xT = wide.xT != nullptr;
+    facts.planes = wide.planes != nullptr;
+    facts.capturing = wide.capturing;
+  } else if (route == kFusedSmall) {
+    small.acquire(ops, n, stream, ws, ws_bytes, ws_entry);
+    facts.xT = small.xT != nullptr;
   }
-  for (int i = n; i <= sqllm::kMaxSegments; ++i) a.ga.block0[i] = block;
-  for (int i = n; i < sqllm::kMaxSegments; ++i) memset(&a.ga.seg[i], 0, sizeof(sqllm::Segment));
-  if (!lin) {
-    const bool widened = widen_csr_chunks(a.ga.seg, n, ops[0].bits, ops[0].batch, &block);
-    if (widened) {
-      int at = 0;
-      for (int i = 0; i < n; ++i) {
-        a.ga.block0[i] = at;
-        at += (a.ga.seg[i].gm.dense_block0 + a.ga.seg[i].gm.dense_blocks + 7) / 8 * 8;
-      }
-      for (int i = n; i <= sqllm::kMaxSegments; ++i) a.ga.block0[i] = at;
-    }
-    set_role_priority(a.ga.seg, n, ops[0].bits, ops[0].batch, block, widened);
+  GroupPlan plan;
+  plan_group(ops, n, route, facts, &plan);
+  if (plan.rc != SQLLM_OK) return plan.rc;
+  if (small.xT && !(g_experimental.skip_prepare_small && g_experimental.skip_prepare_small())) {  // (measurement library only: what the kernel in front costs)
+    const hipError_t e = small.planes ? sqllm::prepare_small(ops[0].vec, small.xT, small.planes, ops[0].batch, ops[0].K, s, e0)
+                                      : sqllm::transpose_small(ops[0].vec, small.xT, ops[0].batch, ops[0].K, s, e0);
+    if (e != hipSuccess) return static_cast<int>(e);
+    e0 = nullptr;
   }
-  if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: ablation bits, LDS pad, timeline buffer)
-  return static_cast<int>(sqllm::launch_fused(ops[0].bits, a, static_cast<hipStream_t>(stream)));
+  for (int l = 0; l < plan.n_launches; ++l) {
+    const LaunchPlan& lp = plan.launch[l];
+    const sqllm_op* op = &ops[lp.first];
+    sqllm::LaunchArgs a;
+    fill_args(&a, ops, lin, plan, lp);
+    a.ev_start = l == 0 ? e0 : nullptr;
+    a.ev_stop = l == plan.n_launches - 1 ? e1 : nullptr;
+    hipError_t e = hipSuccess;
+    switch (route) {
+      case kFusedTiles:
+      case kFusedLinear:
+        if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: ablation bits, LDS pad, timeline buffer)
+        e = sqllm::launch_fused(op->bits, a, s);
+        break;
+      case kColsGroup:
+      case kPerOpCols:
+        e = sqllm::launch_batched_cols(op->bits, a, s);
+        break;
+      case kFusedSmall:
+        a.xT = small.xT;
+        a.planes = small.planes;
+        if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: timeline buffer)
+        e = sqllm::launch_small_split(op->bits, a, s);
+        break;
+      case kPerOpMfma:
+        a.xT = (op->nnz > 0 && op->rows && op->cols && op->vals) ? wide.xT : nullptr;
+        a.Bp = wide.Bp;
+        a.planes = wide.planes;
+        a.plane_flags = wide.flags;
+        a.wide_slabs = wide.slabs;
+        if (lp.sparse_in_grid) {
+          e = sqllm::launch_batched_mfma_split_all(op->bits, a, s);
+          break;
+        }
+        if (lp.sparse_launch) {
+          sqllm::LaunchArgs as = a;
+          as.ev_stop = nullptr;
+          if (g_experimental.decorate) g_experimental.decorate(&as);  // (measurement library: timeline probe, tools/timeline.py --batch)
+          e = sqllm::launch_batched_sparse(as, s);
+          if (e != hipSuccess) return static_cast<int>(e);
+          a.ev_start = nullptr;
+        }
+        e = lp.split ? sqllm::launch_batched_mfma_split(op->bits, a, s) : sqllm::launch_batched_mfma(op->bits, a, s);
+        break;
+    }
+    if (e != hipSuccess) return static_cast<int>(e);
+  }
+  return SQLLM_OK;
+}
+
+// A pass as consecutive same-input groups: `ops` or `lins`, group g of group_sizes[g] members; *n_done = groups enqueued.
+static int launch_groups(const sqllm_op* ops, const sqllm_linear* lins, const int32_t* group_sizes, int32_t n_groups, sqllm_stream_t stream,
+                         int32_t* n_done, void* ws = nullptr, int64_t ws_bytes = 0, bool ws_entry = false) {
+  if (n_done) *n_done = 0;
+  if (n_groups < 0 || (n_groups > 0 && ((!ops && !lins) || !group_sizes))) return SQLLM_E_NULL;
+  int32_t at = 0;
+  for (int32_t g = 0; g < n_groups; ++g) {
+    if (group_sizes[g] < 1) return SQLLM_E_GROUP;
+    int rc = launch_group_with_events(ops ? ops + at : nullptr, group_sizes[g], stream, nullptr, nullptr, lins ? lins + at : nullptr, ws, ws_bytes, ws_entry);
+    if (rc != SQLLM_OK) return rc;
+    at += group_sizes[g];
+    if (n_done) *n_done = g + 1;
+  }
+  return SQLLM_OK;
 }
 
 int sqllm_linear_f16(const sqllm_linear* lin, sqllm_stream_t stream) {
@@ -1077,17 +1103,7 @@ int sqllm_linear_f16(const sqllm_linear* lin, sqllm_stream_t stream) {
 
 int sqllm_linear_f16_groups(const sqllm_linear* lins, const int32_t* group_sizes, int32_t n_groups,
                             sqllm_stream_t stream, int32_t* n_done) {
-  if (n_done) *n_done = 0;
-  if (n_groups < 0 || (n_groups > 0 && (!lins || !group_sizes))) return SQLLM_E_NULL;
-  int32_t at = 0;
-  for (int32_t g = 0; g < n_groups; ++g) {
-    if (group_sizes[g] < 1) return SQLLM_E_GROUP;
-    int rc = launch_group_with_events(nullptr, group_sizes[g], stream, nullptr, nullptr, lins + at);
-    if (rc != SQLLM_OK) return rc;
-    at += group_sizes[g];
-    if (n_done) *n_done = g + 1;
-  }
-  return SQLLM_OK;
+  return launch_groups(nullptr, lins, group_sizes, n_groups, stream, n_done);
 }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
@@ -1100,29 +1116,16 @@ int sqllm_launch_group(const sqllm_op* ops, int32_t n_ops, sqllm_stream_t stream
 
 int sqllm_launch_groups(const sqllm_op* ops, const int32_t* group_sizes, int32_t n_groups,
                         sqllm_stream_t stream, int32_t* n_done) {
-  if (n_done) *n_done = 0;
-  if (n_groups < 0 || (n_groups > 0 && (!ops || !group_sizes))) return SQLLM_E_NULL;
-  int32_t at = 0;
-  for (int32_t g = 0; g < n_groups; ++g) {
-    int rc = launch_group_with_events(ops + at, group_sizes[g], stream, nullptr, nullptr);
-    if (rc != SQLLM_OK) return rc;
-    at += group_sizes[g];
-    if (n_done) *n_done = g + 1;
-  }
-  return SQLLM_OK;
+  return launch_groups(ops, nullptr, group_sizes, n_groups, stream, n_done);
 }
 
+// what a `_ws` launch of the group can use: the scratch its route asks for (the launch asks the same code)
 int64_t sqllm_workspace_bytes(const sqllm_op* ops, int32_t n_ops) {
   if (!ops || n_ops < 1 || ops[0].batch < 2 || ops[0].K <= 0) return 0;  // (batch 1: one kernel, no scratch)
   int64_t need = 0;
-  if (takes_small_split(&ops[0], n_ops)) {
-    bool any_sparse = false;
-    for (int i = 0; i < n_ops; ++i) any_sparse = any_sparse || (ops[i].nnz > 0 && ops[i].rows) || (ops[i].full_rows && ops[i].topX > 0);
-    if (any_sparse && knobs().sparse_transpose.load(std::memory_order_relaxed))
-      need = sqllm::transpose_small_bytes(ops[0].batch, ops[0].K) + (knobs().small_planes.load(std::memory_order_relaxed) ? sqllm::small_planes_bytes(ops[0].K) : 0);
-  } else if (takes_mfma_path(&ops[0], n_ops)) {
-    need = (int64_t)WideScratch::layout(ops, n_ops, false).total();
-  }
+  const Route route = route_of(ops, n_ops, false);
+  if (route == kFusedSmall) need = SmallScratch::layout(ops, n_ops).total();
+  else if (route == kPerOpMfma) need = (int64_t)WideScratch::layout(ops, n_ops, false).total();
   return (need + 255) / 256 * 256;
 }
 
@@ -1136,16 +1139,7 @@ int sqllm_launch_group_ws(const sqllm_op* ops, int32_t n_ops, void* workspace, i
 
 int sqllm_launch_groups_ws(const sqllm_op* ops, const int32_t* group_sizes, int32_t n_groups, void* workspace,
                            int64_t workspace_bytes, sqllm_stream_t stream, int32_t* n_done) {
-  if (n_done) *n_done = 0;
-  if (n_groups < 0 || (n_groups > 0 && (!ops || !group_sizes))) return SQLLM_E_NULL;
-  int32_t at = 0;
-  for (int32_t g = 0; g < n_groups; ++g) {
-    int rc = launch_group_with_events(ops + at, group_sizes[g], stream, nullptr, nullptr, nullptr, workspace, workspace_bytes, true);
-    if (rc != SQLLM_OK) return rc;
-    at += group_sizes[g];
-    if (n_done) *n_done = g + 1;
-  }
-  return SQLLM_OK;
+  return launch_groups(ops, nullptr, group_sizes, n_groups, stream, n_done, workspace, workspace_bytes, true);
 }
 
 int sqllm_launch_sequence(const sqllm_op* ops, int32_t n_ops, sqllm_stream_t stream, int32_t* n_done) {

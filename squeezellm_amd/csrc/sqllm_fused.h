@@ -205,7 +205,8 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i16 = lane & 15, grp = lane >> 4;
   // Dense waves above the sparse roles' waves in the SIMD's issue arbitration, where the host asked for it (sqllm_capi.hip:
-  // set_dense_priority -- 3-bit batch-1 launches with sparse roles whose workgroups are all resident at once).
+  // set_role_priority -- dense_prio 1: 3-bit batch-1 launches with sparse roles whose workgroups are all resident at once; 2 raises the
+  // CSR / top-X workgroups' waves instead, where the kernel enters those roles).
   if (sg.gm.dense_prio == 1) __builtin_amdgcn_s_setprio(1);
   const int ct = bid % n_col_tiles;
   const int ks = bid / n_col_tiles;

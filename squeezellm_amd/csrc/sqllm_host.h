@@ -1,5 +1,5 @@
 // sqllm_host.h -- internal interface of the host layer (sqllm_capi.hip): what the measurement library's code
-// (csrc/experimental/) needs from it -- options, validation, the launch planner -- and the hooks through which
+// (csrc/experimental/) needs from it -- options, validation, the batch-tile geometry (make_plan) -- and the hooks through which
 // that code takes part in option handling and launch routing.  The product library leaves every hook null.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,10 +20,12 @@ struct Knobs {
   std::atomic<int> cu_count{0};
   std::atomic<int> sparse_last{0};
   std::atomic<int> cols_groups{1};  // 0: a group of ops never takes the column-lane kernel (as before round 3)
-  // Routing of the *_batched operators by batch size (0 = the measured defaults, which depend on the bit width:
-  // 13B gate/up shape, profiles/r02_batch_paths_*.txt):
-  //   4-bit: 2..4 rows column-lane kernel (or batch tiles: cols_pays), 5+ matrix cores (round 4; before: 5..8 batch tiles)
-  //   3-bit: 2..8 rows column-lane kernel, 9+ matrix cores
+  // Routing of the operators by batch size (0 = the measured defaults, which depend on the bit width, the shape and what shares
+  // the launch -- sqllm_capi.hip: route_of and the rules it asks; first measured on the 13B gate/up shape, profiles/r02_batch_paths_*.txt):
+  //   1 row: the fused kernel, or the column-lane kernel by launch shape (cols_pays_batch1)
+  //   4-bit: 2..4 rows (single ops of >= 20 MB: ..6) column-lane kernel where it pays (cols_pays), else batch tiles of exactly 2..6
+  //          rows; matrix cores from 7 rows (a small op alone in its launch: 8-row tile up to 8 rows, matrix cores from 9: mfma_min_batch_of)
+  //   3-bit: 2..8 rows column-lane kernel where it pays, else batch tiles; matrix cores from 9 rows
   std::atomic<int> mfma_min_batch{0};  // rows from which the matrix-core kernel takes over
   std::atomic<int> cols_min_batch{0};  // the column-lane kernel serves cols_min_batch .. cols_max_batch rows (0 = default: 2)
   std::atomic<int> cols_max_batch{0};

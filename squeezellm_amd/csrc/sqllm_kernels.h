@@ -60,7 +60,7 @@ struct KernelGeom {
   int k_slices;         // ceil(units_total / units_per_wg)
   int dense_blocks;     // col_tiles * k_slices
   int dense_block0;     // first dense blockIdx.x (csr + topx blocks rounded up to a multiple of 8)
-  int csr_blocks;       // ceil(nnz / kCsrChunk), 0 without a sparse term
+  int csr_blocks;       // ceil(nnz / kCsrChunk) -- of 2 * kCsrChunk with csr_wide --, 0 without a sparse term or with fold_csr
   int topx_blocks;      // ceil(K / kTopxRows), 0 without a top-X term
   int nnz, topX;
   int sparse_last;      // 1: CSR / top-X workgroups come after the dense ones in the grid

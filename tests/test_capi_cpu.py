@@ -457,3 +457,36 @@ def test_product_sources_carry_no_measurement_routing():
     for name in (b"stream", b"pair4", b"ablate", b"lds_pad", b"pass_poll_sleep", b"skip_prepare_small"):
         assert lib.sqllm_set_option(name, 1) == -7, name  # SQLLM_E_OPTION
     assert "TIMING" not in src and "skip_prepare_small()" in src  # the one timing-only mode sits behind a (null) hook
+
+
+def test_plan_query_reports_what_is_launched(tmp_path):
+    """sqllm_plan_query and the launch ask ONE planner (csrc/sqllm_capi.hip: plan_group).  The host layer is built as plain C++
+    against recording launchers (tests/native/launch_recorder.cpp: no device code, nothing is launched, operand pointers are
+    fake) and run as a child process: for every single op of bits x shapes x batches x sparse terms, launched through
+    sqllm_launch_ws with an ample workspace on a part of 256 CUs, the geometry of the last dense launch equals the plan."""
+    import shutil
+
+    from squeezellm_amd import build as B
+
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found: the launch recorder cannot be built")
+    assert "sqllm_capi.hip" in B.SOURCES
+    host = [os.path.join(B.CSRC, "sqllm_capi.hip")]  # the host layer: every other product source is device code and its launchers
+    exe = str(tmp_path / "launch_recorder")
+    # (-x hip --cuda-host-only: the host side alone, with the HIP headers and runtime library the compiler driver knows)
+    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", f"-I{B.INCLUDE}", f"-I{B.CSRC}", *host,
+                        os.path.join(H.ROOT, "tests", "native", "launch_recorder.cpp"), "-o", exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    cases = [ln for ln in out.stdout.splitlines() if ln.startswith("case ")]
+    shapes, batches, sparse = 15, 22, 6
+    assert len(cases) == 2 * shapes * batches * sparse  # no case left out (no batch * K of the grid reaches 2^31)
+    routes = set()
+    for ln in cases:
+        f = dict(kv.split("=") for kv in ln.split()[1:])
+        assert f["rc"] == "0,0" and int(f["dense_launches"]) == 1, ln
+        assert f["launched"] == f["plan"], ln  # col_tiles, k_slices, units_per_wg, dense_blocks, csr_blocks, topx_blocks
+        routes.add(f["via"])
+    assert routes == {"launch_fused", "launch_batched_cols", "launch_small_split", "launch_batched_mfma_split", "launch_batched_mfma_split_all"}

@@ -1,7 +1,16 @@
 #!/bin/bash
-# build_variant.sh <csrc dir> <name>: all product sources of <csrc dir> with build.py's flags -> squeezellm_amd/ab/lib<name>.so
+# build_variant.sh <csrc dir> <name>: all product sources of <csrc dir> -> squeezellm_amd/ab/lib<name>.so, with the compiler, architecture,
+# flags and source list of squeezellm_amd/build.py (a variant built any other way invalidates the same-box A/B it is built for)
 set -e
-C=$1; N=$2; R=/root/repo
-mkdir -p $R/squeezellm_amd/ab
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -fno-gpu-rdc -Wall -Wno-unused-function -mllvm -amdgpu-kernarg-preload-count=16 -shared -I$R/include -I$C -I$C/experimental $C/sqllm_kernels.hip $C/sqllm_mfma_split.hip $C/sqllm_mfma_wide.hip $C/sqllm_capi.hip -o $R/squeezellm_amd/ab/lib$N.so
-ls -la $R/squeezellm_amd/ab/lib$N.so
+C=$(cd "$1" && pwd); N=$2
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
+mkdir -p "$R/squeezellm_amd/ab"
+cd "$R"
+python3 -c '
+import os, subprocess, sys
+from squeezellm_amd import build as B
+csrc, out = sys.argv[1:3]
+subprocess.run([B.hipcc(), f"--offload-arch={B.ARCH}", *B.FLAGS, "-shared", f"-I{B.INCLUDE}", f"-I{csrc}", f"-I{csrc}/experimental",
+                *[os.path.join(csrc, s) for s in B.SOURCES], "-o", out], check=True)
+' "$C" "$R/squeezellm_amd/ab/lib$N.so"
+ls -la "$R/squeezellm_amd/ab/lib$N.so"
