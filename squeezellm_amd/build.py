@@ -27,8 +27,8 @@ SOURCES = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "
 EXPERIMENTAL = os.path.join(CSRC, "experimental")
 EXPERIMENT_SOURCES = ["experimental/sqllm_ablation.hip", "experimental/sqllm_stream.hip", "experimental/sqllm_pair.hip",
                       "experimental/sqllm_pass.hip", "experimental/sqllm_experimental.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("sqllm_kernels.h", "sqllm_decode.h", "sqllm_roles.h", "sqllm_fused.h", "sqllm_split_common.h", "sqllm_host.h", "sqllm_probe.h")] + [os.path.join(INCLUDE, "sqllm_hip.h")]
-EXPERIMENT_HEADERS = [os.path.join(EXPERIMENTAL, h) for h in ("sqllm_pass.h", "sqllm_pass_api.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("sqllm_kernels.h", "sqllm_decode.h", "sqllm_roles.h", "sqllm_fused.h", "sqllm_ranges.h", "sqllm_split_common.h", "sqllm_host.h", "sqllm_probe.h")] + [os.path.join(INCLUDE, "sqllm_hip.h")]
+EXPERIMENT_HEADERS = [os.path.join(EXPERIMENTAL, h) for h in ("sqllm_pass.h", "sqllm_pass_api.h", "sqllm_stream_api.h")]
 ARCH = "gfx950"
 # -amdgpu-kernarg-preload-count: the kernels' leading explicit arguments (the vec pointer) arrive in SGPRs instead of
 # through the first scalar load (gfx950 preloads up to 16 dwords; the by-value descriptor block cannot be preloaded):

@@ -16,6 +16,7 @@
 #include "sqllm_kernels.h"
 #include "sqllm_pass.h"
 #include "sqllm_pass_api.h"
+#include "sqllm_stream_api.h"
 
 #ifndef SQLLM_ABLATION_BUILD
 #error "csrc/experimental/ belongs to the measurement library (python -m squeezellm_amd.build --ablation)"

@@ -34,6 +34,7 @@
 
 #include "sqllm_decode.h"
 #include "sqllm_roles.h"
+#include "sqllm_stream_api.h"
 
 namespace sqllm {
 

@@ -308,9 +308,7 @@ static void cut_ranges(sqllm::KernelGeom* gm, int bits, int ops_in_launch, int s
   if (upw > 0x3fffffff) upw = 0x3fffffff / step * step;
   gm->units_per_wg = (int)upw;
   gm->k_slices = (int)((gm->units_total + upw - 1) / upw);  // pieces per column tile (reported by plan_query)
-  // (the kernels recognise the tile-aligned cut by dense_blocks == col_tiles * k_slices; a contiguous cut that happens
-  // to satisfy the same equation is then READ as tile-aligned -- ranges of units_per_wg units that restart at every
-  // tile -- which covers every unit exactly once as well: tests/test_capi_cpu.py fuzzes both readings)
+  // (how the kernels tell the two cuts apart, and why either reading covers every unit once: sqllm_ranges.h, units_stride_of)
   gm->dense_blocks = aligned ? gm->col_tiles * gm->k_slices : (int)((total_units + upw - 1) / upw);
   gm->sparse_last = 0;
   place_dense(gm);

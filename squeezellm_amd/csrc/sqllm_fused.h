@@ -55,6 +55,7 @@
 #include "sqllm_kernels.h"
 
 #include "sqllm_decode.h"
+#include "sqllm_ranges.h"
 #include "sqllm_roles.h"
 
 namespace sqllm {
@@ -490,23 +491,10 @@ sqllm_fused_matvec(const void* xv, const GroupArgs ga) {
   // prologue a chain of 6-8 such loads (block0 -> s -> sparse_last -> dense_block0 -> dense_blocks ->
   // ... -> q, lut) in front of the first vector load of every workgroup.  So: ONE round of loads
   // fetches vec's address, the block table and -- speculatively -- the whole of segment 0 into
-  // registers; a workgroup of another segment pays a second round for its own descriptor.
-  Segment sg = ga.seg[0];
-  const int n_seg = ga.n_seg, blk1 = ga.block0[1], blk2 = ga.block0[2], blk3 = ga.block0[3];
-  asm volatile("" ::SQLLM_SEG_OPERANDS(sg), "s"(x), "s"(n_seg), "s"(blk1), "s"(blk2), "s"(blk3));
-  __builtin_amdgcn_sched_barrier(0);  // (or the scheduler starts on the block table after the first few loads, waits, and issues the rest behind that wait)
-  // which op of the launch this workgroup belongs to (wave-uniform; 1 segment = a plain op)
-  int s = 0, base = 0;
-  if (n_seg > 1 && (int)blockIdx.x >= blk1) { s = 1; base = blk1; }
-  if (n_seg > 2 && (int)blockIdx.x >= blk2) { s = 2; base = blk2; }
-  if (n_seg > 3 && (int)blockIdx.x >= blk3) { s = 3; base = blk3; }
-  s = __builtin_amdgcn_readfirstlane(s);
-  if (s != 0) {
-    sg = ga.seg[s];
-    asm volatile("" ::SQLLM_SEG_OPERANDS(sg));
-  }
+  // registers; a workgroup of another segment pays a second round for its own descriptor (pick_segment).
+  Segment sg;
+  const int bid = pick_segment(ga, x, sg);
   const KernelGeom& gm = sg.gm;
-  const int bid = blockIdx.x - base;
   const int b0 = blockIdx.y * BT;
   int nb = gm.batch - b0;
   if (nb > BT) nb = BT;
@@ -546,13 +534,7 @@ inline hipError_t launch_inst(const LaunchArgs& a, hipStream_t stream) {
   const int batch = a.ga.seg[0].gm.batch;
   dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
   auto kern = sqllm_fused_matvec<BITS, BT, WAVES, ABL, LIN, SHORT>;
-  if (a.ev_start || a.ev_stop) {
-    // same kernel, with the dispatch's own begin/end timestamps exposed through two events
-    hipExtLaunchKernelGGL(kern, grid, dim3(WAVES * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, 0, a.x, a.ga);
-  } else {
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), a.lds_pad, stream, a.x, a.ga);
-  }
-  return hipGetLastError();
+  return launch_kernel(kern, grid, dim3(WAVES * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga);
 }
 
 }  // namespace sqllm

@@ -117,35 +117,6 @@ struct LaunchArgs {
   int row_blocks = 0;  // tile form: blocks of 16 rows per pass (1, 2 or 4); 0 = mfma_row_blocks(batch)
 };
 
-// ---- streaming batch-1 kernel (sqllm_stream.hip) ----
-constexpr int kStreamPieces4 = 2;  // 64-column tiles one workgroup's range may touch (codebook tables resident at once), 4-bit
-constexpr int kStreamPieces3 = 2;  // ... 3-bit (32 KiB pair tables)
-
-struct StreamSeg {  // one op of the launch, dense term only
-  const uint32_t* q;
-  float* y;
-  const float* lut;
-  int N;
-  int tile0;  // index of the op's first tile in the launch's flattened tile space (INT_MAX: unused slot)
-};
-
-// Dense part of a streaming launch: the ops' 64-column tiles back to back, each tile `steps_per_tile`
-// steps long (a step = 4 units = what one wave load covers), cut into ranges of `steps_per_wg` steps.
-struct StreamArgs {
-  const float* x;
-  int K;
-  int units_total;     // K / 8 (4-bit) or K / 32 (3-bit)
-  int steps_per_tile;  // ceil(units_total / 4)
-  int steps_per_wg;
-  int total_steps;     // tiles of all ops * steps_per_tile
-  int dense_block0;    // first dense workgroup id (the sparse-role workgroups come first)
-  int n_dense;         // dense workgroups
-  int n_seg;
-  uint32_t s_magic;    // ceil(2^32 / steps_per_tile): tile of a step = mulhi(step, s_magic)
-  StreamSeg seg[kMaxSegments];
-  unsigned long long* probe;  // measurement builds: 8 timestamps per workgroup (tools/timeline.py); null otherwise
-};
-
 // batch rows handled per weight pass for a given batch size (template instantiations 1/2/4/8)
 inline int batch_tile(int batch) { return batch <= 1 ? 1 : batch == 2 ? 2 : batch <= 4 ? 4 : 8; }
 // ... of the fused batch-tile kernel behind the OPERATOR names (sqllm_fused_matvec<BITS, BT>, not the fused linear): a tile
@@ -157,10 +128,6 @@ inline int mfma_row_blocks(int batch) { return batch <= 16 ? 1 : batch <= 32 ? 2
 
 hipError_t launch_fused(int bits, const LaunchArgs& a, hipStream_t stream);
 extern bool (*g_fused_variant)(int bits, const LaunchArgs& a, hipStream_t stream, hipError_t* err);  // measurement library hook (null in the product)
-hipError_t launch_pair4(const LaunchArgs& a, hipStream_t stream);  // 4-bit, batch 1, operator launches: column-pair tables, 16-wave workgroups
-// `ga`: the sparse roles of the launch (block0[] = prefix over csr + top-X workgroups only)
-hipError_t launch_stream(int bits, const StreamArgs& sa, const GroupArgs& ga, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
-                         int ablate);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid
@@ -178,12 +145,14 @@ hipError_t split_vec(const float* x, void* planes, uint32_t* flags, int batch, i
 constexpr int kSmallSplitRows = 16;  // rows up to which a group of ops runs as ONE launch on the split matrix-core kernel (all three terms)
 hipError_t launch_small_split(int bits, const LaunchArgs& a, hipStream_t stream);
 hipError_t transpose_vec(const float* x, float* xT, int batch, int K, int Bp, hipStream_t stream, hipEvent_t ev_start);
+// rows of the small transposed vec (2..16 batch rows rounded up to a power of two), as its logarithm
+constexpr int small_rows_log2(int batch) { return batch <= 2 ? 1 : batch <= 4 ? 2 : batch <= 8 ? 3 : 4; }
 // 2..16 rows: xT[k][rp], rp = the batch rounded up to a power of two (K * rp floats)
 hipError_t transpose_small(const float* x, float* xT, int batch, int K, hipStream_t stream, hipEvent_t ev_start);
 // ... + vec as three bf16 planes in fragment order, row block 0 (K / 32 + 1 k blocks of 3 KB; planes 16-byte aligned behind xT)
 hipError_t prepare_small(const float* x, float* xT, void* planes, int batch, int K, hipStream_t stream, hipEvent_t ev_start);
 inline int64_t small_planes_bytes(int K) { return (int64_t)(K / 32 + 1) * 3072; }
-inline int64_t transpose_small_bytes(int batch, int K) { return (int64_t)K * (batch <= 2 ? 2 : batch <= 4 ? 4 : batch <= 8 ? 8 : 16) * 4; }
+inline int64_t transpose_small_bytes(int batch, int K) { return ((int64_t)K << small_rows_log2(batch)) * 4; }
 hipError_t launch_batched_sparse(const LaunchArgs& a, hipStream_t stream);
 hipError_t check_csr(const int* rows, int N, int nnz, hipStream_t stream, int* bad);
 

@@ -108,9 +108,7 @@ __device__ __forceinline__ void dense_role_mfma(const float* __restrict__ x, con
   // ---- this workgroup's share: units [bid * units_per_wg, + units_per_wg) of the FLATTENED
   // (column tile, unit) space -- every workgroup the same number of units whatever N and K are, all
   // of them resident at once (one round, no tail).  A range that crosses a tile boundary is worked
-  // off as two pieces (codebooks restaged, sums flushed in between). ----
-  // (a tile is units_stride long in the flattened space: units_total, or -- tile-aligned ranges, see dense_role_cols --
-  // a whole number of ranges)
+  // off as two pieces (codebooks restaged, sums flushed in between; units_stride: see units_stride_of). ----
   const unsigned total = (unsigned)n_col_tiles * (unsigned)units_stride;
   unsigned gpos = (unsigned)bid * (unsigned)units_per_wg;
   unsigned gend = gpos + (unsigned)units_per_wg;
@@ -347,8 +345,7 @@ sqllm_fused_batched(const float* x, const GroupArgs ga) {
   const KernelGeom& gm = sg.gm;
   const int m0 = blockIdx.y * 16 * MB;
   dense_role_mfma<BITS, MB, WAVES>(x, reinterpret_cast<const u32x4*>(sg.q), sg.y, sg.lut, gm.K, gm.N, gm.batch, m0,
-                                   (int)blockIdx.x, gm.col_tiles, gm.units_total, gm.units_per_wg,
-                                   gm.dense_blocks == gm.col_tiles * gm.k_slices ? gm.k_slices * gm.units_per_wg : gm.units_total, lds);
+                                   (int)blockIdx.x, gm.col_tiles, gm.units_total, gm.units_per_wg, units_stride_of(gm), lds);
 }
 
 // The sparse terms of a wide-batch op, as a launch of their own: inside the matrix-core kernel the
@@ -361,7 +358,7 @@ template <int WAVES>
 __global__ void __launch_bounds__(WAVES * 64)
 sqllm_sparse_batched(const float* x, const GroupArgs ga, const float* xT, int Bp, int pass_rows) {
   constexpr int T = WAVES * 64;
-  __shared__ __attribute__((aligned(16))) float lds[cmax(kCsrSpanMax + cmax(kCsrSpanMax, 64 * (kCsrXtSpan + 1) + 3 * kCsrChunk), kTopxLds)];
+  __shared__ __attribute__((aligned(16))) float lds[kWideSparseLdsFloats];
   const Segment sg = ga.seg[0];  // the whole descriptor in one round of scalar loads (see sqllm_fused_matvec)
   asm volatile("" ::SQLLM_SEG_OPERANDS(sg), "s"(x));
   __builtin_amdgcn_sched_barrier(0);
@@ -499,10 +496,8 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
   if constexpr (BITS == 4) { if (tid < 64) *reinterpret_cast<float*>(table + 16 * 256 + 4 * tid) = 0.f; }
   else { if (tid < 64) *reinterpret_cast<f32x2*>(table + 64 * 512 + 8 * tid) = f32x2{0.f, 0.f}; }
 
-  // The ranges live in a flattened (column tile, unit) space in which a tile is units_stride long: = units_total
-  // (contiguous ranges, some crossing a tile boundary: two pieces, two table builds) or, where the plan could cut
-  // every tile into a whole number of ranges, that number x units_per_wg (>= units_total: no range crosses, the
-  // last one of a tile is short).
+  // the pieces of this workgroup's range, walked as in dense_role_mfma (a range crossing a tile boundary: two pieces, two
+  // table builds; units_stride: see units_stride_of); the tile index is made wave-uniform here
   const unsigned total = (unsigned)n_col_tiles * (unsigned)units_stride;
   unsigned gpos = (unsigned)bid * (unsigned)units_per_wg;
   unsigned gend = gpos + (unsigned)units_per_wg;
@@ -659,6 +654,9 @@ sqllm_fused_cols(const float* x, const GroupArgs ga) {
   // up to kMaxSegments ops over the same vec (q/k/v, gate/up): workgroup ids [block0[s], block0[s+1]) belong to op s.
   // Segment 0's descriptor and the block table in one round of scalar loads (see sqllm_fused_matvec), another
   // segment's in one more.
+  // (A copy of pick_segment, sqllm_ranges.h, on purpose: this kernel reloads without readfirstlane and subtracts inside the
+  // reload's branch, and through the helper its generated code changes -- profiles/refactor_kernel_glue_isa.txt; re-test
+  // with tools/isa_compare.py before folding it in.)
   Segment sg = ga.seg[0];
   const int n_seg = ga.n_seg, blk1 = ga.block0[1], blk2 = ga.block0[2], blk3 = ga.block0[3];
   asm volatile("" ::SQLLM_SEG_OPERANDS(sg), "s"(x), "s"(n_seg), "s"(blk1), "s"(blk2), "s"(blk3));
@@ -680,6 +678,8 @@ sqllm_fused_cols(const float* x, const GroupArgs ga) {
   const int d = bid - gm.dense_block0;
   const int sp = bid < gm.dense_block0 ? bid : -1;
   if (d >= 0 && d < gm.dense_blocks) {
+    // (units_stride_of, sqllm_ranges.h, spelled out on purpose: through the helper this kernel's role dispatch compiles
+    // differently -- profiles/refactor_kernel_glue_isa.txt; re-test with tools/isa_compare.py before folding it in)
     dense_role_cols<BITS, BT, WAVES>(x, sg.q, sg.y, sg.lut, gm.K, gm.N, b0, nb, d, gm.col_tiles, gm.units_total,
                                      gm.units_per_wg,
                                      gm.dense_blocks == gm.col_tiles * gm.k_slices ? gm.k_slices * gm.units_per_wg : gm.units_total, lds);
@@ -723,18 +723,12 @@ static hipError_t launch_mfma_inst(const LaunchArgs& a, hipStream_t stream) {
   dim3 grid(gm.dense_blocks, (gm.batch + 16 * MB - 1) / (16 * MB));
   auto kern = sqllm_fused_batched<BITS, MB, kWaves>;
   const float* x = static_cast<const float*>(a.x);
-  if (a.ev_start || a.ev_stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, 0, x, a.ga);
-  else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, x, a.ga);
-  return hipGetLastError();
+  return launch_kernel(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, x, a.ga);
 }
 
 template <int BITS>
 static hipError_t launch_mfma_bits(const LaunchArgs& a, hipStream_t stream) {
-  switch (mfma_row_blocks(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_mfma_inst<BITS, 1>(a, stream);
-    case 2: return launch_mfma_inst<BITS, 2>(a, stream);
-    default: return launch_mfma_inst<BITS, 4>(a, stream);
-  }
+  return with_row_blocks(mfma_row_blocks(a.ga.seg[0].gm.batch), [&](auto mb) { return launch_mfma_inst<BITS, decltype(mb)::value>(a, stream); });
 }
 
 template <int BITS, int BT>
@@ -743,9 +737,7 @@ static hipError_t launch_cols_inst(const LaunchArgs& a, hipStream_t stream) {
   dim3 grid(a.ga.block0[a.ga.n_seg], (gm.batch + BT - 1) / BT);
   auto kern = sqllm_fused_cols<BITS, BT, kWaves>;
   const float* x = static_cast<const float*>(a.x);
-  if (a.ev_start || a.ev_stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, 0, x, a.ga);
-  else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, x, a.ga);
-  return hipGetLastError();
+  return launch_kernel(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, x, a.ga);
 }
 
 template <int BITS>
@@ -778,9 +770,7 @@ hipError_t launch_batched_sparse(const LaunchArgs& a, hipStream_t stream) {
   dim3 grid(blocks, (gm.batch + pass_rows - 1) / pass_rows);
   auto kern = sqllm_sparse_batched<kWaves>;
   const float* x = static_cast<const float*>(a.x);
-  if (a.ev_start || a.ev_stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, 0, x, a.ga, a.xT, a.Bp, pass_rows);
-  else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, x, a.ga, a.xT, a.Bp, pass_rows);
-  return hipGetLastError();
+  return launch_kernel(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, x, a.ga, a.xT, a.Bp, pass_rows);
 }
 
 // one op (a.ga.seg[0]), operator ABI, batch rows through the matrix cores (dense term only)
@@ -860,28 +850,21 @@ __global__ void __launch_bounds__(256) sqllm_prepare_small(const float* __restri
 }
 
 hipError_t prepare_small(const float* x, float* xT, void* planes, int batch, int K, hipStream_t stream, hipEvent_t ev_start) {
-  const int lr = batch <= 2 ? 1 : batch <= 4 ? 2 : batch <= 8 ? 3 : 4;
   const unsigned threads = (unsigned)(K / 8 + 4) * 16u;
   const dim3 grid((threads + 255u) / 256u);
-  u32x4* pl = static_cast<u32x4*>(planes);
-  if (ev_start) hipExtLaunchKernelGGL(sqllm_prepare_small, grid, dim3(256), 0, stream, ev_start, nullptr, 0, x, xT, pl, batch, K, lr);
-  else hipLaunchKernelGGL(sqllm_prepare_small, grid, dim3(256), 0, stream, x, xT, pl, batch, K, lr);
-  return hipGetLastError();
+  return launch_kernel(sqllm_prepare_small, grid, dim3(256), 0, stream, ev_start, nullptr, x, xT, static_cast<u32x4*>(planes), batch, K,
+                       small_rows_log2(batch));
 }
 
 hipError_t transpose_small(const float* x, float* xT, int batch, int K, hipStream_t stream, hipEvent_t ev_start) {
-  const int lr = batch <= 2 ? 1 : batch <= 4 ? 2 : batch <= 8 ? 3 : 4;
+  const int lr = small_rows_log2(batch);
   const unsigned threads = (unsigned)(K / 4) << lr;
   const dim3 grid((threads + 255u) / 256u);
-  if (ev_start) hipExtLaunchKernelGGL(sqllm_transpose_small, grid, dim3(256), 0, stream, ev_start, nullptr, 0, x, xT, batch, K, lr);
-  else hipLaunchKernelGGL(sqllm_transpose_small, grid, dim3(256), 0, stream, x, xT, batch, K, lr);
-  return hipGetLastError();
+  return launch_kernel(sqllm_transpose_small, grid, dim3(256), 0, stream, ev_start, nullptr, x, xT, batch, K, lr);
 }
 
 hipError_t transpose_vec(const float* x, float* xT, int batch, int K, int Bp, hipStream_t stream, hipEvent_t ev_start) {
-  if (ev_start) hipExtLaunchKernelGGL(sqllm_transpose_vec, dim3((K + 63) / 64, Bp / 64), dim3(256), 0, stream, ev_start, nullptr, 0, x, xT, batch, K, Bp);
-  else hipLaunchKernelGGL(sqllm_transpose_vec, dim3((K + 63) / 64, Bp / 64), dim3(256), 0, stream, x, xT, batch, K, Bp);
-  return hipGetLastError();
+  return launch_kernel(sqllm_transpose_vec, dim3((K + 63) / 64, Bp / 64), dim3(256), 0, stream, ev_start, nullptr, x, xT, batch, K, Bp);
 }
 
 // Debug aid (option "validate_csr"): is `rows` a CSR row-pointer array for nnz values?  The fused

@@ -40,6 +40,7 @@
 #include "sqllm_kernels.h"
 
 #include "sqllm_decode.h"
+#include "sqllm_ranges.h"
 #include "sqllm_roles.h"
 #include "sqllm_split_common.h"
 #include "sqllm_probe.h"
@@ -101,6 +102,7 @@ __device__ __forceinline__ void dense_role_mfma_split(const float* __restrict__ 
   }
   const uint32_t lane_off = 8 * (i16 + 16 * (grp & 1));  // byte offset of this lane's slot inside an entry row
 
+  // (the piece walk of dense_role_mfma)
   const unsigned total = (unsigned)n_col_tiles * (unsigned)units_stride;
   unsigned gpos = (unsigned)bid * (unsigned)units_per_wg;
   unsigned gend = gpos + (unsigned)units_per_wg;
@@ -321,9 +323,7 @@ sqllm_fused_batched_split(const float* x, const GroupArgs ga) {
   const KernelGeom& gm = sg.gm;
   const int m0 = blockIdx.y * 16 * MB;
   dense_role_mfma_split<BITS, MB, WAVES>(x, reinterpret_cast<const u32x4*>(sg.q), sg.y, sg.lut, gm.K, gm.N, gm.batch, m0,
-                                         (int)blockIdx.x, gm.col_tiles, gm.units_total, gm.units_per_wg,
-                                         gm.dense_blocks == gm.col_tiles * gm.k_slices ? gm.k_slices * gm.units_per_wg : gm.units_total,
-                                         lds);
+                                         (int)blockIdx.x, gm.col_tiles, gm.units_total, gm.units_per_wg, units_stride_of(gm), lds);
 }
 
 // The same with the op's sparse terms in the grid (17 rows up to the wide form's switch-over, one op per launch):
@@ -335,8 +335,7 @@ template <int BITS, int MB, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64, (MB == 1 || (BITS == 4 && MB == 2)) ? 4 : 2)
 sqllm_fused_batched_split_all(const float* x, const GroupArgs ga, const float* xT, int Bp) {
   constexpr int T = WAVES * 64;
-  __shared__ __attribute__((aligned(16))) float lds[cmax(split_lds_floats(BITS, WAVES),
-                                                         cmax(kCsrSpanMax + cmax(kCsrSpanMax, 64 * (kCsrXtSpan + 1) + 3 * kCsrChunk), kTopxLds))];
+  __shared__ __attribute__((aligned(16))) float lds[cmax(split_lds_floats(BITS, WAVES), kWideSparseLdsFloats)];
   const Segment sg = ga.seg[0];
   asm volatile("" ::SQLLM_SEG_OPERANDS(sg), "s"(x), "s"(xT));
   __builtin_amdgcn_sched_barrier(0);
@@ -348,8 +347,7 @@ sqllm_fused_batched_split_all(const float* x, const GroupArgs ga, const float* x
   const int d = bid - gm.dense_block0;
   if (d >= 0 && d < gm.dense_blocks) {
     dense_role_mfma_split<BITS, MB, WAVES>(x, reinterpret_cast<const u32x4*>(sg.q), sg.y, sg.lut, gm.K, gm.N, gm.batch, m0, d, gm.col_tiles,
-                                           gm.units_total, gm.units_per_wg,
-                                           gm.dense_blocks == gm.col_tiles * gm.k_slices ? gm.k_slices * gm.units_per_wg : gm.units_total, lds);
+                                           gm.units_total, gm.units_per_wg, units_stride_of(gm), lds);
   } else if (bid < gm.csr_blocks) {
     if (xT) {
       csr_role<T, 1, float, float, true>(x, sg.y, sg.rows, sg.cols, sg.vals, gm.nnz, gm.K, gm.N, m0, rows_here, bid, lds, nullptr, 0, xT, Bp);
@@ -386,27 +384,13 @@ __global__ void __launch_bounds__(WAVES * 64, 4)
 sqllm_fused_small_split(const float* x, const GroupArgs ga, const float* xT, const char* planes) {
   constexpr int T = WAVES * 64;
   __shared__ __attribute__((aligned(16))) float lds[cmax(split_lds_floats(BITS, WAVES) + kFoldSum + kFoldRp, kTopxLds)];
-  // one round of scalar loads for the block table and segment 0 (see sqllm_fused_matvec)
-  Segment sg = ga.seg[0];
-  const int n_seg = ga.n_seg, blk1 = ga.block0[1], blk2 = ga.block0[2], blk3 = ga.block0[3];
-  asm volatile("" ::SQLLM_SEG_OPERANDS(sg), "s"(x), "s"(n_seg), "s"(blk1), "s"(blk2), "s"(blk3));
-  __builtin_amdgcn_sched_barrier(0);
-  int s = 0, base = 0;
-  if (n_seg > 1 && (int)blockIdx.x >= blk1) { s = 1; base = blk1; }
-  if (n_seg > 2 && (int)blockIdx.x >= blk2) { s = 2; base = blk2; }
-  if (n_seg > 3 && (int)blockIdx.x >= blk3) { s = 3; base = blk3; }
-  s = __builtin_amdgcn_readfirstlane(s);
-  if (s != 0) {
-    sg = ga.seg[s];
-    asm volatile("" ::SQLLM_SEG_OPERANDS(sg));
-  }
+  Segment sg;
+  const int bid = pick_segment(ga, x, sg);
   const KernelGeom& gm = sg.gm;
-  const int bid = blockIdx.x - base;
   const int d = bid - gm.dense_block0;
   if (d >= 0 && d < gm.dense_blocks) {
     dense_role_mfma_split<BITS, 1, WAVES, true, XM>(x, reinterpret_cast<const u32x4*>(sg.q), sg.y, sg.lut, gm.K, gm.N, gm.batch, 0, d, gm.col_tiles,
-                                                gm.units_total, gm.units_per_wg,
-                                                gm.dense_blocks == gm.col_tiles * gm.k_slices ? gm.k_slices * gm.units_per_wg : gm.units_total, lds,
+                                                gm.units_total, gm.units_per_wg, units_stride_of(gm), lds,
                                                 gm.nnz > 0 ? sg.rows : nullptr, sg.cols, sg.vals, xT, SQLLM_PROBE_PTR(sg), planes);
   } else if (bid < gm.topx_blocks) {
     // top-X slabs: gm.topx_blocks workgroups share the op's ceil(K / kTopxRows) slabs (with the transposed vec: 8-16
@@ -415,8 +399,7 @@ sqllm_fused_small_split(const float* x, const GroupArgs ga, const float* xT, con
     const int spw = (slabs + gm.topx_blocks - 1) / gm.topx_blocks;
     const int s0 = bid * spw, s1 = s0 + spw < slabs ? s0 + spw : slabs;
     if (xT && gm.topX <= 16) {
-      const int lr = gm.batch <= 2 ? 1 : gm.batch <= 4 ? 2 : gm.batch <= 8 ? 3 : 4;
-      if (s0 < s1) topx_role_xt<T>(xT, lr, sg.y, sg.full_rows, sg.full_idx, gm.topX, gm.K, gm.N, gm.batch, s0, s1, lds);
+      if (s0 < s1) topx_role_xt<T>(xT, small_rows_log2(gm.batch), sg.y, sg.full_rows, sg.full_idx, gm.topX, gm.K, gm.N, gm.batch, s0, s1, lds);
     } else {
       for (int sl = s0; sl < s1; ++sl) {
         if (sl > s0) __syncthreads();
@@ -434,9 +417,7 @@ hipError_t launch_split_inst(const LaunchArgs& a, hipStream_t stream) {
   dim3 grid(gm.dense_blocks, (gm.batch + 16 * MB - 1) / (16 * MB));
   auto kern = sqllm_fused_batched_split<BITS, MB, kWaves>;
   const float* x = static_cast<const float*>(a.x);
-  if (a.ev_start || a.ev_stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, 0, x, a.ga);
-  else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, x, a.ga);
-  return hipGetLastError();
+  return launch_kernel(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, x, a.ga);
 }
 
 template <int BITS, int MB>
@@ -445,27 +426,18 @@ hipError_t launch_split_all_inst(const LaunchArgs& a, hipStream_t stream) {
   dim3 grid(gm.dense_block0 + gm.dense_blocks, (gm.batch + 16 * MB - 1) / (16 * MB));
   auto kern = sqllm_fused_batched_split_all<BITS, MB, kWaves>;
   const float* x = static_cast<const float*>(a.x);
-  if (a.ev_start || a.ev_stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, 0, x, a.ga, a.xT, a.Bp);
-  else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, x, a.ga, a.xT, a.Bp);
-  return hipGetLastError();
+  return launch_kernel(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, x, a.ga, a.xT, a.Bp);
 }
 
 template <int BITS>
 hipError_t launch_split_all_bits(const LaunchArgs& a, hipStream_t stream) {
-  switch (a.row_blocks > 0 ? a.row_blocks : mfma_row_blocks(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_split_all_inst<BITS, 1>(a, stream);
-    case 2: return launch_split_all_inst<BITS, 2>(a, stream);
-    default: return launch_split_all_inst<BITS, 4>(a, stream);
-  }
+  return with_row_blocks(a.row_blocks > 0 ? a.row_blocks : mfma_row_blocks(a.ga.seg[0].gm.batch),
+                         [&](auto mb) { return launch_split_all_inst<BITS, decltype(mb)::value>(a, stream); });
 }
 
 template <int BITS>
 hipError_t launch_split_bits(const LaunchArgs& a, hipStream_t stream) {
-  switch (mfma_row_blocks(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_split_inst<BITS, 1>(a, stream);
-    case 2: return launch_split_inst<BITS, 2>(a, stream);
-    default: return launch_split_inst<BITS, 4>(a, stream);
-  }
+  return with_row_blocks(mfma_row_blocks(a.ga.seg[0].gm.batch), [&](auto mb) { return launch_split_inst<BITS, decltype(mb)::value>(a, stream); });
 }
 
 }  // namespace
@@ -478,9 +450,7 @@ hipError_t launch_small_split_inst(const LaunchArgs& a, hipStream_t stream) {
   const float* x = static_cast<const float*>(a.x);
   const char* planes = static_cast<const char*>(a.planes);
   auto kern = sqllm_fused_small_split<BITS, kWaves, XM>;
-  if (a.ev_start || a.ev_stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, 0, x, a.ga, a.xT, planes);
-  else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, x, a.ga, a.xT, planes);
-  return hipGetLastError();
+  return launch_kernel(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, a.ev_stop, x, a.ga, a.xT, planes);
 }
 }  // namespace
 

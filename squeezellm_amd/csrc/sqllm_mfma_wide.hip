@@ -20,6 +20,7 @@
 #include "sqllm_kernels.h"
 
 #include "sqllm_decode.h"
+#include "sqllm_ranges.h"
 #include "sqllm_split_common.h"
 
 namespace sqllm {
@@ -545,23 +546,17 @@ hipError_t launch_wide_bits(const LaunchArgs& a, hipStream_t stream) {
   const int sliced_units = gm.k_slices > 1 ? (gm.dense_blocks - a.wide_full_units) / gm.k_slices : 0;
   float* slabs = sliced_units > 0 ? a.wide_slabs : nullptr;
   hipEvent_t stop = slabs ? nullptr : a.ev_stop;  // (with slabs the op ends with the reduce launch)
-  if (a.planes) {
-    auto kern = sqllm_fused_wide<BITS, true>;
-    if (a.ev_start || stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, stop, 0, a.planes, a.plane_flags, a.wide_full_units, slabs, a.ga, static_cast<const float*>(a.x));
-    else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.planes, a.plane_flags, a.wide_full_units, slabs, a.ga, static_cast<const float*>(a.x));
-  } else {
-    auto kern = sqllm_fused_wide<BITS, false>;
-    const uint32_t* none = nullptr;
-    if (a.ev_start || stop) hipExtLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.ev_start, stop, 0, a.x, none, a.wide_full_units, slabs, a.ga, static_cast<const float*>(a.x));
-    else hipLaunchKernelGGL(kern, grid, dim3(kWaves * 64), 0, stream, a.x, none, a.wide_full_units, slabs, a.ga, static_cast<const float*>(a.x));
-  }
-  hipError_t e = hipGetLastError();
+  const float* x32 = static_cast<const float*>(a.x);
+  const uint32_t* none = nullptr;
+  const hipError_t e =
+      a.planes ? launch_kernel(sqllm_fused_wide<BITS, true>, grid, dim3(kWaves * 64), 0, stream, a.ev_start, stop, a.planes, a.plane_flags,
+                               a.wide_full_units, slabs, a.ga, x32)
+               : launch_kernel(sqllm_fused_wide<BITS, false>, grid, dim3(kWaves * 64), 0, stream, a.ev_start, stop, a.x, none,
+                               a.wide_full_units, slabs, a.ga, x32);
   if (e != hipSuccess || !slabs) return e;
   const Segment& sg = a.ga.seg[0];
-  dim3 rgrid(sliced_units * kWideTiles);
-  if (a.ev_stop) hipExtLaunchKernelGGL(sqllm_wide_reduce, rgrid, dim3(256), 0, stream, nullptr, a.ev_stop, 0, (const float*)slabs, sg.y, gm.N, gm.batch, gm.col_tiles, a.wide_full_units, gm.k_slices);
-  else hipLaunchKernelGGL(sqllm_wide_reduce, rgrid, dim3(256), 0, stream, (const float*)slabs, sg.y, gm.N, gm.batch, gm.col_tiles, a.wide_full_units, gm.k_slices);
-  return hipGetLastError();
+  return launch_kernel(sqllm_wide_reduce, dim3(sliced_units * kWideTiles), dim3(256), 0, stream, nullptr, a.ev_stop, (const float*)slabs, sg.y,
+                       gm.N, gm.batch, gm.col_tiles, a.wide_full_units, gm.k_slices);
 }
 
 }  // namespace
@@ -570,9 +565,7 @@ hipError_t launch_wide_bits(const LaunchArgs& a, hipStream_t stream) {
 hipError_t split_vec(const float* x, void* planes, uint32_t* flags, int batch, int K, hipStream_t stream, hipEvent_t ev_start) {
   u32x4* out = static_cast<u32x4*>(planes);
   const uint32_t n_frag = (uint32_t)(split_planes_chunks(batch, K) / 3);  // (rb, kb, lane) triples
-  if (ev_start) hipExtLaunchKernelGGL(sqllm_split_vec, dim3(kSplitFlagWgs), dim3(256), 0, stream, ev_start, nullptr, 0, x, out, n_frag, flags, batch, K);
-  else hipLaunchKernelGGL(sqllm_split_vec, dim3(kSplitFlagWgs), dim3(256), 0, stream, x, out, n_frag, flags, batch, K);
-  return hipGetLastError();
+  return launch_kernel(sqllm_split_vec, dim3(kSplitFlagWgs), dim3(256), 0, stream, ev_start, nullptr, x, out, n_frag, flags, batch, K);
 }
 
 // one op (a.ga.seg[0]) in the wide form: a.planes = vec as split_vec's planes (or null: split in registers), a.wide_slabs =

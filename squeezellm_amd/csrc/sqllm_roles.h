@@ -832,6 +832,10 @@ __device__ __forceinline__ void topx_role_xt(const float* __restrict__ xT, int l
   }
 }
 
+// LDS floats of the sparse roles of a wide-batch op (sqllm_sparse_batched, sqllm_fused_batched_split_all): the CSR role on the
+// transposed vec, or gathering; the top-X role
+constexpr int kWideSparseLdsFloats = cmax(kCsrSpanMax + cmax(kCsrSpanMax, 64 * (kCsrXtSpan + 1) + 3 * kCsrChunk), kTopxLds);
+
 #undef SQLLM_CSR_STAMP
 
 }  // namespace sqllm
