@@ -11,8 +11,8 @@
 // partial products whose magnitude can reach 2^-16 of it or more:
 //         w x  ~  wh xh + wh xm + wm xh + wh xl + wl xh + wm xm            (dropped: wm xl, wl xm, wl xl <= 2^-24 |w x|)
 // A bf16 x bf16 product is exact in fp32, the matrix instruction accumulates in fp32, so the result carries the
-// rounding of an fp32 FMA chain plus 3 x 2^-24 per product: fp32 class (measured against the fp64 oracle next to the
-// fp32 kernel: tests/test_gpu_batched.py, same 2e-5 gate, observed ~3e-7).  Six v_mfma_f32_16x16x32_bf16 (32 k's
+// rounding of an fp32 FMA chain plus 3 x 2^-24 per product: fp32 class (pinned per route on full-mantissa operands by
+// tests/test_gpu_precision.py; measured figures: profiles/precision_routes.txt).  Six v_mfma_f32_16x16x32_bf16 (32 k's
 // each, 16 cycles) replace 8 x v_mfma_f32_16x16x4_f32 (4 k's each, 32 cycles): 96 instead of 256 matrix-pipe cycles
 // per 16 rows x 16 columns x 32 k's.
 //
