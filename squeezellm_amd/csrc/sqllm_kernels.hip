@@ -410,7 +410,13 @@ sqllm_sparse_batched(const float* x, const GroupArgs ga, const float* xT, int Bp
 //       ([i0 + 8 i1][column] x {lut[i0], lut[i1]}, 32 KB): one ds_read_b64 per two weights;
 //     * decode is a software pipeline over stages of ST k's (ST * rows <= 32 SGPRs of vec):
 //       [wait] [issue lookups + vec loads of stage s + 1] [packed FMAs of stage s]; scalar loads
-//       return out of order, so the wait is lgkmcnt(0) and sits in front of the next issue.
+//       return out of order, so the wait is lgkmcnt(0) and sits in front of the next issue;
+//     * ONE ROW (BT == 1, the batch-1 routes of cols_pays_batch1) has a decode loop of its own: vec is requested by groups
+//       of 32 k's (4 x s_load_dwordx8 into one of two sets of 32 SGPRs), so a scalar load is in flight during one stage
+//       in four only; in the other three the wait for stage s is a counted lgkmcnt(reads of s + 1) BEHIND the issue of stage
+//       s + 1 (LDS returns in order) -- one full drain per 32 weights instead of four; and chunk pairs whose units all exist
+//       run without the dead-unit selects (the piece's last pair(s) take the guarded copy).  Same FMAs on the same
+//       accumulators in the same order: results are bit-identical to the staged loop's.
 // Work is cut as in the matrix-core kernel: equal contiguous ranges of the flattened
 // (column tile, unit) space, one per workgroup, a range crossing a tile boundary = two pieces.
 // Waves meet in LDS slabs (plain stores) and leave as one atomic per (row, column).
@@ -601,6 +607,97 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
         for (int b = 0; b < BT; ++b)
           acc[b][m % NA] = __builtin_elementwise_fma(o.v[m], f32x2{o.x[b][2 * m], o.x[b][2 * m + 1]}, acc[b][m % NA]);
     };
+    if constexpr (BT == 1) {
+      // ---- one row: vec by GROUPS of 32 k's (4-bit: the chunk's four units; 3-bit: one unit), two sets of 32 SGPRs ----
+      // The lookups stay stages of ST = 8 k's in two register sets.  The LDS queue returns in order, so while no scalar load is
+      // in flight the wait for stage s is a COUNTED one placed BEHIND the issue of stage s + 1 (lgkmcnt = the reads of s + 1);
+      // the next group's vec is requested once per group, behind the wait of the group's third stage, and the one full drain
+      // (lgkmcnt(0): scalar loads return out of order) stands in front of the issue that follows the fourth:
+      //     [issue s+1] [wait s] [FMAs s]   x2      [issue s+1] [wait s] [vec of group g+1] [FMAs s]      [drain] [issue s+1] [FMAs s]
+      // Chunk pairs whose units all exist take the loop without the dead-unit selects; the piece's last pair(s) take the
+      // guarded copy.  The vec offset is clamped in both (the look-ahead behind the last live chunk is a dead unit).
+      // Every column's sum runs over k in the same order and on the same accumulators as in the staged loop below.
+      constexpr int GS = 32 / ST;                 // stages per vec group
+      constexpr int LPS = BITS == 4 ? 2 * NP : NP;  // LDS reads per stage
+      static_assert(NS % GS == 0 && (NB * NS / GS) % 2 == 0, "vec groups alternate between two SGPR sets");
+      struct V { f32x2 v[NP]; };
+      XV xs[2][GS];
+      auto look = [&](const uint32_t (&buf)[D][R], int st, int cc, V& o, auto guard) {
+        const int j = st / SPU, sub = st % SPU;
+        bool live = true;
+        if constexpr (decltype(guard)::value) live = cc * D + j < n_w;
+        if constexpr (BITS == 4) {
+          const uint32_t lo = buf[j][0] & 0x0F0F0F0Fu, hi = (buf[j][0] >> 4) & 0x0F0F0F0Fu;
+#define SQ_L(WORD, SEL) *reinterpret_cast<const float __attribute__((address_space(3)))*>(__builtin_amdgcn_perm(WORD, lane_base, SEL))
+#pragma unroll
+          for (int m = 0; m < NP; ++m) {
+            const uint32_t sel = live ? 0x0C0C0400u + ((uint32_t)(sub * NP + m) << 8) : 0x0C0C0100u;
+            o.v[m] = f32x2{SQ_L(lo, sel), SQ_L(hi, sel)};
+          }
+#undef SQ_L
+        } else {
+          const uint32_t lane_or_dead = lane_base | (live ? 0u : 0x8000u);
+#pragma unroll
+          for (int m = 0; m < NP; ++m)
+            o.v[m] = *reinterpret_cast<const f32x2 __attribute__((address_space(3)))*>(
+                lane_or_dead | field6_x512(buf[j][0], buf[j][1], buf[j][2], sub * NP + m));
+        }
+      };
+      // vec of the group that starts at stage st0 of chunk cc
+      auto vec_group = [&](int st0, int cc, XV (&xg)[GS]) {
+#pragma unroll
+        for (int g = 0; g < GS; ++g) {
+          const int j = (st0 + g) / SPU, sub = (st0 + g) % SPU;
+          int u = u0 + w + (cc * D + j) * WAVES;
+          if (u > u1 - 1) u = u1 - 1;
+          uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
+          asm volatile("" : "+s"(koff));
+          xg[g] = XVec<ST>::load(xrow[0], koff);
+        }
+      };
+      auto fma1 = [&](const V& o, const XV& xv) {
+#pragma unroll
+        for (int m = 0; m < NP; ++m)
+          acc[0][m % NA] = __builtin_elementwise_fma(o.v[m], f32x2{xv[2 * m], xv[2 * m + 1]}, acc[0][m % NA]);
+      };
+      V va, vb;
+      auto chunk_pair = [&](int c, auto guard) {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+#pragma unroll
+          for (int st = 0; st < NS; ++st) {
+            V& cur = (st & 1) ? vb : va;
+            V& nxt = (st & 1) ? va : vb;
+            const int set = ((k * NS + st) / GS) & 1, pos = st % GS;
+            const bool wrap = st + 1 == NS;  // the next stage opens the next chunk
+            if (pos == GS - 1) __builtin_amdgcn_s_waitcnt(0xC07F);  // the drain: lgkmcnt(0)
+            if (wrap) look(wbuf[(k + 1) % NB], 0, c + k + 1, nxt, guard);
+            else look(wbuf[k], st + 1, c + k, nxt, guard);
+            __builtin_amdgcn_sched_barrier(0);
+            if (pos != GS - 1) {
+              __builtin_amdgcn_s_waitcnt(0xC07F | (LPS << 8));  // lgkmcnt(LPS): everything but the lookups just issued
+              if (pos == GS - 2) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (st + 2 == NS) vec_group(0, c + k + 1, xs[set ^ 1]);
+                else vec_group(st + 2, c + k, xs[set ^ 1]);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+            }
+            fma1(cur, xs[set][pos]);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          load_chunk(k, wbuf[k]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      vec_group(0, 0, xs[0]);
+      __builtin_amdgcn_s_waitcnt(0xC07F);  // (no scalar load in flight when the loop's counted waits begin)
+      look(wbuf[0], 0, 0, va, std::true_type{});
+      __builtin_amdgcn_sched_barrier(0);
+      int c = 0;
+      for (; (c + NB) * D <= n_w; c += NB) chunk_pair(c, std::false_type{});
+      for (; c < nc; c += NB) chunk_pair(c, std::true_type{});
+    } else {
     St sa, sb;
     issue(wbuf[0], 0, 0, sa);
     __builtin_amdgcn_sched_barrier(0);
@@ -625,6 +722,7 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
         load_chunk(k, wbuf[k]);
         __builtin_amdgcn_sched_barrier(0);
       }
+    }
     }
 
     // ---- waves meet in LDS: slab [wave][row][column], then one atomic per (row, column) ----
