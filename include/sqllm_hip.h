@@ -400,6 +400,33 @@ int64_t sqllm_nuq_workspace_bytes(const sqllm_nuq* d);
  * descriptor, values, centroids or workspace) before the device is touched; a short workspace is SQLLM_E_SHAPE. */
 int sqllm_nuq_fit(const sqllm_nuq* d, void* workspace, int64_t workspace_bytes, sqllm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dense export: the matrix the three weight terms of an op stand for,
+ *
+ *     W[n, k] = lookup_table[n, idx(k, n)] + sum CSR(n, k) + sum_c [full_row_indices[c] == n] full_rows[k, c]
+ *
+ * written as out[n * ld + k] for every n < N, k < K: [N, K] with K contiguous, the layout of nn.Linear.weight.
+ * Every element is summed in fp32 (duplicate CSR entries and duplicate top-X indices accumulate, as in the op)
+ * and rounded ONCE: not at all for SQLLM_DTYPE_F32, to nearest-even _Float16 for SQLLM_DTYPE_F16 (overflow gives
+ * +-inf; NaN / inf in the operands propagate).  A position with at most one sparse contribution is bit-exact:
+ * the table entry, or one fp32 add.  Elements k in [K, ld) of a row are NOT written; nothing else is.
+ * Enqueues ONE kernel on `stream`; allocates nothing, retains nothing, never synchronises (option "validate_csr"
+ * aside, which blocks as it does for every launch): a stream capture of the call holds one kernel node.
+ * SQLLM_E_NULL for a NULL descriptor, out, qweight or lookup_table; SQLLM_E_BITS; SQLLM_E_SHAPE for bad K / N,
+ * ld < K, an ld that is no multiple of 8 (fp16) / 4 (fp32) or an unknown out_dtype; SQLLM_E_ALIGN for a qweight
+ * or out that is not 16-byte aligned; SQLLM_E_SPARSE as for sqllm_launch -- all before the device is touched.
+ * ------------------------------------------------------------------------------------------- */
+#define SQLLM_DTYPE_F32 0
+#define SQLLM_DTYPE_F16 1
+typedef struct sqllm_dequant_desc {
+  sqllm_op op;       /* bits, K, N, qweight, lookup_table, CSR and top-X operands as for sqllm_launch;
+                        vec, mul and batch are ignored */
+  void* out;         /* [N, ld] of out_dtype, 16-byte aligned */
+  int64_t ld;        /* elements per output row, >= K; for fp16 a multiple of 8, for fp32 of 4 */
+  int32_t out_dtype; /* SQLLM_DTYPE_* */
+} sqllm_dequant_desc;
+int sqllm_dequant(const sqllm_dequant_desc* d, sqllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

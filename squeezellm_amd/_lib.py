@@ -56,6 +56,14 @@ class SqllmNuq(ctypes.Structure):
                 ("centroids", c_void_p), ("cost", c_void_p)]
 
 
+class SqllmDequant(ctypes.Structure):
+    """struct sqllm_dequant_desc (include/sqllm_hip.h): op.vec / op.mul / op.batch are ignored."""
+
+    _fields_ = [("op", SqllmOp), ("out", c_void_p), ("ld", ctypes.c_int64), ("out_dtype", c_int32)]
+
+
+DTYPE_F32, DTYPE_F16 = 0, 1  # SQLLM_DTYPE_*
+
 P = c_void_p  # every device pointer crosses as void*
 
 _DENSE = [P, P, P, P, c_int, c_int, P]
@@ -89,6 +97,7 @@ SIGNATURES = {
     "sqllm_plan_query": [POINTER(SqllmOp), POINTER(SqllmPlan)],
     "sqllm_nuq_workspace_bytes": [POINTER(SqllmNuq)],
     "sqllm_nuq_fit": [POINTER(SqllmNuq), P, ctypes.c_int64, P],
+    "sqllm_dequant": [POINTER(SqllmDequant), P],
 }
 for _b in (3, 4):
     SIGNATURES[f"sqllm_vecquant{_b}matmul_nuq_perchannel"] = _DENSE

@@ -104,6 +104,29 @@ def to_state_dict(layers: dict, extra: dict | None = None) -> dict:
     return sd
 
 
+def to_dense_state_dict(checkpoint, topX: int = 0, dtype=torch.float16, device=None) -> dict:
+    """The other inverse: a quantised checkpoint (a path or a loaded state dict) -> an ordinary state dict in which every
+    quantised linear `<name>` is `<name>.weight` [N, K] of `dtype` (decode.dequantize_layer: all weight terms, rounded
+    once) and, if the checkpoint has one, `<name>.bias`; every other entry passes through untouched (the same objects).
+    The per-layer fields of the quantised format (qweight, lookup_table, rows / cols / vals, startrows, full rows and
+    the `sparse_threshold.<name>` counts) are dropped.  `topX` as for load_layers -- it moves outliers between two
+    terms and leaves the matrix unchanged; `device`: the GPU to decode on (default: the current one).  Weights and
+    biases both come out on that device in `dtype`, as QuantLinearLUT.to_linear makes them: `.cpu()` them to save."""
+    from . import decode
+
+    sd = torch.load(checkpoint, map_location="cpu") if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, "__fspath__") else checkpoint
+    device = torch.device(device if device is not None else "cuda")
+    names = quantized_names(sd)
+    consumed = {f"{n}.{f}" for n in names for f in _FIELDS} | {f"sparse_threshold.{n}" for n in names}
+    out = {k: v for k, v in sd.items() if k not in consumed}
+    for name in names:
+        lay = layer_operands(sd, name, topX=topX, device=device)
+        out[f"{name}.weight"] = decode.dequantize_layer(lay, dtype=dtype)
+        if f"{name}.bias" in sd:
+            out[f"{name}.bias"] = sd[f"{name}.bias"].to(device=device, dtype=dtype)
+    return out
+
+
 def _fold_full_rows(rows, cols, vals, full_rows, full_idx):
     N = rows.numel() - 1
     K = full_rows.shape[0]

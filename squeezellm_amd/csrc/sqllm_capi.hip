@@ -70,6 +70,19 @@ int cu_count() {
   return c;
 }
 
+// the sparse operands of an op: shared by every entry point that takes them (sqllm_launch ..., sqllm_dequant)
+int validate_sparse(const sqllm_op* op) {
+  if (op->rows) {
+    if (op->nnz < 0) return SQLLM_E_SPARSE;
+    if (op->nnz > 0 && (!op->cols || !op->vals)) return SQLLM_E_NULL;
+  }
+  if (op->full_rows) {
+    if (op->topX < 0) return SQLLM_E_SPARSE;
+    if (op->topX > 0 && !op->full_row_indices) return SQLLM_E_NULL;
+  }
+  return SQLLM_OK;
+}
+
 int validate(const sqllm_op* op) {
   if (!op) return SQLLM_E_NULL;
   if (op->bits != 3 && op->bits != 4) return SQLLM_E_BITS;
@@ -81,15 +94,7 @@ int validate(const sqllm_op* op) {
   if ((reinterpret_cast<uintptr_t>(op->qweight) & 15u) != 0 ||
       (reinterpret_cast<uintptr_t>(op->lookup_table) & 15u) != 0)
     return SQLLM_E_ALIGN;
-  if (op->rows) {
-    if (op->nnz < 0) return SQLLM_E_SPARSE;
-    if (op->nnz > 0 && (!op->cols || !op->vals)) return SQLLM_E_NULL;
-  }
-  if (op->full_rows) {
-    if (op->topX < 0) return SQLLM_E_SPARSE;
-    if (op->topX > 0 && !op->full_row_indices) return SQLLM_E_NULL;
-  }
-  return SQLLM_OK;
+  return validate_sparse(op);
 }
 
 // option "validate_csr": a value check of rows[] on the device (blocks the host; debugging aid)

@@ -48,6 +48,7 @@ int device_slot();  // index of the calling thread's current device in per-devic
 Knobs& knobs();
 int cu_count();
 int validate(const sqllm_op* op);
+int validate_sparse(const sqllm_op* op);  // the CSR / top-X operand checks of validate() alone
 int validate_csr_values(const sqllm_op* op, sqllm_stream_t stream);
 void make_plan(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch = 1, int max_slices = sqllm::kMaxSlices,
                int waves = sqllm::kWaves);

@@ -9,6 +9,7 @@ C array of `sqllm_op` descriptors (include/sqllm_hip.h) and then
 With `linear=True` the ops are fused linears (sqllm_linear_f16): fp16 activations in, fp16 out,
 bias included, no zero-fill / cast launches around them -- the whole matvec branch of
 QuantLinearLUT.forward (squeezellm/quant.py:211-312) per kernel.
+`dequantize_layer` is the other direction: a layer's operands -> the dense [N, K] matrix they stand for, one kernel.
 All launches go to torch's current stream; nothing here synchronises.
 """
 from __future__ import annotations
@@ -195,3 +196,65 @@ class OpSequence:
             self.launch()
         return g
 
+
+_DENSE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16}
+
+
+def dequantize_layer(layer: dict, dtype=torch.float16, out=None) -> torch.Tensor:
+    """The dense matrix W [N, K] (K contiguous: the layout of nn.Linear.weight) that a layer's operands stand for --
+    codebook entry + CSR outliers + top-X columns, summed in fp32 and rounded once to `dtype` (torch.float16 or
+    torch.float32) -- written by ONE kernel (sqllm_dequant, include/sqllm_hip.h) on torch's current stream.
+
+    `layer`: an operand dict as made by synth.make_layer, pack.pack_layer or checkpoint.layer_operands (bits, K, N,
+    qweight, lookup_table and, optionally, rows / cols / vals and full_rows / full_row_indices), on the GPU.
+    `out`: a 2-D [N, >= K] tensor of `dtype` to write into (row stride = out.stride(0): a multiple of 8 elements for
+    fp16, of 4 for fp32; unit stride along K; columns beyond K are left alone); the [N, K] view of it is returned.
+    Without `out` a new [N, K] tensor is allocated (a stream-ordered torch allocation: capture-safe)."""
+    if dtype not in _DENSE_DTYPES:
+        raise TypeError(f"dtype must be torch.float16 or torch.float32, got {dtype}")
+    code = _DENSE_DTYPES[dtype]
+    K, N = layer["K"], layer["N"]
+    qweight, lut = layer["qweight"], layer["lookup_table"]
+    for name, t, dt in (("qweight", qweight, torch.int32), ("lookup_table", lut, torch.float32)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} GPU tensor (there is no CPU path)")
+    if tuple(qweight.shape) != (K // 32 * layer["bits"], N) or tuple(lut.shape) != (N, 1 << layer["bits"]):
+        raise ValueError(f"qweight / lookup_table shapes {tuple(qweight.shape)} / {tuple(lut.shape)} do not match K={K}, N={N}, "
+                         f"bits={layer['bits']}")
+    dev = qweight.device
+    if out is None:  # (K % 32 == 0: a row stride of K elements is aligned for either dtype)
+        out = torch.empty((N, K), dtype=dtype, device=dev)
+    else:
+        if (out.dtype != dtype or out.device != dev or out.dim() != 2 or out.shape[0] != N or out.shape[1] < K
+                or (out.shape[1] > 1 and out.stride(1) != 1) or (N > 1 and out.stride(0) < out.shape[1])):
+            raise ValueError(f"out must be a [{N}, >= {K}] {dtype} tensor on {dev} with unit stride along K")
+    d = _lib.SqllmDequant()
+    o = d.op
+    o.bits, o.K, o.N = layer["bits"], K, N
+    o.qweight, o.lookup_table = qweight.data_ptr(), lut.data_ptr()
+    vals = layer.get("vals")
+    if layer.get("rows") is not None and vals is not None and vals.numel():
+        csr = (layer["rows"], layer["cols"], vals)
+        for name, t, dt in zip(("rows", "cols", "vals"), csr, (torch.int32, torch.int32, torch.float32)):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor on {dev}")
+        if csr[0].numel() != N + 1 or csr[1].numel() != vals.numel():
+            raise ValueError("rows must have N + 1 entries and cols as many as vals")
+        o.rows, o.cols, o.vals, o.nnz = csr[0].data_ptr(), csr[1].data_ptr(), vals.data_ptr(), vals.numel()
+    full_rows = layer.get("full_rows")
+    if full_rows is not None and full_rows.shape[1] > 0:
+        idx = layer["full_row_indices"]
+        for name, t, dt in (("full_rows", full_rows, torch.float32), ("full_row_indices", idx, torch.int32)):
+            if t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor on {dev}")
+        if full_rows.shape[0] != K or idx.numel() != full_rows.shape[1]:
+            raise ValueError(f"full_rows must be [{K}, topX] with topX indices")
+        o.full_rows, o.full_row_indices, o.topX = full_rows.data_ptr(), idx.data_ptr(), full_rows.shape[1]
+    d.out = out.data_ptr()
+    d.ld = out.stride(0) if N > 1 else max(out.shape[1], K)
+    d.out_dtype = code
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = lib.sqllm_dequant(ctypes.byref(d), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "sqllm_dequant")
+    return out if out.shape[1] == K else out[:, :K]

@@ -130,6 +130,23 @@ def quantize_linear(weight: torch.Tensor, gradient: torch.Tensor | None, bits: i
                            bias=None if bias is None else bias.to(device=dev, dtype=torch.float32))
 
 
+def reconstruction_error(weight: torch.Tensor, gradient: torch.Tensor | None, layer: dict) -> dict:
+    """How far a packed layer is from the weight [N, K] it was made from: the FINAL dense-and-sparse layer is decoded on
+    the GPU (decode.dequantize_layer, fp32: codebook entry + CSR + top-X columns) and compared in fp64 there.
+    Returns {"sse": sum (W - W_hat)^2, "weighted_sse": sum g (W - W_hat)^2 with the Fisher diagonal `gradient` as
+    weights (None: ones), "max_abs": max |W - W_hat|} as Python floats."""
+    from . import decode
+
+    w_hat = decode.dequantize_layer(layer, dtype=torch.float32)
+    dev = w_hat.device
+    if tuple(weight.shape) != tuple(w_hat.shape):
+        raise ValueError(f"weight is {tuple(weight.shape)}, the layer decodes to {tuple(w_hat.shape)}")
+    diff = weight.to(device=dev, dtype=torch.float64) - w_hat.to(torch.float64)
+    sq = diff * diff
+    wsse = sq.sum() if gradient is None else (sq * gradient.to(device=dev, dtype=torch.float64)).sum()
+    return {"sse": float(sq.sum()), "weighted_sse": float(wsse), "max_abs": float(diff.abs().max())}
+
+
 def _short_name(name: str) -> str:
     return _SHORT.get(name.rsplit(".", 1)[-1], name.rsplit(".", 1)[-1])
 
@@ -152,11 +169,12 @@ def default_names(model_sd) -> list[str]:
 
 
 def quantize_state_dict(model_sd: dict, grad_sd: dict, bits: int, names=None, sensitivity: float = 0.0,
-                        outlier_config: dict | None = None, topX: int = 0, device=None) -> dict:
+                        outlier_config: dict | None = None, topX: int = 0, device=None, report: bool = False) -> dict:
     """A model's state dict + its Fisher diagonal (same keys, or the keys without `.weight`) -> a flat checkpoint in the
     reference's format (checkpoint.to_state_dict).  Every linear of `names` (default: default_names) is quantised;
     everything else is copied through.  `outlier_config` is the JSON generate_outlier_config.py writes:
-    {"outlier_threshold": ..., "outlier_config": [{short module name: threshold} per decoder layer]}."""
+    {"outlier_threshold": ..., "outlier_config": [{short module name: threshold} per decoder layer]}.
+    report=True prints every layer's reconstruction_error (one line per layer, stderr)."""
     device = torch.device(device or "cuda")
     names = list(names) if names is not None else default_names(model_sd)
     per_layer = None if outlier_config is None else outlier_config["outlier_config"]
@@ -175,6 +193,9 @@ def quantize_state_dict(model_sd: dict, grad_sd: dict, bits: int, names=None, se
         lay = quantize_linear(weight.to(device), grad.to(device), bits, sensitivity=sensitivity, threshold=thres,
                               topX=topX, bias=model_sd.get(f"{name}.bias"))
         layers[name] = lay
+        if report:
+            err = reconstruction_error(weight.to(device), grad.to(device), lay)
+            print(f"{name}: sse {err['sse']:.6e}  weighted_sse {err['weighted_sse']:.6e}  max_abs {err['max_abs']:.6e}", file=sys.stderr)
     done = {f"{n}.weight" for n in names} | {f"{n}.bias" for n in names}
     extra = {k: v for k, v in model_sd.items() if k not in done}
     return checkpoint.to_state_dict(layers, extra)
@@ -189,6 +210,7 @@ def main(argv=None) -> int:
     ap.add_argument("--sensitivity", type=float, default=0.0, help="percent of weights kept as sensitivity outliers")
     ap.add_argument("--outlier-config", default=None, help="JSON from generate_outlier_config.py")
     ap.add_argument("--topx", type=int, default=0, help="densest outlier rows held dense (full_rows)")
+    ap.add_argument("--report", action="store_true", help="print every layer's reconstruction error (plain and Fisher-weighted)")
     a = ap.parse_args(argv)
     cfg = None
     if a.outlier_config:
@@ -196,7 +218,7 @@ def main(argv=None) -> int:
             cfg = json.load(f)
     model_sd = torch.load(a.model, map_location="cpu")
     grad_sd = torch.load(a.gradient, map_location="cpu")
-    sd = quantize_state_dict(model_sd, grad_sd, a.bits, sensitivity=a.sensitivity, outlier_config=cfg, topX=a.topx)
+    sd = quantize_state_dict(model_sd, grad_sd, a.bits, sensitivity=a.sensitivity, outlier_config=cfg, topX=a.topx, report=a.report)
     torch.save(sd, a.out)
     print(f"wrote {a.out}: {len(checkpoint.quantized_names(sd))} quantised linears, {a.bits}-bit", file=sys.stderr)
     return 0

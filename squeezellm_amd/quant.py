@@ -123,6 +123,36 @@ class QuantLinearLUT(nn.Module):
             m.full_rows, m.full_row_indices = layer["full_rows"], layer["full_row_indices"]
         return m
 
+    def _operands(self) -> dict:
+        """The operand dict of this module (no copies) with exactly the weight terms its forward applies: the sparse
+        terms follow `include_sparse`, `numvals` and `topX` as `op_kind` does -- a module built with
+        include_sparse=False yields the dense term alone even if it carries sparse buffers, and the top-X columns
+        count only where the hybrid op would run."""
+        lay = dict(bits=self.bits, K=self.infeatures, N=self.outfeatures, qweight=self.qweight, lookup_table=self.lookup_table,
+                   bias=self.bias)
+        if self.include_sparse:
+            if self.numvals > 0 and getattr(self, "vals", None) is not None:
+                lay.update(rows=self.rows, cols=self.cols, vals=self.vals)
+            if self.topX > 0:
+                lay.update(full_rows=self.full_rows, full_row_indices=self.full_row_indices)
+        return lay
+
+    def dequantize(self, dtype=torch.float16, out=None) -> torch.Tensor:
+        """The dense weight [outfeatures, infeatures] this module multiplies by (all weight terms its forward applies: the sparse ones follow `include_sparse`, `numvals` and `topX` as `op_kind` does, summed
+        in fp32, rounded once to `dtype`): one kernel on the current stream (decode.dequantize_layer)."""
+        from . import decode
+
+        return decode.dequantize_layer(self._operands(), dtype=dtype, out=out)
+
+    def to_linear(self, dtype=torch.float16) -> nn.Linear:
+        """An ordinary nn.Linear on the module's device: weight = dequantize(dtype), bias copied (cast to `dtype`)."""
+        w = self.dequantize(dtype)
+        lin = nn.Linear(self.infeatures, self.outfeatures, bias=self.bias is not None, device="meta")
+        lin.weight = nn.Parameter(w, requires_grad=False)
+        if self.bias is not None:
+            lin.bias = nn.Parameter(self.bias.detach().to(device=w.device, dtype=dtype, copy=True), requires_grad=False)
+        return lin
+
 
 _is_capturing = torch.cuda.is_current_stream_capturing
 
@@ -134,7 +164,38 @@ class QuantLinearLUTFused(QuantLinearLUT):
     existing model over with `fuse_quant_lut(model)`.  Result = fp16(fp32 accumulation + bias);
     the reference's batched branch rounds to fp16 before adding the bias (and then promotes to
     fp32), so the two differ by at most one fp16 rounding of the output.  Other dtypes take the
-    parent's path."""
+    parent's path.
+
+    Prompt-width inputs: the fused kernel decodes the packed weights once per 8 rows.  With `dense_min_rows` set, a call
+    of at least that many rows instead writes the layer's dense fp16 matrix once (`dequantize`: one kernel) and
+    multiplies with torch's fp16 GEMM.  That matrix is a temporary of the call -- a torch allocation on the current
+    stream, capture-safe, never cached on the module -- so the peak extra memory is ONE layer's matrix
+    (2 * infeatures * outfeatures bytes: 142 MB for a 13B gate/up layer).  Recommended value: 128 -- on the 13B shapes
+    the dense route measured 2.8 - 6.4x faster at 128 rows and 17 - 34x at 2048 (the figures per shape stand beside the
+    attribute, the table in DESIGN.md 4.5); the break-even lies lower and is not measured.  The default stays None."""
+
+    # rows from which forward takes the dense route; None (default): never -- every call runs the fused kernel, as before
+    # the route existed.
+    # Recommended where prompts are run through this class: 128.  Measured on an MI355X (tools/dequant_bench.py, table in
+    # DESIGN.md 4.5, raw output profiles/dequant_bench.txt), 13B shapes, w3 and w4, with and without sparse terms, the
+    # dense route is faster at every row count the tool runs:
+    #     gate/up (5120 x 13824):  128 rows 5.6 - 6.4x,  512 rows 14 - 17x,  2048 rows 21 - 29x
+    #     o_proj  (5120 x 5120):   128 rows 2.8 - 4.3x,  512 rows 7.8 - 14x,  2048 rows 18 - 34x
+    # so the break-even lies below 128 rows on both shapes and has not been measured; 128 is the lowest row count with a
+    # measurement behind it, not the break-even.  The price is the temporary matrix (see the class docstring).
+    dense_min_rows = None
+
+    @property
+    def last_route(self):
+        """"fused" or "dense": the way the most recent fp16 GPU forward of this module went (None before the first)."""
+        return self.__dict__.get("_last_route")
+
+    def _forward_dense(self, x: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
+        w = self.dequantize(torch.float16)  # a temporary of this call
+        y = torch.nn.functional.linear(x2, w)
+        if self.bias is not None:
+            y = (y.float() + self.bias).half()
+        return y.reshape(*x.shape[:-1], self.outfeatures)
 
     GRAPH_WS_MAX_BYTES = 4 << 20  # eager calls keep a second, graph-only workspace ready up to this size (decode batches)
 
@@ -266,6 +327,10 @@ class QuantLinearLUTFused(QuantLinearLUT):
         if not x2.is_contiguous():
             x2 = x2.contiguous()
         rows = x2.shape[0]
+        if self.dense_min_rows is not None and rows >= self.dense_min_rows:
+            self.__dict__["_last_route"] = "dense"
+            return self._forward_dense(x, x2)
+        self.__dict__["_last_route"] = "fused"
         dev = x.get_device()
         out = torch.empty((rows, N), dtype=torch.float16, device=x.device)
         lin, ref, _keep = self._descriptor(dev, quant_cuda._raw_stream(dev))
