@@ -427,6 +427,44 @@ typedef struct sqllm_dequant_desc {
 } sqllm_dequant_desc;
 int sqllm_dequant(const sqllm_dequant_desc* d, sqllm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Encode: the inverse of sqllm_dequant -- from a weight matrix and its per-channel codebooks to the operands of an op,
+ *
+ *     idx(k, n) = the first j minimising |fl32(w[n, k] - lookup_table[n, j])|      (strict < over ascending j)
+ *     z_n       = the entry of lookup_table[n, :] with the smallest |c|            (ties: the lowest index)
+ *
+ * weight is [N, ld] with K contiguous (nn.Linear.weight), fp32 or fp16 (widened exactly); `mask` (optional) is [N, K],
+ * one byte per weight, non-zero = outlier candidate.  A position is an OUTLIER iff mask != 0, w != 0 and
+ * fl32(w - z_n) != 0.  Every masked position (outlier or not) gets the index of z_n in qweight; every other position
+ * idx(k, n).  These are the rules of the reference's packer (quant.py:117-131), so a layer encoded here equals one it packed.
+ *
+ * sqllm_encode writes all of qweight [K/32*bits, N] and, with a mask, all of rows [N + 1]: the exclusive scan of the
+ * per-channel outlier counts (rows[0] == 0, rows[N] == nnz < 2^31), overwritten, never accumulated into.  It enqueues
+ * one kernel without a mask and three nodes with one (a zero-fill of rows, the encode kernel, the scan); the counts are
+ * integers, so the result does not depend on any order.
+ * sqllm_encode_csr takes the same descriptor with the rows sqllm_encode wrote, and `nnz` >= rows[N], the capacity of
+ * cols / vals (the caller reads rows[N] back to size them).  It writes cols[e] = k and vals[e] = fl32(w - z_n) for every
+ * outlier, channel by channel and in ascending k within a channel, each at a position computed from rows and its rank
+ * -- no atomics: the result is deterministic, byte for byte.  Nothing is written at or beyond cols / vals [nnz].  One kernel.
+ * Both allocate nothing, retain nothing and never synchronise: a stream capture holds kernel and memset nodes only.
+ * SQLLM_E_NULL for a NULL descriptor, weight, lookup_table or qweight, for NULL rows with a mask, and in
+ * sqllm_encode_csr for a NULL mask, rows, cols or vals; SQLLM_E_BITS; SQLLM_E_SHAPE for bad K / N, ld < K, an ld that is
+ * no multiple of 8 (fp16) / 4 (fp32) or an unknown weight_dtype; SQLLM_E_ALIGN for a weight or qweight that is not
+ * 16-byte aligned or a mask that is not 8-byte aligned; SQLLM_E_SPARSE for nnz < 0 -- all before the device is touched.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_encode_desc {
+  int32_t bits, K, N;        /* bits in {3, 4}; K % 32 == 0; N % 4 == 0 */
+  int32_t weight_dtype;      /* SQLLM_DTYPE_* */
+  const void* weight;        /* [N, ld] of weight_dtype, 16-byte aligned */
+  int64_t ld;                /* elements per weight row, >= K; for fp16 a multiple of 8, for fp32 of 4 */
+  const float* lookup_table; /* [N, 2^bits] */
+  const uint8_t* mask;       /* [N, K] or NULL: no outliers, rows is not touched */
+  int32_t* qweight;          /* out: [K/32*bits, N], 16-byte aligned */
+  int32_t* rows;             /* [N + 1]: written by sqllm_encode, read by sqllm_encode_csr */
+} sqllm_encode_desc;
+int sqllm_encode(const sqllm_encode_desc* d, sqllm_stream_t stream);
+int sqllm_encode_csr(const sqllm_encode_desc* d, int32_t* cols, float* vals, int32_t nnz, sqllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,13 @@ class SqllmDequant(ctypes.Structure):
     _fields_ = [("op", SqllmOp), ("out", c_void_p), ("ld", ctypes.c_int64), ("out_dtype", c_int32)]
 
 
+class SqllmEncode(ctypes.Structure):
+    """struct sqllm_encode_desc (include/sqllm_hip.h): weight + codebooks (+ mask) -> qweight (+ rows)."""
+
+    _fields_ = [("bits", c_int32), ("K", c_int32), ("N", c_int32), ("weight_dtype", c_int32), ("weight", c_void_p),
+                ("ld", ctypes.c_int64), ("lookup_table", c_void_p), ("mask", c_void_p), ("qweight", c_void_p), ("rows", c_void_p)]
+
+
 DTYPE_F32, DTYPE_F16 = 0, 1  # SQLLM_DTYPE_*
 
 P = c_void_p  # every device pointer crosses as void*
@@ -98,6 +105,8 @@ SIGNATURES = {
     "sqllm_nuq_workspace_bytes": [POINTER(SqllmNuq)],
     "sqllm_nuq_fit": [POINTER(SqllmNuq), P, ctypes.c_int64, P],
     "sqllm_dequant": [POINTER(SqllmDequant), P],
+    "sqllm_encode": [POINTER(SqllmEncode), P],
+    "sqllm_encode_csr": [POINTER(SqllmEncode), P, P, c_int32, P],
 }
 for _b in (3, 4):
     SIGNATURES[f"sqllm_vecquant{_b}matmul_nuq_perchannel"] = _DENSE

@@ -3,8 +3,9 @@
 The reference's route is quantization/nuq.py (one sklearn KMeans per output channel on the CPU: Lloyd from a k-means++
 start, a local optimum) followed by quantization/pack.py.  Here the codebooks are the EXACT optimum of the same
 objective, sum over a row of g * (w - c)^2 with g the Fisher diagonal, computed per row by the HIP kernel behind
-sqllm_nuq_fit (csrc/sqllm_nuq.hip); torch does the plumbing around it (sorting, index assignment) and
-squeezellm_amd.pack / .checkpoint produce the operands and the checkpoint.
+sqllm_nuq_fit (csrc/sqllm_nuq.hip); torch does the plumbing around it (sorting, the outlier mask), sqllm_encode
+(csrc/sqllm_encode.hip, through pack.encode_layer) turns weight + codebooks + mask into the packed operands, and
+squeezellm_amd.checkpoint writes the checkpoint.
 
     python -m squeezellm_amd.nuq --model sd.pt --gradient g.pt --bits 4 --out sq.pt \\
         [--sensitivity 0.05] [--outlier-config cfg.json] [--topx 0]
@@ -27,15 +28,10 @@ _SHORT = {"q_proj": "q", "k_proj": "k", "v_proj": "v", "o_proj": "o", "out_proj"
 WORKSPACE_BUDGET = 1 << 30  # bytes of kernel workspace one chunk of rows may use
 
 
-def remove_outliers(weight: torch.Tensor, gradient: torch.Tensor | None = None, sensitivity: float = 0.0,
-                    threshold: float | None = None):
-    """Split a weight into (dense, outliers), both fp32 of its shape, as squeezellm/outliers.py does for one module:
-    first the `sensitivity` percent of entries with the largest gradient (the threshold is the num-th largest gradient
-    and only entries STRICTLY above it go: outliers.py:15-18), then, on what is left, every entry with
-    w >= threshold or w <= -threshold (outliers.py:51-54); the second set adds to the first.  num == 0 means no
-    sensitivity outliers (the reference would fail there)."""
-    w = weight.to(torch.float32)
-    outliers = torch.zeros_like(w)
+def _outlier_masks(w: torch.Tensor, gradient: torch.Tensor | None, sensitivity: float, threshold: float | None):
+    """The two boolean masks remove_outliers applies one after the other (None: that step does nothing): the
+    sensitivity outliers, then the threshold outliers of what the first step left."""
+    t = t2 = None
     if sensitivity:
         if gradient is None:
             raise ValueError("sensitivity-based outliers need the gradient")
@@ -44,12 +40,41 @@ def remove_outliers(weight: torch.Tensor, gradient: torch.Tensor | None = None, 
         if num > 0:
             thres = g.reshape(-1).topk(k=num).values[-1]
             t = g > thres
-            outliers = w * t
-            w = w * ~t
     if threshold is not None:
-        t = torch.logical_or(w >= threshold, w <= -threshold)
-        outliers = outliers + w * t
+        left = w if t is None else w * ~t
+        t2 = torch.logical_or(left >= threshold, left <= -threshold)
+    return t, t2
+
+
+def outlier_mask(weight: torch.Tensor, gradient: torch.Tensor | None = None, sensitivity: float = 0.0,
+                 threshold: float | None = None) -> torch.Tensor:
+    """The boolean mask [N, K] of the positions remove_outliers takes out of the dense part (True = outlier candidate;
+    a candidate whose weight is 0 leaves no outlier behind) -- what pack.encode_layer takes as `mask`."""
+    w = weight.to(torch.float32)
+    t, t2 = _outlier_masks(w, gradient, sensitivity, threshold)
+    if t is None and t2 is None:
+        return torch.zeros(w.shape, dtype=torch.bool, device=w.device)
+    if t is None or t2 is None:
+        return t if t2 is None else t2
+    return torch.logical_or(t, t2)
+
+
+def remove_outliers(weight: torch.Tensor, gradient: torch.Tensor | None = None, sensitivity: float = 0.0,
+                    threshold: float | None = None):
+    """Split a weight into (dense, outliers), both fp32 of its shape, as squeezellm/outliers.py does for one module:
+    first the `sensitivity` percent of entries with the largest gradient (the threshold is the num-th largest gradient
+    and only entries STRICTLY above it go: outliers.py:15-18), then, on what is left, every entry with
+    w >= threshold or w <= -threshold (outliers.py:51-54); the second set adds to the first.  num == 0 means no
+    sensitivity outliers (the reference would fail there).  outlier_mask returns the positions alone."""
+    w = weight.to(torch.float32)
+    outliers = torch.zeros_like(w)
+    t, t2 = _outlier_masks(w, gradient, sensitivity, threshold)
+    if t is not None:
+        outliers = w * t
         w = w * ~t
+    if t2 is not None:
+        outliers = outliers + w * t2
+        w = w * ~t2
     return w, outliers
 
 
@@ -63,6 +88,12 @@ def fit_lut(weight: torch.Tensor, gradient: torch.Tensor | None = None, bits: in
     ascending, idx uint8 [N, K], cost fp64 [N]).  The sample weights are gradient * (weight != 0) (nuq.py:172-173),
     ones without a gradient; a row whose weights sum to 0 is fitted with unit weights.  idx is the first j that
     minimises |w - lut_j| in fp32 -- the rule pack.outliers_to_csr uses to find the zero-nearest centroid."""
+    lut, cost, w = _fit_codebooks(weight, gradient, bits)
+    return lut, assign_indices(w, lut), cost
+
+
+def _fit_codebooks(weight: torch.Tensor, gradient: torch.Tensor | None, bits: int):
+    """fit_lut without the index matrix: (lookup_table, cost, the weight as contiguous fp32)."""
     if bits not in (3, 4):
         raise ValueError("bits must be 3 or 4")
     if weight.dim() != 2 or not weight.is_cuda:
@@ -99,7 +130,7 @@ def fit_lut(weight: torch.Tensor, gradient: torch.Tensor | None = None, bits: in
                               centroids=lut[r0:r1].data_ptr(), cost=cost[r0:r1].data_ptr())
             _lib.check(lib.sqllm_nuq_fit(ctypes.byref(d), ws.data_ptr(), ws.numel(), stream), "sqllm_nuq_fit")
             del vals, wts, order  # (the caching allocator keeps them stream-ordered)
-    return lut, assign_indices(w, lut), cost
+    return lut, cost, w
 
 
 def assign_indices(weight: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
@@ -123,11 +154,19 @@ def quantize_linear(weight: torch.Tensor, gradient: torch.Tensor | None, bits: i
     full_rows; the dense part is fitted with the outliers zeroed, as nuq.py does."""
     dev = weight.device
     g = None if gradient is None else gradient.to(dev)
-    dense, outliers = remove_outliers(weight, g, sensitivity, threshold)
-    lut, idx, _ = fit_lut(dense, g, bits)
     sparse = bool(sensitivity) or threshold is not None
-    return pack.pack_layer(idx, lut, bits, outliers if sparse else None, topX=topX if sparse else 0,
-                           bias=None if bias is None else bias.to(device=dev, dtype=torch.float32))
+    mask = outlier_mask(weight, g, sensitivity, threshold) if sparse else None
+    dense = weight.to(torch.float32)
+    if mask is not None:
+        dense = dense * ~mask
+    lut, _, dense = _fit_codebooks(dense, g, bits)  # (rejects non-finite weights)
+    b32 = None if bias is None else bias.to(device=dev, dtype=torch.float32)
+    if weight.shape[0] % 4:  # not a shape the kernels take (N % 4 == 0): the torch packer still writes its buffers
+        return pack.pack_layer(assign_indices(dense, lut), lut, bits, weight.to(torch.float32) * mask if sparse else None,
+                               topX=topX if sparse else 0, bias=b32)
+    del dense
+    # fit, then encode on the GPU: neither the uint8 index matrix nor the dense outlier matrix is built
+    return pack.encode_layer(weight, lut, bits, mask, topX=topX if sparse else 0, bias=b32, check_finite=False)
 
 
 def reconstruction_error(weight: torch.Tensor, gradient: torch.Tensor | None, layer: dict) -> dict:

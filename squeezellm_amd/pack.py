@@ -9,6 +9,8 @@ and adds the missing top-X extraction.  It is host-side tooling around the hot p
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 
@@ -115,4 +117,60 @@ def pack_layer(idx_nk: torch.Tensor, lookup_table: torch.Tensor, bits: int, outl
         if topX > 0:
             rows, cols, vals, fr, fi = extract_topx_rows(rows, cols, vals, K, topX)
         layer.update(rows=rows, cols=cols, vals=vals, full_rows=fr, full_row_indices=fi)
+    return layer
+
+
+def encode_layer(weight: torch.Tensor, lookup_table: torch.Tensor, bits: int, mask: torch.Tensor | None = None,
+                 topX: int = 0, bias: torch.Tensor | None = None, check_finite: bool = True) -> dict:
+    """The dict pack_layer returns, straight from a weight [N, K] (fp16 or fp32; anything else is widened to fp32), its
+    codebooks [N, 2**bits] and an optional boolean outlier mask [N, K] -- CUDA tensors only, on the GPU in one pass
+    (sqllm_encode / sqllm_encode_csr, csrc/sqllm_encode.hip) instead of nuq.assign_indices + pack_layer: no index matrix,
+    no int64 temporaries, no dense outlier matrix.  Bit for bit what
+        pack_layer(assign_indices(weight * ~mask, lookup_table), lookup_table, bits, weight * mask, topX, bias)
+    gives.  One 4-byte read-back (rows[N]) sizes cols / vals.  A weight that is a view with a row stride (a multiple of 8
+    elements for fp16, 4 for fp32, 16-byte aligned) is read in place.  Non-finite weights are rejected, as fit_lut does."""
+    from . import _lib
+
+    if bits not in (3, 4):
+        raise NotImplementedError("Only 3 and 4 bits is supported.")
+    if weight.dim() != 2 or not weight.is_cuda:
+        raise ValueError("encode_layer takes a 2-D CUDA tensor (the CPU path is pack_layer)")
+    N, K = weight.shape
+    if tuple(lookup_table.shape) != (N, 1 << bits):
+        raise ValueError(f"lookup_table is {tuple(lookup_table.shape)}, expected {(N, 1 << bits)}")
+    dev = weight.device
+    w = weight if weight.dtype in (torch.float16, torch.float32) else weight.to(torch.float32)
+    f16 = w.dtype == torch.float16
+    if K and N and (w.stride(1) != 1 or w.stride(0) < K or w.stride(0) % (8 if f16 else 4) or w.data_ptr() % 16):
+        w = w.contiguous()
+    if check_finite and not bool(torch.isfinite(w).all()):
+        raise ValueError("weight holds non-finite values")
+    lut = lookup_table.to(device=dev, dtype=torch.float32).contiguous()
+    m8 = None
+    if mask is not None:
+        if tuple(mask.shape) != (N, K):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match weight {(N, K)}")
+        m8 = mask.to(device=dev, dtype=torch.bool).contiguous().view(torch.uint8)
+    qweight = torch.empty((K // 32 * bits, N), dtype=torch.int32, device=dev)
+    rows = torch.empty(N + 1, dtype=torch.int32, device=dev) if m8 is not None else None
+    lib = _lib.load()
+    d = _lib.SqllmEncode(bits=bits, K=K, N=N, weight_dtype=_lib.DTYPE_F16 if f16 else _lib.DTYPE_F32, weight=w.data_ptr(),
+                         ld=w.stride(0) if K and N else K, lookup_table=lut.data_ptr(),
+                         mask=None if m8 is None else m8.data_ptr(), qweight=qweight.data_ptr(),
+                         rows=None if rows is None else rows.data_ptr())
+    layer = dict(bits=bits, K=K, N=N, qweight=qweight, lookup_table=lut, bias=bias,
+                 rows=None, cols=None, vals=None, full_rows=None, full_row_indices=None)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.sqllm_encode(ctypes.byref(d), stream), "sqllm_encode")
+        if m8 is not None:
+            nnz = int(rows[N].item())  # the one read-back: sizes cols / vals
+            cols = torch.empty(nnz, dtype=torch.int32, device=dev)
+            vals = torch.empty(nnz, dtype=torch.float32, device=dev)
+            if nnz:
+                _lib.check(lib.sqllm_encode_csr(ctypes.byref(d), cols.data_ptr(), vals.data_ptr(), nnz, stream), "sqllm_encode_csr")
+            fr = fi = None
+            if topX > 0:
+                rows, cols, vals, fr, fi = extract_topx_rows(rows, cols, vals, K, topX)
+            layer.update(rows=rows, cols=cols, vals=vals, full_rows=fr, full_row_indices=fi)
     return layer
