@@ -465,6 +465,72 @@ typedef struct sqllm_encode_desc {
 int sqllm_encode(const sqllm_encode_desc* d, sqllm_stream_t stream);
 int sqllm_encode_csr(const sqllm_encode_desc* d, int32_t* cols, float* vals, int32_t nnz, sqllm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Outlier selection: exact order statistics of a whole matrix, and the mask sqllm_encode takes.
+ *
+ * The reference decides a linear's outliers from the quartiles of all its weights (np.quantile on the CPU,
+ * quantization/generate_outlier_config.py:47-53) and from the num-th largest gradient (topk, squeezellm/outliers.py:15-18).
+ * Both are order statistics of one matrix of 16 M .. 180 M elements.  sqllm_select finds up to 8 of them in one call:
+ *
+ *     out[i]  = np.sort(values[:, :cols], axis=None)[ranks[i]]     compared as a VALUE: -0.0 and +0.0 are one value,
+ *                                                                  returned as +0.0; +-inf order as usual
+ *     less[i] = (values[:, :cols] < out[i]).sum()
+ *
+ * by a most-significant-digit radix select on the order-preserving unsigned key of every element (-0 -> +0, then all bits
+ * of a negative value flipped, the sign bit of a non-negative one set; fp16 is widened exactly, so its keys are taken on
+ * the 16 bits of the half): three passes over the matrix for fp32 (digits of 11 + 11 + 10 bits), two for fp16 (11 + 5),
+ * each a histogram kernel (16-byte non-temporal loads, one LDS histogram per live prefix -- ranks that share a prefix
+ * share one --, 64-bit integer atomics for the non-empty bins) and a one-workgroup kernel that picks every rank's bin.
+ * Only integers are counted: the result is a function of the input alone, two runs are byte-identical.  NaN inputs give an
+ * unspecified result (never a fault or a hang; nuq checks finiteness before it calls).  Elements [cols, ld) of a row are never read.
+ * The call enqueues one memset node and 2 x passes kernels on `stream`; it allocates nothing, retains nothing and never
+ * synchronises.  `workspace`: workspace_bytes >= sqllm_select_workspace_bytes(d) of device memory, 16-byte aligned,
+ * contents irrelevant before and after (the library zero-fills what it needs), one call at a time.
+ * SQLLM_E_NULL for a NULL descriptor, values, out or workspace; SQLLM_E_SHAPE for an unknown dtype, n_ranks outside 1..8,
+ * a rank outside [0, rows * cols), rows or cols < 1, cols or ld that is no multiple of 4 (fp32) / 8 (fp16), ld < cols,
+ * rows * cols >= 2^40 or a short workspace; SQLLM_E_ALIGN for values or workspace not 16-byte aligned (out: 4, less: 8)
+ * -- all before the device is touched.
+ * ------------------------------------------------------------------------------------------- */
+#define SQLLM_SELECT_MAX_RANKS 8
+typedef struct sqllm_select_desc {
+  int32_t dtype;               /* SQLLM_DTYPE_F32 / _F16 (widened exactly) */
+  int32_t n_ranks;             /* 1..8 */
+  const void* values;          /* [rows, ld], 16-byte aligned; elements [cols, ld) of a row are never read */
+  int64_t rows, cols, ld;      /* cols % 4 == 0 (fp32) / % 8 == 0 (fp16); ld >= cols, same multiple; rows*cols < 2^40 */
+  int64_t ranks[SQLLM_SELECT_MAX_RANKS]; /* 0-based positions in ascending order, each in [0, rows*cols); any order, repeats allowed */
+  float* out;                  /* device [n_ranks]: the value at each rank */
+  int64_t* less;               /* device [n_ranks] or NULL: how many elements are strictly below out[i] */
+} sqllm_select_desc;
+/* bytes of workspace sqllm_select needs for this descriptor (the pointers are not looked at; no GPU needed; grows with
+ * n_ranks), or a negative SQLLM_E_* code for bad shapes */
+int64_t sqllm_select_workspace_bytes(const sqllm_select_desc* d);
+int sqllm_select(const sqllm_select_desc* d, void* workspace, int64_t workspace_bytes, sqllm_stream_t stream);
+
+/* The outlier mask of one linear (nuq.outlier_mask; squeezellm/outliers.py:18,53-55), both operands widened to fp32:
+ *
+ *     mask[n, k] = (g[n, k] > *g_threshold) || (w[n, k] >= *w_threshold) || (w[n, k] <= -*w_threshold)
+ *
+ * a NULL gradient / w_threshold contributes false.  The thresholds are DEVICE pointers: a sqllm_select on the same stream
+ * feeds the mask without a host round trip.  mask is written as bytes 0 / 1 for all of [N, K] and nothing else; *count is
+ * OVERWRITTEN with the number of ones.  One kernel (one integer atomic per workgroup) plus a memset node for count;
+ * allocates nothing, retains nothing, never synchronises.
+ * SQLLM_E_NULL for a NULL descriptor or weight, a gradient without g_threshold or the reverse, mask and count both NULL;
+ * SQLLM_E_SHAPE for K % 32 != 0, K < 1, N < 1, N * K >= 2^40 (the select's bound; the kernel's 32-bit partial counts are
+ * argued below it), an unknown dtype, ld < K or an ld that is no multiple of 8 (fp16) / 4 (fp32);
+ * SQLLM_E_ALIGN for a weight or gradient not 16-byte aligned, a mask or count not 8-byte aligned, a threshold not 4-byte
+ * aligned -- all before the device is touched. */
+typedef struct sqllm_outlier_desc {
+  int32_t weight_dtype, grad_dtype;   /* SQLLM_DTYPE_* */
+  int32_t K, N;                       /* K % 32 == 0, N >= 1, N * K < 2^40 */
+  const void* weight;  int64_t ld_w;  /* [N, ld_w], 16-byte aligned, ld rules of sqllm_encode */
+  const void* gradient; int64_t ld_g; /* same rules, or NULL: no sensitivity step */
+  const float* g_threshold;           /* DEVICE [1]; required iff gradient != NULL */
+  const float* w_threshold;           /* DEVICE [1], or NULL: no threshold step */
+  uint8_t* mask;                      /* out [N, K], 0 / 1, 8-byte aligned; NULL: count only */
+  int64_t* count;                     /* DEVICE [1] or NULL: number of 1s, OVERWRITTEN */
+} sqllm_outlier_desc;
+int sqllm_outlier_mask(const sqllm_outlier_desc* d, sqllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,24 @@ class SqllmEncode(ctypes.Structure):
                 ("ld", ctypes.c_int64), ("lookup_table", c_void_p), ("mask", c_void_p), ("qweight", c_void_p), ("rows", c_void_p)]
 
 
+SELECT_MAX_RANKS = 8  # SQLLM_SELECT_MAX_RANKS
+
+
+class SqllmSelect(ctypes.Structure):
+    """struct sqllm_select_desc (include/sqllm_hip.h): up to 8 exact order statistics of a matrix."""
+
+    _fields_ = [("dtype", c_int32), ("n_ranks", c_int32), ("values", c_void_p), ("rows", ctypes.c_int64), ("cols", ctypes.c_int64),
+                ("ld", ctypes.c_int64), ("ranks", ctypes.c_int64 * SELECT_MAX_RANKS), ("out", c_void_p), ("less", c_void_p)]
+
+
+class SqllmOutlier(ctypes.Structure):
+    """struct sqllm_outlier_desc (include/sqllm_hip.h): weight (+ gradient) and device thresholds -> byte mask, count."""
+
+    _fields_ = [("weight_dtype", c_int32), ("grad_dtype", c_int32), ("K", c_int32), ("N", c_int32), ("weight", c_void_p),
+                ("ld_w", ctypes.c_int64), ("gradient", c_void_p), ("ld_g", ctypes.c_int64), ("g_threshold", c_void_p),
+                ("w_threshold", c_void_p), ("mask", c_void_p), ("count", c_void_p)]
+
+
 DTYPE_F32, DTYPE_F16 = 0, 1  # SQLLM_DTYPE_*
 
 P = c_void_p  # every device pointer crosses as void*
@@ -107,6 +125,9 @@ SIGNATURES = {
     "sqllm_dequant": [POINTER(SqllmDequant), P],
     "sqllm_encode": [POINTER(SqllmEncode), P],
     "sqllm_encode_csr": [POINTER(SqllmEncode), P, P, c_int32, P],
+    "sqllm_select_workspace_bytes": [POINTER(SqllmSelect)],
+    "sqllm_select": [POINTER(SqllmSelect), P, ctypes.c_int64, P],
+    "sqllm_outlier_mask": [POINTER(SqllmOutlier), P],
 }
 for _b in (3, 4):
     SIGNATURES[f"sqllm_vecquant{_b}matmul_nuq_perchannel"] = _DENSE
@@ -141,7 +162,8 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.argtypes = argtypes
         fn.restype = (c_char_p if name == "sqllm_error_string" else
-                      ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes") else c_int)
+                      ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes",
+                                               "sqllm_select_workspace_bytes") else c_int)
     if lib.sqllm_abi_version() != 1:
         raise RuntimeError(f"libsqllm_hip.so ABI {lib.sqllm_abi_version()} != 1 expected by this package")
     _lib = lib
@@ -216,4 +238,12 @@ def nuq_workspace_bytes(bits: int, N: int, K: int) -> int:
     d = SqllmNuq(bits=bits, N=N, K=K)
     n = int(load().sqllm_nuq_workspace_bytes(ctypes.byref(d)))
     check(n if n < 0 else 0, "sqllm_nuq_workspace_bytes")
+    return n
+
+
+def select_workspace_bytes(dtype: int, n_ranks: int, rows: int, cols: int, ld: int | None = None) -> int:
+    """Bytes of device workspace one sqllm_select of these shapes needs (no GPU needed); raises on bad shapes."""
+    d = SqllmSelect(dtype=dtype, n_ranks=n_ranks, rows=rows, cols=cols, ld=cols if ld is None else ld)
+    n = int(load().sqllm_select_workspace_bytes(ctypes.byref(d)))
+    check(n if n < 0 else 0, "sqllm_select_workspace_bytes")
     return n
