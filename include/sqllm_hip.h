@@ -181,6 +181,39 @@ int sqllm_linear_f16(const sqllm_linear* lin, sqllm_stream_t stream);
 int sqllm_linear_f16_groups(const sqllm_linear* lins, const int32_t* group_sizes, int32_t n_groups,
                             sqllm_stream_t stream, int32_t* n_done);
 
+/* The same linear with bf16 at its two ends -- the 16-bit type most checkpoints are held in:
+ *
+ *     out[b, n] = bf16_rne( bias[n] + sum_k W[n, k] * float(x[b, k]) )      (all three weight terms)
+ *
+ * The same sqllm_linear struct:  op.vec  is bf16 [batch, K] (widened EXACTLY: a 16-bit shift),  op.mul  is bf16
+ * [batch, N], OVERWRITTEN;  bias  stays fp32.  Everything else is sqllm_linear_f16's, word for word: one kernel, nothing
+ * allocated, validation, grouping rules, the 63-contribution limit and every error code; the workspace and
+ * sqllm_linear_workspace_bytes are unchanged, and because a workspace is all-zero between launches ONE workspace may
+ * serve fp16 and bf16 launches alternately on one stream.  Inside a contribution (a dense K slice with the top-X rows of
+ * its tile, a CSR chunk's part of a row) accumulation is fp32 in the SAME ORDER as the fp16 kernel; between contributions
+ * it is the 2^-28 fixed-point word; the finished sum plus the bias is rounded ONCE, to nearest-even, to bf16.  NaN and
+ * +-inf in the operands travel through the three sticky flag bits as above.
+ *
+ * One thing differs, and it differs loudly.  The word holds contributions only up to +-131072 (2^17).  The fp16 kernel
+ * clamps there, because such a result is not finite in fp16 anyway; in bf16 it IS finite, and a clamp would return a wrong
+ * finite number.  sqllm_linear_bf16 therefore treats a FINITE contribution with |v| > 131072 as the infinity of its sign:
+ * the matching sticky flag is set and nothing is added.  So
+ *   - a result built from in-range contributions is exact to the fixed-point rounding (2^-28 per contribution), up to
+ *     63 x 131072 in magnitude;
+ *   - a result with a contribution beyond the range is +inf or -inf, or NaN if contributions of both signs were beyond
+ *     it -- never a finite wrong value, with ONE exception: a CSR chunk of 1024 consecutive non-zeros that spans more
+ *     than 2048 rows (an extremely sparse region of the matrix) adds its values to the word UNCOUNTED, one per non-zero,
+ *     and while such a word is transiently negative a sticky flag can be lost (the same corner in which the fp16 kernel
+ *     can report a NaN as a finite number).  There, a single outlier product vals[i] * x[cols[i]] beyond +-131072 may be
+ *     dropped and the result come out finite and wrong.  Dense contributions and ordinary CSR chunks are not affected.
+ * The reference's fp32 path (and the fp32 operator names here) would return the finite value there: a caller whose
+ * activations can drive one K slice of one output past 131072 in magnitude must use those.  (How K is cut into
+ * contributions is the planner's choice -- sqllm_plan_query: k_slices -- so between 131072 and 63 x 131072 whether a
+ * large result comes out finite depends on the shape; below 131072 in sum_k |W[n, k] x[b, k]| it always does.) */
+int sqllm_linear_bf16(const sqllm_linear* lin, sqllm_stream_t stream);
+int sqllm_linear_bf16_groups(const sqllm_linear* lins, const int32_t* group_sizes, int32_t n_groups,
+                             sqllm_stream_t stream, int32_t* n_done);
+
 /* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
@@ -407,23 +440,24 @@ int sqllm_nuq_fit(const sqllm_nuq* d, void* workspace, int64_t workspace_bytes, 
  *
  * written as out[n * ld + k] for every n < N, k < K: [N, K] with K contiguous, the layout of nn.Linear.weight.
  * Every element is summed in fp32 (duplicate CSR entries and duplicate top-X indices accumulate, as in the op)
- * and rounded ONCE: not at all for SQLLM_DTYPE_F32, to nearest-even _Float16 for SQLLM_DTYPE_F16 (overflow gives
- * +-inf; NaN / inf in the operands propagate).  A position with at most one sparse contribution is bit-exact:
+ * and rounded ONCE: not at all for SQLLM_DTYPE_F32, to nearest-even _Float16 for SQLLM_DTYPE_F16, to nearest-even bf16
+ * for SQLLM_DTYPE_BF16 (overflow gives +-inf; NaN / inf in the operands propagate).  A position with at most one sparse contribution is bit-exact:
  * the table entry, or one fp32 add.  Elements k in [K, ld) of a row are NOT written; nothing else is.
  * Enqueues ONE kernel on `stream`; allocates nothing, retains nothing, never synchronises (option "validate_csr"
  * aside, which blocks as it does for every launch): a stream capture of the call holds one kernel node.
  * SQLLM_E_NULL for a NULL descriptor, out, qweight or lookup_table; SQLLM_E_BITS; SQLLM_E_SHAPE for bad K / N,
- * ld < K, an ld that is no multiple of 8 (fp16) / 4 (fp32) or an unknown out_dtype; SQLLM_E_ALIGN for a qweight
+ * ld < K, an ld that is no multiple of 8 (fp16, bf16) / 4 (fp32) or an unknown out_dtype; SQLLM_E_ALIGN for a qweight
  * or out that is not 16-byte aligned; SQLLM_E_SPARSE as for sqllm_launch -- all before the device is touched.
  * ------------------------------------------------------------------------------------------- */
 #define SQLLM_DTYPE_F32 0
 #define SQLLM_DTYPE_F16 1
+#define SQLLM_DTYPE_BF16 3 /* sqllm_dequant's out_dtype only (2 stays unassigned); the offline entry points below take F32 / F16 */
 typedef struct sqllm_dequant_desc {
   sqllm_op op;       /* bits, K, N, qweight, lookup_table, CSR and top-X operands as for sqllm_launch;
                         vec, mul and batch are ignored */
   void* out;         /* [N, ld] of out_dtype, 16-byte aligned */
-  int64_t ld;        /* elements per output row, >= K; for fp16 a multiple of 8, for fp32 of 4 */
-  int32_t out_dtype; /* SQLLM_DTYPE_* */
+  int64_t ld;        /* elements per output row, >= K; for fp16 and bf16 a multiple of 8, for fp32 of 4 */
+  int32_t out_dtype; /* SQLLM_DTYPE_F32 / _F16 / _BF16 */
 } sqllm_dequant_desc;
 int sqllm_dequant(const sqllm_dequant_desc* d, sqllm_stream_t stream);
 

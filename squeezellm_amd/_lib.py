@@ -88,6 +88,7 @@ class SqllmOutlier(ctypes.Structure):
 
 
 DTYPE_F32, DTYPE_F16 = 0, 1  # SQLLM_DTYPE_*
+DTYPE_BF16 = 3  # (sqllm_dequant's out_dtype only; 2 is unassigned)
 
 P = c_void_p  # every device pointer crosses as void*
 
@@ -115,6 +116,8 @@ SIGNATURES = {
     "sqllm_linear_workspace_bytes": [POINTER(SqllmOp)],
     "sqllm_linear_f16": [POINTER(SqllmLinear), P],
     "sqllm_linear_f16_groups": [POINTER(SqllmLinear), POINTER(c_int32), c_int32, P, POINTER(c_int32)],
+    "sqllm_linear_bf16": [POINTER(SqllmLinear), P],
+    "sqllm_linear_bf16_groups": [POINTER(SqllmLinear), POINTER(c_int32), c_int32, P, POINTER(c_int32)],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],

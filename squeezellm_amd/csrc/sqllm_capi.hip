@@ -538,7 +538,7 @@ bool takes_cols_path(const sqllm_op* op) { return !takes_mfma_path(op) && cols_r
 
 enum Route {
   kFusedTiles,   // ONE launch of the fused batch-tile kernel over the group (batch 1 and the small batches the other routes leave)
-  kFusedLinear,  // ... as the fused fp16 linear (sqllm_linear_f16)
+  kFusedLinear,  // ... as the fused 16-bit linear (sqllm_linear_f16 / sqllm_linear_bf16: one route, one plan, two kernels)
   kColsGroup,    // ONE launch of the column-lane kernel, its workgroups divided between the ops
   kFusedSmall,   // up to 16 rows on the split matrix-core kernel: ONE launch for the whole group, sparse roles included
   kPerOpMfma,    // one launch per op (the members of a group only share their input) of the matrix-core kernel (wide batches)
@@ -963,9 +963,11 @@ struct SmallScratch {
 };
 
 // The operands of launch `lp` of a planned group.  `lin` (optional): the fused-linear descriptors the ops were taken from.
-static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_linear* lin, const GroupPlan& plan, const LaunchPlan& lp) {
+static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_linear* lin, const GroupPlan& plan, const LaunchPlan& lp,
+                      bool bf16 = false) {
   a->x = ops[0].vec;
   a->linear = lin != nullptr;
+  a->bf16 = lin != nullptr && bf16;
   a->wide = lp.wide;
   a->wide_full_units = lp.wide_full_units;
   a->row_blocks = lp.row_blocks;
@@ -977,7 +979,7 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
     fill_segment(&ops[lp.first + i], &sg);
     sg.gm = plan.gm[lp.first + i];
     if (lin) {
-      // accumulate into the workspace plane; op->mul is the fp16 result
+      // accumulate into the workspace plane; op->mul is the fp16 / bf16 result
       sg.y = reinterpret_cast<float*>(lin[lp.first + i].workspace);
       sg.out16 = ops[lp.first + i].mul;
       sg.bias = lin[lp.first + i].bias;
@@ -989,9 +991,11 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
 // call the launcher(s) the plan names.  `lin` (optional) points at the fused-linear descriptors: the ops are then lin[i].op.
 // `ws` / `ws_bytes`: the caller's workspace (sqllm_launch_*_ws; sqllm_workspace_bytes says how much a group can use), or null.
 // `ws_entry`: the call came through a `_ws` entry point -- up to 16 rows nothing is allocated then, workspace or not.
+// `bf16` (fused linears only): vec and mul are bf16 -- same route, plan and workspace; the flag travels in LaunchArgs and
+// launch_fused hands such a launch to launch_linear_bf16 (sqllm_linear_bf16.hip), so the host layer calls the launchers it always did.
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, const sqllm_linear* lin = nullptr, void* ws = nullptr, int64_t ws_bytes = 0,
-                                    bool ws_entry = false) {
+                                    bool ws_entry = false, bool bf16 = false) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
   sqllm_op tmp[sqllm::kMaxSegments];
@@ -1037,7 +1041,7 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
     const LaunchPlan& lp = plan.launch[l];
     const sqllm_op* op = &ops[lp.first];
     sqllm::LaunchArgs a;
-    fill_args(&a, ops, lin, plan, lp);
+    fill_args(&a, ops, lin, plan, lp, bf16);
     a.ev_start = l == 0 ? e0 : nullptr;
     a.ev_stop = l == plan.n_launches - 1 ? e1 : nullptr;
     hipError_t e = hipSuccess;
@@ -1045,7 +1049,7 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
       case kFusedTiles:
       case kFusedLinear:
         if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: ablation bits, LDS pad, timeline buffer)
-        e = sqllm::launch_fused(op->bits, a, s);
+        e = sqllm::launch_fused(op->bits, a, s);  // (a.bf16, set above for the bf16 entry points: the launcher of sqllm_linear_bf16.hip)
         break;
       case kColsGroup:
       case kPerOpCols:
@@ -1085,13 +1089,13 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
 
 // A pass as consecutive same-input groups: `ops` or `lins`, group g of group_sizes[g] members; *n_done = groups enqueued.
 static int launch_groups(const sqllm_op* ops, const sqllm_linear* lins, const int32_t* group_sizes, int32_t n_groups, sqllm_stream_t stream,
-                         int32_t* n_done, void* ws = nullptr, int64_t ws_bytes = 0, bool ws_entry = false) {
+                         int32_t* n_done, void* ws = nullptr, int64_t ws_bytes = 0, bool ws_entry = false, bool bf16 = false) {
   if (n_done) *n_done = 0;
   if (n_groups < 0 || (n_groups > 0 && ((!ops && !lins) || !group_sizes))) return SQLLM_E_NULL;
   int32_t at = 0;
   for (int32_t g = 0; g < n_groups; ++g) {
     if (group_sizes[g] < 1) return SQLLM_E_GROUP;
-    int rc = launch_group_with_events(ops ? ops + at : nullptr, group_sizes[g], stream, nullptr, nullptr, lins ? lins + at : nullptr, ws, ws_bytes, ws_entry);
+    int rc = launch_group_with_events(ops ? ops + at : nullptr, group_sizes[g], stream, nullptr, nullptr, lins ? lins + at : nullptr, ws, ws_bytes, ws_entry, bf16);
     if (rc != SQLLM_OK) return rc;
     at += group_sizes[g];
     if (n_done) *n_done = g + 1;
@@ -1107,6 +1111,16 @@ int sqllm_linear_f16(const sqllm_linear* lin, sqllm_stream_t stream) {
 int sqllm_linear_f16_groups(const sqllm_linear* lins, const int32_t* group_sizes, int32_t n_groups,
                             sqllm_stream_t stream, int32_t* n_done) {
   return launch_groups(nullptr, lins, group_sizes, n_groups, stream, n_done);
+}
+
+int sqllm_linear_bf16(const sqllm_linear* lin, sqllm_stream_t stream) {
+  if (!lin) return SQLLM_E_NULL;
+  return launch_group_with_events(nullptr, 1, stream, nullptr, nullptr, lin, nullptr, 0, false, true);
+}
+
+int sqllm_linear_bf16_groups(const sqllm_linear* lins, const int32_t* group_sizes, int32_t n_groups,
+                             sqllm_stream_t stream, int32_t* n_done) {
+  return launch_groups(nullptr, lins, group_sizes, n_groups, stream, n_done, nullptr, 0, false, true);
 }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {

@@ -51,7 +51,8 @@ template <> struct Fmt<3> {
   static constexpr int kRows = 3;
   static constexpr int kK = 32;
 };
-// element type of vec: fp32 behind the reference operator names, fp16 for the fused linear
+// element type of vec: fp32 behind the reference operator names, fp16 for the fused linear (the bf16 linear,
+// sqllm_linear_bf16.hip, names its types itself)
 template <bool LIN> struct XType { using type = float; };
 template <> struct XType<true> { using type = _Float16; };
 // accumulator word: the caller's fp32 `mul`, or the fused linear's fixed-point workspace plane
@@ -455,7 +456,7 @@ __device__ __forceinline__ void step3_pair(const u32x4 (&slot)[3], float xslot0,
 // Contributions are clamped to +-2^17 (twice the largest finite fp16) so that the at most 63 of
 // them a column can receive stay inside the 55-bit field; sums beyond that are not finite in
 // fp16 anyway.  Rounding: 2^-28 absolute per contribution, far below one fp16 ulp of any normal
-// fp16 result.
+// fp16 result.  (The bf16 linear does not clamp: beyond +-2^17 a contribution counts as +-inf, see FixRange below.)
 //
 // Non-finite values (round 3).  The reference's fp32 atomics carry NaN / Inf through to the output
 // (squeezellm/quant.py:214-223: zeros, op, cast); an integer sum cannot, so the word's two top bits
@@ -465,7 +466,8 @@ __device__ __forceinline__ void step3_pair(const u32x4 (&slot)[3], float xslot0,
 // signs make a NaN, as inf - inf does); a non-finite value adds nothing to the sum.  The count keeps
 // bits 55-60 (at most 63 contributions).
 // (Only the wide-span CSR fallback adds values uncounted; while such a word is transiently negative an
-// OR may be lost -- a NaN is then reported as a finite number, as before round 3.)
+// OR may be lost -- a NaN is then reported as a finite number, as before round 3; in the bf16 linear the same goes for
+// the flag of an out-of-range value, whose add deposited nothing: the one case where its result can be finite and wrong.)
 // ------------------------------------------------------------------------------------------------
 typedef unsigned long long u64;
 constexpr int kFixShift = 28;
@@ -473,14 +475,36 @@ constexpr int kCountShift = 55;
 constexpr u64 kCountUnit = 1ull << kCountShift;
 constexpr u64 kNanFlag = 1ull << 63, kPosInfFlag = 1ull << 62, kNegInfFlag = 1ull << 61, kFlagMask = kNanFlag | kPosInfFlag | kNegInfFlag;
 
+// The 16-bit type of a fused linear's two ends (OT: what the activations arrive as and the finished columns leave as) decides
+// what a contribution beyond the word's +-2^17 means.  fp16: such a result is not finite in fp16 anyway -- clamp.  bf16
+// (sqllm_linear_bf16.hip): it IS finite there, and a clamp would hand back a wrong finite number, so a finite contribution
+// with |v| > 2^17 counts as the infinity of its sign -- flag set, nothing added: the same test with another constant.
+// (Operator instantiations, OT = the fp16 default, never reach any of this: their `lin` is null.)
+template <typename OT> struct FixRange {
+  static constexpr float kCarried = 3.402823466e38f;  // |v| up to here goes into the sum; beyond: the flags
+  static constexpr bool kClamp = true;
+};
+template <> struct FixRange<__bf16> {
+  static constexpr float kCarried = 131072.f;
+  static constexpr bool kClamp = false;  // (what is carried is in range already)
+};
+// element type of the fused linear's output for a vec type: fp32 vec is the operator ABI (no fused output, the fp16 rules by default)
+template <typename XT> struct OutType { using type = _Float16; };
+template <> struct OutType<__bf16> { using type = __bf16; };
+
+template <typename OT = _Float16>
 __device__ __forceinline__ u64 to_fixed(float v) {
-  v = (__builtin_fabsf(v) <= 3.402823466e38f) ? __builtin_fminf(__builtin_fmaxf(v, -131072.f), 131072.f) : 0.f;  // (NaN / inf ride in the flags)
+  if constexpr (FixRange<OT>::kClamp)
+    v = (__builtin_fabsf(v) <= 3.402823466e38f) ? __builtin_fminf(__builtin_fmaxf(v, -131072.f), 131072.f) : 0.f;  // (NaN / inf ride in the flags)
+  else
+    v = (__builtin_fabsf(v) <= FixRange<OT>::kCarried) ? v : 0.f;  // (NaN / inf / out of range ride in the flags)
   return (u64)(long long)__builtin_rintf(v * (float)(1 << kFixShift));
 }
 
-// set the word's sticky flag if `v` is not finite (call before the add that deposits v)
+// set the word's sticky flag if `v` is not finite -- bf16: or beyond the word's range -- (call before the add that deposits v)
+template <typename OT = _Float16>
 __device__ __forceinline__ void flag_nonfinite(u64* word, float v) {
-  if (!(__builtin_fabsf(v) <= 3.402823466e38f))
+  if (!(__builtin_fabsf(v) <= FixRange<OT>::kCarried))
     __hip_atomic_fetch_or(reinterpret_cast<__attribute__((address_space(1))) u64*>(reinterpret_cast<uintptr_t>(word)),
                           (v != v) ? kNanFlag : (v > 0.f ? kPosInfFlag : kNegInfFlag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -491,7 +515,8 @@ __device__ __forceinline__ int csr_chunks_of_row(int r0, int r1) {
 }
 
 // `total` = the word after this thread's own counted add.  Finishes the column if that add was the
-// last of the `target` contributions.
+// last of the `target` contributions.  OT: the element type of the output, known at compile time (one rounding, to nearest-even).
+template <typename OT = _Float16>
 __device__ __forceinline__ void column_done(const Segment& sg, u64* word, u64 total, unsigned target,
                                             size_t at, int c) {
   const u64 flags = total & kFlagMask;
@@ -504,7 +529,7 @@ __device__ __forceinline__ void column_done(const Segment& sg, u64* word, u64 to
   else if (flags & kPosInfFlag) v = __builtin_inff();
   else if (flags & kNegInfFlag) v = -__builtin_inff();
   v += sg.bias ? sg.bias[c] : 0.f;
-  reinterpret_cast<_Float16*>(sg.out16)[at] = (_Float16)v;
+  reinterpret_cast<OT*>(sg.out16)[at] = (OT)v;
   atomicExch(word, 0ull);  // result unused: a plain atomic store
 }
 
@@ -514,12 +539,15 @@ __device__ __forceinline__ void column_done(const Segment& sg, u64* word, u64 to
 // makes the compiler treat vmcnt as out of order -- every later wait for a load turns into
 // vmcnt(0), including the codebook staging wait of the dense role (+0.3-0.6 us per launch).
 #define SQLLM_GLOBAL(T, p) reinterpret_cast<__attribute__((address_space(1))) T*>(reinterpret_cast<uintptr_t>(p))
+// (OT: the fused linear's 16-bit type, see FixRange; it means nothing to the fp32 form)
+template <typename OT = _Float16>
 __device__ __forceinline__ void acc_add(float* p, float v) {
   __hip_atomic_fetch_add(SQLLM_GLOBAL(float, p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+template <typename OT = _Float16>
 __device__ __forceinline__ void acc_add(u64* p, float v) {
-  flag_nonfinite(p, v);
-  __hip_atomic_fetch_add(SQLLM_GLOBAL(u64, p), to_fixed(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  flag_nonfinite<OT>(p, v);
+  __hip_atomic_fetch_add(SQLLM_GLOBAL(u64, p), to_fixed<OT>(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // vec element load.  COH (dependency-gated pass, sqllm_pass.hip): the element may have been produced by ANOTHER

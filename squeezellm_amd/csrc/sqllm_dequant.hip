@@ -1,6 +1,6 @@
 // sqllm_dequant.hip -- the packed-to-dense direction (include/sqllm_hip.h: sqllm_dequant): ONE kernel writes
 //     W[n, k] = lookup_table[n, idx(k, n)] + sum CSR(n, k) + sum_c [full_row_indices[c] == n] full_rows[k, c]
-// as an [N, ld] matrix with k contiguous (nn.Linear.weight), fp32 or fp16, every element rounded once from its fp32 sum.
+// as an [N, ld] matrix with k contiguous (nn.Linear.weight), fp32, fp16 or bf16, every element rounded once from its fp32 sum.
 //
 // The packed words are contiguous along N, the output along K: the kernel is a decode plus a transpose.  What is transposed
 // is the PACKED tile (4 bytes per 8 or 10.7 weights), not the decoded one: both formats are a plain little-endian bit
@@ -21,11 +21,16 @@
 //      one value = the bits of one fp32 add; duplicates accumulate), and the lanes read the row back.  Which channels of the
 //      tile have a top-X column at all is marked once per workgroup in step 1.  No workgroup barrier after step 1;
 //   4. every store is 16 bytes per lane and a wave's store instruction covers 1024 contiguous bytes of one output row
-//      (fp16: lane = 8 k's; fp32: lane = 4 k's, twice, 256 k's apart).
+//      (fp16 / bf16: lane = 8 k's; fp32: lane = 4 k's, twice, 256 k's apart).
+// The body is ONE device template over the output type; sqllm_dequant_kernel<BITS, F16> (fp32 / fp16) and
+// sqllm_dequant_bf16_kernel<BITS> are its kernels -- the 16-bit paths differ in the final conversion and the type of the
+// 16-byte store alone.
 // Per weight: BITS / 8 bytes read, 2 or 4 written, one LDS lookup; designed to be bound by the HBM writes (what a
 // measurement says about that: DESIGN.md 4.5).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "sqllm_hip.h"
 #include "sqllm_host.h"
@@ -64,8 +69,10 @@ __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int BITS, bool F16>
-__global__ void __launch_bounds__(kDqThreads) sqllm_dequant_kernel(const DequantArgs a) {
+// OT: the output element -- float, _Float16 or __bf16 (F16 below: a 16-bit output, eight k's per lane and store)
+template <int BITS, typename OT>
+__device__ __forceinline__ void dequant_tile(const DequantArgs& a) {
+  constexpr bool F16 = sizeof(OT) == 2;
   constexpr int E = 1 << BITS;
   constexpr int kRows = kDqChunkK * BITS / 32;  // word rows of a whole chunk
   __shared__ uint32_t wt[(kRows + 1) * kDqStride];  // (+ 1: the upper word of the last row's 64-bit window is read, never used)
@@ -195,11 +202,11 @@ __global__ void __launch_bounds__(kDqThreads) sqllm_dequant_kernel(const Dequant
     const int64_t o = (int64_t)n * a.ld + k0;
     if (F16) {
       if (8 * lane < kc) {
-        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+        typedef OT h8 __attribute__((ext_vector_type(8)));
         h8 h;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) h[j] = (_Float16)acc[j];
-        *reinterpret_cast<h8*>(static_cast<_Float16*>(a.out) + o + 8 * lane) = h;
+        for (int j = 0; j < 8; ++j) h[j] = (OT)acc[j];  // (one rounding, to nearest-even, of the fp32 sum)
+        *reinterpret_cast<h8*>(static_cast<OT*>(a.out) + o + 8 * lane) = h;
       }
     } else {
 #pragma unroll
@@ -213,6 +220,16 @@ __global__ void __launch_bounds__(kDqThreads) sqllm_dequant_kernel(const Dequant
   }
 }
 
+template <int BITS, bool F16>
+__global__ void __launch_bounds__(kDqThreads) sqllm_dequant_kernel(const DequantArgs a) {
+  dequant_tile<BITS, typename std::conditional<F16, _Float16, float>::type>(a);
+}
+
+template <int BITS>
+__global__ void __launch_bounds__(kDqThreads) sqllm_dequant_bf16_kernel(const DequantArgs a) {
+  dequant_tile<BITS, __bf16>(a);
+}
+
 }  // namespace sqllm
 
 using namespace sqllm;
@@ -222,8 +239,8 @@ extern "C" int sqllm_dequant(const sqllm_dequant_desc* d, sqllm_stream_t stream)
   const sqllm_op* op = &d->op;
   if (op->bits != 3 && op->bits != 4) return SQLLM_E_BITS;
   if (op->K <= 0 || op->N <= 0 || (op->K % 32) != 0 || (op->N % 4) != 0) return SQLLM_E_SHAPE;
-  if (d->out_dtype != SQLLM_DTYPE_F32 && d->out_dtype != SQLLM_DTYPE_F16) return SQLLM_E_SHAPE;
-  if (d->ld < op->K || (d->ld % (d->out_dtype == SQLLM_DTYPE_F16 ? 8 : 4)) != 0) return SQLLM_E_SHAPE;
+  if (d->out_dtype != SQLLM_DTYPE_F32 && d->out_dtype != SQLLM_DTYPE_F16 && d->out_dtype != SQLLM_DTYPE_BF16) return SQLLM_E_SHAPE;
+  if (d->ld < op->K || (d->ld % (d->out_dtype == SQLLM_DTYPE_F32 ? 4 : 8)) != 0) return SQLLM_E_SHAPE;
   if (!d->out || !op->qweight || !op->lookup_table) return SQLLM_E_NULL;
   if ((reinterpret_cast<uintptr_t>(op->qweight) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d->out) & 15u) != 0) return SQLLM_E_ALIGN;
   int rc = sqllm_host::validate_sparse(op);
@@ -252,7 +269,10 @@ extern "C" int sqllm_dequant(const sqllm_dequant_desc* d, sqllm_stream_t stream)
   if (grid.y > 65535u) return SQLLM_E_SHAPE;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool f16 = d->out_dtype == SQLLM_DTYPE_F16;
-  if (op->bits == 4) {
+  if (d->out_dtype == SQLLM_DTYPE_BF16) {
+    if (op->bits == 4) hipLaunchKernelGGL((sqllm_dequant_bf16_kernel<4>), grid, dim3(kDqThreads), 0, s, a);
+    else hipLaunchKernelGGL((sqllm_dequant_bf16_kernel<3>), grid, dim3(kDqThreads), 0, s, a);
+  } else if (op->bits == 4) {
     if (f16) hipLaunchKernelGGL((sqllm_dequant_kernel<4, true>), grid, dim3(kDqThreads), 0, s, a);
     else hipLaunchKernelGGL((sqllm_dequant_kernel<4, false>), grid, dim3(kDqThreads), 0, s, a);
   } else {

@@ -64,7 +64,8 @@ namespace sqllm {
 // Dense epilogue (shared by the dense-role variants): fold the 4 lane rows, then the waves through
 // LDS, one atomic per column.  `slabs` = LDS area [WAVES][BT][64] floats followed by the ticket.
 // ------------------------------------------------------------------------------------------------
-template <int BT, int WAVES, int ABL>
+// OT: the 16-bit type of a fused linear's output (sqllm_decode.h: FixRange, column_done); the fp16 default elsewhere
+template <int BT, int WAVES, int ABL, typename OT = _Float16>
 __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float* slabs, const float* topx_sum,
                                                bool fold_topx, float* __restrict__ y, int N, int col0, int b0,
                                                int nb, int lane, int wave, const Segment& sg, const Segment* lin,
@@ -137,8 +138,8 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
         const size_t at = (size_t)(b0 + b) * N + c;
         if (fold_topx) sum += topx_sum[b * kTileN + lane];
         if (lin) {
-          const u64 mine = kCountUnit + to_fixed(sum);
-          flag_nonfinite(reinterpret_cast<u64*>(y) + at, sum);
+          const u64 mine = kCountUnit + to_fixed<OT>(sum);
+          flag_nonfinite<OT>(reinterpret_cast<u64*>(y) + at, sum);
           total[b] = atomicAdd(reinterpret_cast<u64*>(y) + at, mine) + mine;
         } else {
           atomicAdd(y + at, sum);
@@ -150,7 +151,7 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
 #pragma unroll
       for (int b = 0; b < BT; ++b) {
         const size_t at = (size_t)(b0 + b) * N + c;
-        if (b < nb) column_done(*lin, reinterpret_cast<u64*>(y) + at, total[b], target, at, c);
+        if (b < nb) column_done<OT>(*lin, reinterpret_cast<u64*>(y) + at, total[b], target, at, c);
       }
     }
   }
@@ -182,7 +183,7 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
                                            int n_col_tiles, int units_total, int units_per_wg, float* lds,
                                            const Segment& sg, const Segment* lin) {
   using F = Fmt<BITS>;
-  constexpr uint32_t XB = sizeof(XT);  // bytes per element of vec (4: operator ABI, 2: fused linear)
+  constexpr uint32_t XB = sizeof(XT);  // bytes per element of vec (4: operator ABI, 2: fused linear, fp16 or bf16)
   // Clean slate for the compiler's wait-count model: the other roles sit upstream of this one in
   // the kernel's (static) control-flow graph, and whatever memory operation they leave "pending"
   // there (a FLAT access, a load into a register this role reuses) would otherwise be waited for
@@ -453,7 +454,7 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
     acc[0][0] = f32x2{accp[0].x + accp[0].y, accp[1].x + accp[1].y};
     acc[1][0] = f32x2{accp[2].x + accp[2].y, accp[3].x + accp[3].y};
   }
-  dense_epilogue<BT, WAVES, ABL>(acc, lds + kCodebookFloats, topx_sum, fold_topx, y, N, col0, b0, nb, lane, wave, sg, lin, tl);
+  dense_epilogue<BT, WAVES, ABL, typename OutType<XT>::type>(acc, lds + kCodebookFloats, topx_sum, fold_topx, y, N, col0, b0, nb, lane, wave, sg, lin, tl);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -81,11 +81,11 @@ struct Segment {
   const float* vals;
   const float* full_rows;
   const int* full_idx;
-  // fused-linear launches only (sqllm_linear_f16): `y` is then the plane of 64-bit accumulator
+  // fused-linear launches only (sqllm_linear_f16 / _bf16): `y` is then the plane of 64-bit accumulator
   // words [batch, N] in the caller's workspace (all zero between launches) and the finished
-  // columns leave as fp16
+  // columns leave as fp16 / bf16
   const float* bias;    // fp32 [N] or null
-  void* out16;          // fp16 [batch, N]
+  void* out16;          // fp16 or bf16 [batch, N]
   KernelGeom gm;
 };
 
@@ -99,8 +99,9 @@ struct GroupArgs {
 };
 
 struct LaunchArgs {
-  const void* x;        // fp32 (operator launches) or fp16 (fused-linear launches)
+  const void* x;        // fp32 (operator launches) or fp16 / bf16 (fused-linear launches)
   bool linear = false;  // fused-linear launch: fp16 in / fp16 out, bias, self-cleaning workspace
+  bool bf16 = false;    // ... with bf16 at both ends instead (sqllm_linear_bf16.hip: launch_linear_bf16)
   GroupArgs ga;
   hipEvent_t ev_start = nullptr;  // optional: recorded at this kernel's begin / end (profiling aid)
   hipEvent_t ev_stop = nullptr;
@@ -127,6 +128,7 @@ inline int batch_tile_op(int batch) { return (batch == 3 || batch == 5 || batch 
 inline int mfma_row_blocks(int batch) { return batch <= 16 ? 1 : batch <= 32 ? 2 : 4; }
 
 hipError_t launch_fused(int bits, const LaunchArgs& a, hipStream_t stream);
+hipError_t launch_linear_bf16(int bits, const LaunchArgs& a, hipStream_t stream);  // the fused linear, bf16 in / bf16 out (a.linear && a.bf16): launch_fused hands such launches on
 extern bool (*g_fused_variant)(int bits, const LaunchArgs& a, hipStream_t stream, hipError_t* err);  // measurement library hook (null in the product)
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)

@@ -1000,6 +1000,7 @@ hipError_t launch_fused(int bits, const LaunchArgs& a, hipStream_t stream) {
     hipError_t err = hipSuccess;
     if (g_fused_variant(bits, a, stream, &err)) return err;
   }
+  if (a.linear && a.bf16) return launch_linear_bf16(bits, a, stream);  // bf16 at both ends: the kernel of sqllm_linear_bf16.hip, same plan
   if (a.linear) return bits == 4 ? launch_bt<4, true>(a, stream) : launch_bt<3, true>(a, stream);
   return bits == 4 ? launch_bt<4, false>(a, stream) : launch_bt<3, false>(a, stream);
 }

@@ -77,6 +77,7 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
                                          const float* __restrict__ xT = nullptr, int Bp = 0,
                                          unsigned long long* tl = nullptr, GATE gate = GATE()) {
   constexpr bool LIN = sizeof(AT) == 8;
+  using OT = typename OutType<XT>::type;  // fused linear: the 16-bit type of its two ends (range rule and output store)
   int tid_ = threadIdx.x;
   // (inside the persistent pass kernel the role runs in a loop over work items: what it derives from the thread id
   // is recomputed per item -- hoisted out of that loop it would be live across every other role of the kernel)
@@ -424,18 +425,18 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
           if (flush_head) {
             const float h = head + (cont_prev ? carry : 0.f);
             if (in_lds) atomicAdd(sacc + bb * n + rf, h);
-            else acc_add(y + (size_t)(b0 + bs + bb) * N + c_lo + rf, h);
+            else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + rf, h);
           }
 #pragma unroll
           for (int i = 1; i < EPT - 1; ++i) {
             if (mid[i]) {
               if (in_lds) atomicAdd(sacc + bb * n + lr[i], q[i]);
-              else acc_add(y + (size_t)(b0 + bs + bb) * N + c_lo + lr[i], q[i]);
+              else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + lr[i], q[i]);
             }
           }
           if (flush_tail) {
             if (in_lds) atomicAdd(sacc + bb * n + rl, t);
-            else acc_add(y + (size_t)(b0 + bs + bb) * N + c_lo + rl, t);
+            else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + rl, t);
           }
         }
       }
@@ -453,13 +454,13 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
           // one COUNTED contribution per row this chunk holds a part of, whatever its value
           const int r0 = srows[i], r1 = srows[i + 1];
           if ((r0 > e0 ? r0 : e0) < (r1 < e1 ? r1 : e1)) {
-            const u64 mine = kCountUnit + to_fixed(sum);
-            flag_nonfinite(y + at, sum);
+            const u64 mine = kCountUnit + to_fixed<OT>(sum);
+            flag_nonfinite<OT>(y + at, sum);
             const unsigned target = (unsigned)lin->gm.k_slices + (unsigned)csr_chunks_of_row(r0, r1);
-            column_done(*lin, y + at, atomicAdd(y + at, mine) + mine, target, at, c_lo + i);
+            column_done<OT>(*lin, y + at, atomicAdd(y + at, mine) + mine, target, at, c_lo + i);
           }
         } else {
-          if (sum != 0.f) acc_add(y + at, sum);
+          if (sum != 0.f) acc_add<OT>(y + at, sum);
         }
       }
       SQLLM_CSR_STAMP(5)  // atomics issued
@@ -474,7 +475,7 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
         if ((r0 > e0 ? r0 : e0) < (r1 < e1 ? r1 : e1)) {
           const size_t at = (size_t)(b0 + bs) * N + c_lo + i;
           const unsigned target = (unsigned)lin->gm.k_slices + (unsigned)csr_chunks_of_row(r0, r1);
-          column_done(*lin, y + at, atomicAdd(y + at, kCountUnit) + kCountUnit, target, at, c_lo + i);
+          column_done<OT>(*lin, y + at, atomicAdd(y + at, kCountUnit) + kCountUnit, target, at, c_lo + i);
         }
       }
     }
@@ -672,6 +673,7 @@ __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
                                           const float* __restrict__ full_rows,
                                           const int* __restrict__ full_idx, int topX, int K, int N,
                                           int b0, int nb, int slab, float* lds, GATE gate = GATE()) {
+  using OT = typename OutType<XT>::type;  // (see csr_role)
   int tid_ = threadIdx.x;
   if constexpr (XCOH) asm volatile("" : "+v"(tid_));  // (see csr_role)
   const int tid = tid_;
@@ -733,7 +735,7 @@ __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
           float sum = 0.f;
 #pragma unroll
           for (int w = 0; w < T / 64; ++w) sum += lds[(r * (T / 64) + w) * 16 + cc];
-          acc_add(y + (size_t)(b0 + bp + r) * N + dst, sum);  // (cc == c: this thread's own early-loaded index)
+          acc_add<OT>(y + (size_t)(b0 + bp + r) * N + dst, sum);  // (cc == c: this thread's own early-loaded index)
         }
       }
     }
@@ -753,11 +755,11 @@ __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
       const int kk = e / topX;
       const int c = e - kk * topX;
       const float p = fr[e] * ld_x<XCOH>(xb + kk);
-      if (in_lds) atomicAdd(sacc + c, p); else acc_add(yb + full_idx[c], p);
+      if (in_lds) atomicAdd(sacc + c, p); else acc_add<OT>(yb + full_idx[c], p);
     }
     if (in_lds) {
       __syncthreads();
-      for (int c = tid; c < topX; c += T) acc_add(yb + full_idx[c], sacc[c]);
+      for (int c = tid; c < topX; c += T) acc_add<OT>(yb + full_idx[c], sacc[c]);
       __syncthreads();
     }
   }

@@ -6,8 +6,8 @@ below an eager launch (~3-4 us of host time).  `OpSequence` pre-marshals every o
 C array of `sqllm_op` descriptors (include/sqllm_hip.h) and then
   * `launch()`  enqueues the whole pass through one FFI crossing (sqllm_launch_sequence), or
   * `graph()`   captures that into a HIP graph for replay.
-With `linear=True` the ops are fused linears (sqllm_linear_f16): fp16 activations in, fp16 out,
-bias included, no zero-fill / cast launches around them -- the whole matvec branch of
+With `linear=True` the ops are fused linears (sqllm_linear_f16 / sqllm_linear_bf16): fp16 or bf16 activations in, the
+same type out, bias included, no zero-fill / cast launches around them -- the whole matvec branch of
 QuantLinearLUT.forward (squeezellm/quant.py:211-312) per kernel.
 `dequantize_layer` is the other direction: a layer's operands -> the dense [N, K] matrix they stand for, one kernel.
 All launches go to torch's current stream; nothing here synchronises.
@@ -76,7 +76,9 @@ class OpSequence:
         batch) are enqueued as one kernel (sqllm_launch_group), up to 4 per launch -- q/k/v and
         gate/up of a decoder layer.
         linear: `ys[i] = fp16(layer_i(xs[i]) + bias_i)` with fp16 xs / ys (ys overwritten) instead
-        of the operator semantics `ys[i] += layer_i(xs[i])` on fp32.
+        of the operator semantics `ys[i] += layer_i(xs[i])` on fp32.  bf16 xs / ys work the same way
+        (sqllm_linear_bf16_groups; its range rule: include/sqllm_hip.h) -- ONE dtype for the whole
+        sequence, fp16 or bf16, taken from xs[0]; anything else is a ValueError.
         fold_topx (fused linears only): hand the kernel a CSR that contains the layer's top-X rows
         (`fold_topx_into_csr`, built once per layer) instead of the separate dense rows.
         workspace (batched operator sequences): own ONE workspace buffer for the pass, sized by
@@ -88,7 +90,14 @@ class OpSequence:
         self.linear = bool(linear)
         self._keep = [layers, xs, ys]  # keep the tensors alive as long as the descriptors
         self.device = xs[0].device if self.n else torch.device("cuda")
-        io = torch.float16 if linear else torch.float32
+        io = torch.float32
+        if linear:
+            io = xs[0].dtype if self.n else torch.float16
+            if io not in (torch.float16, torch.bfloat16):
+                raise ValueError(f"linear=True takes fp16 or bf16 xs / ys, got {io}")
+            if any(t.dtype != io for t in list(xs) + list(ys)):
+                raise ValueError(f"linear=True: every x and y of a sequence must have one dtype (xs[0] is {io})")
+        self.io_dtype = io
         if linear:
             self.lins = (_lib.SqllmLinear * self.n)()
             self.ops = [self.lins[i].op for i in range(self.n)]
@@ -155,7 +164,8 @@ class OpSequence:
         """Enqueue the whole pass on the current stream of the sequence's device (one FFI crossing)."""
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if self.linear:
-            rc = self._lib.sqllm_linear_f16_groups(self.lins, self._sizes, self.n_groups, stream, ctypes.byref(self._done))
+            fn = self._lib.sqllm_linear_bf16_groups if self.io_dtype is torch.bfloat16 else self._lib.sqllm_linear_f16_groups
+            rc = fn(self.lins, self._sizes, self.n_groups, stream, ctypes.byref(self._done))
         elif self._ws is not None:
             rc = self._lib.sqllm_launch_groups_ws(self.ops, self._sizes, self.n_groups, self._ws.data_ptr(), self._ws.numel(), stream,
                                                   ctypes.byref(self._done))
@@ -197,21 +207,21 @@ class OpSequence:
         return g
 
 
-_DENSE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16}
+_DENSE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 
 def dequantize_layer(layer: dict, dtype=torch.float16, out=None) -> torch.Tensor:
     """The dense matrix W [N, K] (K contiguous: the layout of nn.Linear.weight) that a layer's operands stand for --
-    codebook entry + CSR outliers + top-X columns, summed in fp32 and rounded once to `dtype` (torch.float16 or
-    torch.float32) -- written by ONE kernel (sqllm_dequant, include/sqllm_hip.h) on torch's current stream.
+    codebook entry + CSR outliers + top-X columns, summed in fp32 and rounded once to `dtype` (torch.float16,
+    torch.bfloat16 or torch.float32) -- written by ONE kernel (sqllm_dequant, include/sqllm_hip.h) on torch's current stream.
 
     `layer`: an operand dict as made by synth.make_layer, pack.pack_layer or checkpoint.layer_operands (bits, K, N,
     qweight, lookup_table and, optionally, rows / cols / vals and full_rows / full_row_indices), on the GPU.
     `out`: a 2-D [N, >= K] tensor of `dtype` to write into (row stride = out.stride(0): a multiple of 8 elements for
-    fp16, of 4 for fp32; unit stride along K; columns beyond K are left alone); the [N, K] view of it is returned.
+    fp16 and bf16, of 4 for fp32; unit stride along K; columns beyond K are left alone); the [N, K] view of it is returned.
     Without `out` a new [N, K] tensor is allocated (a stream-ordered torch allocation: capture-safe)."""
     if dtype not in _DENSE_DTYPES:
-        raise TypeError(f"dtype must be torch.float16 or torch.float32, got {dtype}")
+        raise TypeError(f"dtype must be torch.float16, torch.bfloat16 or torch.float32, got {dtype}")
     code = _DENSE_DTYPES[dtype]
     K, N = layer["K"], layer["N"]
     qweight, lut = layer["qweight"], layer["lookup_table"]

@@ -155,20 +155,25 @@ class QuantLinearLUT(nn.Module):
 
 
 _is_capturing = torch.cuda.is_current_stream_capturing
+# activation dtypes of the fused forward -> the entry point that takes them (one sqllm_linear descriptor serves both)
+_FUSED_ENTRY = {torch.float16: "sqllm_linear_f16", torch.bfloat16: "sqllm_linear_bf16"}
 
 
 class QuantLinearLUTFused(QuantLinearLUT):
-    """Opt-in forward for fp16 activations: ONE kernel per call (sqllm_linear_f16) instead of the
+    """Opt-in forward for fp16 and bf16 activations: ONE kernel per call (sqllm_linear_f16 / sqllm_linear_bf16) instead of the
     reference's four (`zeros`/`bias.clone()`, `x.float()`, the op, `y.to(fp16)`; quant.py:214-223,
     :311-312 and :314-321, :380-383).  Same buffers and state dict as QuantLinearLUT -- switch an
     existing model over with `fuse_quant_lut(model)`.  Result = fp16(fp32 accumulation + bias);
     the reference's batched branch rounds to fp16 before adding the bias (and then promotes to
-    fp32), so the two differ by at most one fp16 rounding of the output.  Other dtypes take the
-    parent's path.
+    fp32), so the two differ by at most one fp16 rounding of the output.  bf16 input gives
+    bf16(fp32 accumulation + bias) the same way, from the same module, workspace and descriptor cache -- fp16 and bf16
+    calls may alternate -- with ONE difference: a partial sum (one K slice of one output) beyond +-131072 in magnitude
+    makes that output +-inf instead of a finite number (include/sqllm_hip.h, sqllm_linear_bf16, with the one corner
+    where this is not guaranteed; the fp32 path returns the finite value there).  Other dtypes take the parent's path.
 
     Prompt-width inputs: the fused kernel decodes the packed weights once per 8 rows.  With `dense_min_rows` set, a call
-    of at least that many rows instead writes the layer's dense fp16 matrix once (`dequantize`: one kernel) and
-    multiplies with torch's fp16 GEMM.  That matrix is a temporary of the call -- a torch allocation on the current
+    of at least that many rows instead writes the layer's dense matrix in the activations' 16-bit type once (`dequantize`:
+    one kernel) and multiplies with torch's GEMM of that type (the bias is added in fp32, one rounding).  That matrix is a temporary of the call -- a torch allocation on the current
     stream, capture-safe, never cached on the module -- so the peak extra memory is ONE layer's matrix
     (2 * infeatures * outfeatures bytes: 142 MB for a 13B gate/up layer).  Recommended value: 128 -- on the 13B shapes
     the dense route measured 2.8 - 6.4x faster at 128 rows and 17 - 34x at 2048 (the figures per shape stand beside the
@@ -187,14 +192,14 @@ class QuantLinearLUTFused(QuantLinearLUT):
 
     @property
     def last_route(self):
-        """"fused" or "dense": the way the most recent fp16 GPU forward of this module went (None before the first)."""
+        """"fused" or "dense": the way the most recent fp16 / bf16 GPU forward of this module went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def _forward_dense(self, x: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
-        w = self.dequantize(torch.float16)  # a temporary of this call
+        w = self.dequantize(x2.dtype)  # a temporary of this call (fp16 or bf16, as the activations)
         y = torch.nn.functional.linear(x2, w)
         if self.bias is not None:
-            y = (y.float() + self.bias).half()
+            y = (y.float() + self.bias).to(x2.dtype)
         return y.reshape(*x.shape[:-1], self.outfeatures)
 
     GRAPH_WS_MAX_BYTES = 4 << 20  # eager calls keep a second, graph-only workspace ready up to this size (decode batches)
@@ -318,7 +323,7 @@ class QuantLinearLUTFused(QuantLinearLUT):
         return entry[1]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if x.dtype is not torch.float16 or not x.is_cuda:
+        if x.dtype not in _FUSED_ENTRY or not x.is_cuda:
             return super().forward(x)
         K, N = self.infeatures, self.outfeatures
         if x.shape[-1] != K:
@@ -332,19 +337,19 @@ class QuantLinearLUTFused(QuantLinearLUT):
             return self._forward_dense(x, x2)
         self.__dict__["_last_route"] = "fused"
         dev = x.get_device()
-        out = torch.empty((rows, N), dtype=torch.float16, device=x.device)
+        out = torch.empty((rows, N), dtype=x.dtype, device=x.device)
         lin, ref, _keep = self._descriptor(dev, quant_cuda._raw_stream(dev))
         batch = 0 if rows == 1 else rows
         ws = self._workspace(batch, self.qweight.device)  # (one buffer per device and stream, grown to the largest batch seen)
         o = lin.op
         o.batch, o.vec, o.mul = batch, x2.data_ptr(), out.data_ptr()
         lin.workspace = ws.data_ptr()
-        quant_cuda._launch(quant_cuda._fn("sqllm_linear_f16"), dev, (ref,))
+        quant_cuda._launch(quant_cuda._fn(_FUSED_ENTRY[x.dtype]), dev, (ref,))
         return out.reshape(*x.shape[:-1], N)
 
 
 def fuse_quant_lut(module: nn.Module) -> int:
-    """Switch every QuantLinearLUT under `module` to the fused fp16 forward (in place, buffers and
+    """Switch every QuantLinearLUT under `module` to the fused fp16 / bf16 forward (in place, buffers and
     state dict untouched).  Returns the number of layers switched."""
     n = 0
     for m in module.modules():

@@ -3,6 +3,9 @@
     python tools/isa_compare.py dump OUTDIR          # compile this tree's kernel sources to OUTDIR/*.s
     python tools/isa_compare.py compare DIR_A DIR_B  # per kernel: metadata equal? instruction stream identical?
 
+`compare` counts as a difference: a kernel whose metadata or instruction stream differs, a kernel symbol on one side only, a
+source file present in A only.  A source file present in B only (a source B added) is listed as "new in B" with its kernel
+count and NOT counted; `dump` skips product sources the tree does not have (an older tree).
 `dump` uses the command of tests/test_codegen_cpu.py (build.FLAGS without -fPIC, -S --cuda-device-only), once plain
 for the product sources and once with -DSQLLM_ABLATION_BUILD for the kernel sources of the measurement library.
 To dump a commit that does not have this script yet, copy the script into that tree's tools/ first (it reads the
@@ -17,7 +20,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from squeezellm_amd import build as B  # noqa: E402
 
-PRODUCT = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip"]
+PRODUCT = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "sqllm_dequant.hip", "sqllm_linear_bf16.hip"]
 META = (".vgpr_count", ".sgpr_count", ".agpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size",
         ".vgpr_spill_count", ".sgpr_spill_count")
 CLASSES = ("v_mfma", "ds_read", "global_load", "buffer_load", "s_load", "s_barrier", "s_waitcnt")
@@ -30,6 +33,8 @@ def dump(outdir):
     jobs += [(s, "ablation", ["-DSQLLM_ABLATION_BUILD"]) for s in PRODUCT + [e for e in B.EXPERIMENT_SOURCES if "sqllm_experimental" not in e]]
     procs = []
     for src, tag, extra in jobs:
+        if not os.path.exists(os.path.join(B.CSRC, src)):  # (an older tree: the source came later)
+            continue
         out = os.path.join(outdir, f"{tag}__{os.path.basename(src)}.s")
         cmd = [B.hipcc(), f"--offload-arch={B.ARCH}", *[f for f in B.FLAGS if f != "-fPIC"], *extra, "-S",
                "--cuda-device-only", f"-I{B.INCLUDE}", f"-I{B.CSRC}", f"-I{B.EXPERIMENTAL}", os.path.join(B.CSRC, src), "-o", out]
@@ -81,8 +86,11 @@ def compare(a, b):
         if not f.endswith(".s"):
             continue
         pa, pb = os.path.join(a, f), os.path.join(b, f)
-        if not (os.path.exists(pa) and os.path.exists(pb)):
-            lines.append(f"{f}: present on one side only")
+        if os.path.exists(pb) and not os.path.exists(pa):  # a source B added: nothing to compare it with
+            lines.append(f"{f}: new in B, {len(parse(pb))} kernels (not compared)")
+            continue
+        if not os.path.exists(pb):
+            lines.append(f"{f}: present in A only")
             diff += 1
             continue
         ka, kb = parse(pa), parse(pb)
