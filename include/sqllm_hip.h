@@ -215,6 +215,54 @@ int sqllm_linear_bf16_groups(const sqllm_linear* lins, const int32_t* group_size
                              sqllm_stream_t stream, int32_t* n_done);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gated fused linear: the front half of a LLaMA MLP -- gate_proj, up_proj, SiLU and the product -- in one kernel.
+ *
+ * For two packed layers `gate` and `up` with the same K, N, bits and batch, over the same 16-bit activations x:
+ *
+ *     g = bias_gate[n] + sum_k Wg[n,k] * float(x[b,k])      (all three weight terms, fp32 as in sqllm_linear_*)
+ *     u = bias_up[n]   + sum_k Wu[n,k] * float(x[b,k])
+ *     out[b,n] = OT( (g / (1 + exp(-g))) * u )              evaluated in fp32, rounded ONCE to OT (fp16 or bf16, = type of x)
+ *
+ *   - Accumulation inside and between contributions is exactly sqllm_linear_f16 / _bf16's: fixed-point words, counted
+ *     returning atomics, sticky flags, the same order of additions.  The 63-contribution limit applies per member.
+ *   - Non-finite g or u follow the fp32 formula above, which is what torch.nn.functional.silu(g) * u gives in fp32:
+ *     silu(+inf) = +inf, silu(-inf) = NaN, silu(NaN) = NaN, silu of a large negative finite value is -0.
+ *   - The range rule is the bf16 rule for BOTH output types.  The fp16 linear clamps a contribution beyond +-131072
+ *     because such an fp16 result is not finite anyway.  Here that argument fails: g = 200000, u = 0.05 has a finite fp16
+ *     product, and a clamp would return a wrong finite number.  Both gated kernels therefore use the no-clamp form of
+ *     sqllm_linear_bf16: a finite contribution with |v| > 131072 sets the infinity flag of its sign and adds nothing.  The
+ *     corner carved out above stays as it is, 256 rows earlier: a CSR chunk spanning more than 1792 rows adds its values uncounted, a flag
+ *     can be lost there, and the result can be finite and wrong.
+ *   - The result is a function of the operands alone: integer sums commute, and the final step is computed from the same
+ *     two fp32 values whichever member finishes first.  Run to run it is bit-identical.  (Inside a contribution the order
+ *     of additions is fixed as well: where the linears let a CSR chunk's waves add their parts of a long row in arrival
+ *     order, these kernels add them in wave order.  ONE exception: top-X rows passed as full_rows -- not folded into the
+ *     CSR, as the Python module folds them -- are summed per K slice by eight waves in arrival order, as in the linears;
+ *     such a column's last fp32 bit, and with it an output on a rounding boundary of OT, can differ between runs.)
+ *
+ * The two members may differ in their sparse terms (a dense-only gate with an up that has CSR and top-X rows).
+ * `workspace`: sqllm_gated_workspace_bytes(&gate) bytes, 16-byte aligned -- the two members' accumulator planes and a plane
+ * of 64-bit pair words [batch, N] in which the two finished values of an output meet -- zero-filled ONCE by the caller and
+ * left zero-filled by every launch; it serves one launch at a time.  Like every entry point: one kernel, nothing
+ * allocated, nothing retained, no synchronisation, capturable as one kernel node.  Rejected before the device is touched:
+ * act other than SQLLM_ACT_SILU (SQLLM_E_OPTION); a non-NULL mul in either member, members that differ in vec / K / N /
+ * bits / batch (SQLLM_E_GROUP); a NULL descriptor, out or workspace (SQLLM_E_NULL); a workspace that is not 16-byte aligned
+ * (SQLLM_E_ALIGN); and everything sqllm_linear_* rejects, with its codes.
+ * ------------------------------------------------------------------------------------------- */
+#define SQLLM_ACT_SILU 0
+typedef struct sqllm_gated {
+  sqllm_op gate, up;      /* as for sqllm_linear_*: vec = 16-bit [batch, K], shared; mul must be NULL */
+  const float* bias_gate; /* fp32 [N] or NULL */
+  const float* bias_up;
+  void* out;              /* fp16 / bf16 [batch, N], OVERWRITTEN */
+  void* workspace;        /* sqllm_gated_workspace_bytes(), zero-filled ONCE, left zero-filled */
+  int32_t act;            /* SQLLM_ACT_SILU; anything else: SQLLM_E_OPTION */
+} sqllm_gated;
+int64_t sqllm_gated_workspace_bytes(const sqllm_op* gate); /* two accumulator planes + the pair plane */
+int sqllm_gated_f16(const sqllm_gated* g, sqllm_stream_t stream);
+int sqllm_gated_bf16(const sqllm_gated* g, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

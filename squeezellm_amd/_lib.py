@@ -42,6 +42,16 @@ class SqllmLinear(ctypes.Structure):
     _fields_ = [("op", SqllmOp), ("bias", c_void_p), ("workspace", c_void_p)]
 
 
+class SqllmGated(ctypes.Structure):
+    """struct sqllm_gated (include/sqllm_hip.h): gate and up share op.vec (fp16 / bf16); their op.mul stay NULL."""
+
+    _fields_ = [("gate", SqllmOp), ("up", SqllmOp), ("bias_gate", c_void_p), ("bias_up", c_void_p), ("out", c_void_p),
+                ("workspace", c_void_p), ("act", c_int32)]
+
+
+ACT_SILU = 0  # SQLLM_ACT_SILU
+
+
 class SqllmPlan(ctypes.Structure):
     """struct sqllm_plan (include/sqllm_hip.h)."""
 
@@ -118,6 +128,9 @@ SIGNATURES = {
     "sqllm_linear_f16_groups": [POINTER(SqllmLinear), POINTER(c_int32), c_int32, P, POINTER(c_int32)],
     "sqllm_linear_bf16": [POINTER(SqllmLinear), P],
     "sqllm_linear_bf16_groups": [POINTER(SqllmLinear), POINTER(c_int32), c_int32, P, POINTER(c_int32)],
+    "sqllm_gated_workspace_bytes": [POINTER(SqllmOp)],
+    "sqllm_gated_f16": [POINTER(SqllmGated), P],
+    "sqllm_gated_bf16": [POINTER(SqllmGated), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],
@@ -166,7 +179,7 @@ def load() -> ctypes.CDLL:
         fn.argtypes = argtypes
         fn.restype = (c_char_p if name == "sqllm_error_string" else
                       ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes",
-                                               "sqllm_select_workspace_bytes") else c_int)
+                                               "sqllm_select_workspace_bytes", "sqllm_gated_workspace_bytes") else c_int)
     if lib.sqllm_abi_version() != 1:
         raise RuntimeError(f"libsqllm_hip.so ABI {lib.sqllm_abi_version()} != 1 expected by this package")
     _lib = lib
@@ -208,6 +221,12 @@ def linear_workspace_bytes(N: int, batch: int = 0) -> int:
     """Bytes of zero-filled device memory one fused linear of this shape needs (no GPU needed)."""
     op = SqllmOp(N=N, batch=batch)
     return int(load().sqllm_linear_workspace_bytes(ctypes.byref(op)))
+
+
+def gated_workspace_bytes(N: int, batch: int = 0) -> int:
+    """Bytes of zero-filled device memory one gated pair of this shape needs (no GPU needed)."""
+    op = SqllmOp(N=N, batch=batch)
+    return int(load().sqllm_gated_workspace_bytes(ctypes.byref(op)))
 
 
 def workspace_bytes(bits: int, K: int, N: int, batch: int, nnz: int = 0, topX: int = 0, n_ops: int = 1) -> int:

@@ -15,6 +15,10 @@
 #include "sqllm_host.h"
 #include "sqllm_kernels.h"
 
+namespace sqllm {
+hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated.hip
+}
+
 namespace sqllm_host {
 
 ExperimentalHooks g_experimental;
@@ -993,9 +997,10 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
 // `ws_entry`: the call came through a `_ws` entry point -- up to 16 rows nothing is allocated then, workspace or not.
 // `bf16` (fused linears only): vec and mul are bf16 -- same route, plan and workspace; the flag travels in LaunchArgs and
 // launch_fused hands such a launch to launch_linear_bf16 (sqllm_linear_bf16.hip), so the host layer calls the launchers it always did.
+// `pair` (sqllm_gated_*: two fused linears, gate and up): the plane of pair words; the launch then goes to the gated kernel.
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, const sqllm_linear* lin = nullptr, void* ws = nullptr, int64_t ws_bytes = 0,
-                                    bool ws_entry = false, bool bf16 = false) {
+                                    bool ws_entry = false, bool bf16 = false, void* pair = nullptr) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
   sqllm_op tmp[sqllm::kMaxSegments];
@@ -1048,6 +1053,11 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
     switch (route) {
       case kFusedTiles:
       case kFusedLinear:
+        if (pair) {  // (sqllm_linear_gated.hip; without that file in the link there is no such kernel.  Not decorated: the measurement
+                     // library's ablation bits, LDS pad and timeline buffer belong to the kernels it instantiates itself)
+          e = sqllm::g_launch_linear_gated ? sqllm::g_launch_linear_gated(op->bits, a, pair, s) : hipErrorNotSupported;
+          break;
+        }
         if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: ablation bits, LDS pad, timeline buffer)
         e = sqllm::launch_fused(op->bits, a, s);  // (a.bf16, set above for the bf16 entry points: the launcher of sqllm_linear_bf16.hip)
         break;
@@ -1122,6 +1132,37 @@ int sqllm_linear_bf16_groups(const sqllm_linear* lins, const int32_t* group_size
                              sqllm_stream_t stream, int32_t* n_done) {
   return launch_groups(nullptr, lins, group_sizes, n_groups, stream, n_done, nullptr, 0, false, true);
 }
+
+// workspace of a gated pair: the two members' accumulator planes, then the plane of pair words [batch, N]
+int64_t sqllm_gated_workspace_bytes(const sqllm_op* gate) {
+  if (!gate || gate->N <= 0) return 0;
+  return 2 * sqllm_linear_workspace_bytes(gate) + align16(8ll * (gate->batch <= 0 ? 1 : gate->batch) * gate->N);
+}
+
+// gate and up as the two-op group of the fused linear (same route, plan and validation), finished by the gated kernel
+static int launch_gated(const sqllm_gated* g, sqllm_stream_t stream, bool bf16) {
+  if (!g) return SQLLM_E_NULL;
+  if (g->act != SQLLM_ACT_SILU) return SQLLM_E_OPTION;
+  const sqllm_op &a = g->gate, &b = g->up;
+  if (a.mul || b.mul) return SQLLM_E_GROUP;
+  if (a.vec != b.vec || a.K != b.K || a.N != b.N || a.bits != b.bits || a.batch != b.batch)
+    return SQLLM_E_GROUP;
+  if (!g->out || !g->workspace) return SQLLM_E_NULL;
+  if ((reinterpret_cast<uintptr_t>(g->workspace) & 15u) != 0) return SQLLM_E_ALIGN;
+  const int64_t plane = sqllm_linear_workspace_bytes(&a);
+  sqllm_linear lin[2];
+  lin[0].op = a;
+  lin[1].op = b;
+  lin[0].op.mul = lin[1].op.mul = static_cast<float*>(g->out);  // (what the linear's validation and fill_args read as the output)
+  lin[0].bias = g->bias_gate;
+  lin[1].bias = g->bias_up;
+  lin[0].workspace = g->workspace;
+  lin[1].workspace = static_cast<char*>(g->workspace) + plane;
+  return launch_group_with_events(nullptr, 2, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, static_cast<char*>(g->workspace) + 2 * plane);
+}
+
+int sqllm_gated_f16(const sqllm_gated* g, sqllm_stream_t stream) { return launch_gated(g, stream, false); }
+int sqllm_gated_bf16(const sqllm_gated* g, sqllm_stream_t stream) { return launch_gated(g, stream, true); }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

@@ -532,6 +532,36 @@ __device__ __forceinline__ void column_done(const Segment& sg, u64* word, u64 to
   reinterpret_cast<OT*>(sg.out16)[at] = (OT)v;
   atomicExch(word, 0ull);  // result unused: a plain atomic store
 }
+// The first half of column_done on its own, for a finishing step that does something else with the value (sqllm_linear_gated.hip):
+// false if that add was not the last; otherwise *out = the column's fp32 sum, flags applied, bias added.  (column_done keeps its
+// own copy of these lines: written as a call of this function, the bf16 linear's kernels came out with other register numbers.)
+__device__ __forceinline__ bool column_value(const Segment& sg, u64 total, unsigned target, int c, float* out) {
+  const u64 flags = total & kFlagMask;
+  total &= ~kFlagMask;
+  const u64 count = (total + (kCountUnit >> 1)) >> kCountShift;  // S may be negative: round, do not truncate
+  if ((unsigned)count != target) return false;
+  const long long sfix = (long long)(total - (count << kCountShift));
+  float v = (float)sfix * (1.f / (float)(1 << kFixShift));
+  if ((flags & kNanFlag) || (flags & (kPosInfFlag | kNegInfFlag)) == (kPosInfFlag | kNegInfFlag)) v = __builtin_nanf("");
+  else if (flags & kPosInfFlag) v = __builtin_inff();
+  else if (flags & kNegInfFlag) v = -__builtin_inff();
+  v += sg.bias ? sg.bias[c] : 0.f;
+  *out = v;
+  return true;
+}
+
+// The finishing step as a compile-time POLICY of dense_epilogue / dense_role (sqllm_fused.h) and csr_role / topx_role
+// (sqllm_roles.h): what a contributor does with the word after its own counted add, and which 16-bit type's range rule
+// (FixRange) the contributions follow.  The default is the fused linear's: column_done, the range rule of the
+// activations' type.  (sqllm_linear_gated.hip brings the other one: the finished value meets the other member's in a pair word.)
+struct ColumnStore {
+  static constexpr bool kOrderedCsr = false;  // (csr_role: the LDS adds of a row that several waves hold parts of, in any order)
+  template <typename XT> struct Range { using type = typename OutType<XT>::type; };
+  template <typename OT>
+  __device__ __forceinline__ void done(const Segment& sg, u64* word, u64 total, unsigned target, size_t at, int c) const {
+    column_done<OT>(sg, word, total, target, at, c);
+  }
+};
 
 // accumulate one UNCOUNTED value: fp32 atomic (operator launches) or fixed-point add (fused linear).
 // The pointer is cast to the global address space on purpose: through a generic pointer these

@@ -65,11 +65,13 @@ namespace sqllm {
 // LDS, one atomic per column.  `slabs` = LDS area [WAVES][BT][64] floats followed by the ticket.
 // ------------------------------------------------------------------------------------------------
 // OT: the 16-bit type of a fused linear's output (sqllm_decode.h: FixRange, column_done); the fp16 default elsewhere
-template <int BT, int WAVES, int ABL, typename OT = _Float16>
+// FIN: the finishing step of a fused linear's column (sqllm_decode.h: ColumnStore, the default -- column_done)
+template <int BT, int WAVES, int ABL, typename OT = _Float16, typename FIN = ColumnStore>
 __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float* slabs, const float* topx_sum,
                                                bool fold_topx, float* __restrict__ y, int N, int col0, int b0,
                                                int nb, int lane, int wave, const Segment& sg, const Segment* lin,
-                                               unsigned long long* tl /* timeline stamps: sqllm_probe.h (null in the product) */) {
+                                               unsigned long long* tl /* timeline stamps: sqllm_probe.h (null in the product) */,
+                                               FIN fin = FIN()) {
   const int i16 = lane & 15, grp = lane >> 4;
   if constexpr (ABL & 8) {
     if (acc[0][0].x + acc[0][0].y + acc[1][0].x + acc[1][0].y == 12345.678f) y[0] = 1.f;  // keep the work alive
@@ -151,7 +153,7 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
 #pragma unroll
       for (int b = 0; b < BT; ++b) {
         const size_t at = (size_t)(b0 + b) * N + c;
-        if (b < nb) column_done<OT>(*lin, reinterpret_cast<u64*>(y) + at, total[b], target, at, c);
+        if (b < nb) fin.template done<OT>(*lin, reinterpret_cast<u64*>(y) + at, total[b], target, at, c);
       }
     }
   }
@@ -177,11 +179,11 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
 // address arithmetic cost more VALU than the overlap returns), and up to 32 waves per CU at different
 // phases keep the memory pipe busy.
 // ------------------------------------------------------------------------------------------------
-template <int BITS, int BT, int WAVES, int ABL, typename XT, bool HALF = false, bool SHORT = false>
+template <int BITS, int BT, int WAVES, int ABL, typename XT, bool HALF = false, bool SHORT = false, typename FIN = ColumnStore>
 __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* __restrict__ y,
                                            const float* lut, int K, int N, int b0, int nb, int bid,
                                            int n_col_tiles, int units_total, int units_per_wg, float* lds,
-                                           const Segment& sg, const Segment* lin) {
+                                           const Segment& sg, const Segment* lin, FIN fin = FIN()) {
   using F = Fmt<BITS>;
   constexpr uint32_t XB = sizeof(XT);  // bytes per element of vec (4: operator ABI, 2: fused linear, fp16 or bf16)
   // Clean slate for the compiler's wait-count model: the other roles sit upstream of this one in
@@ -454,7 +456,7 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
     acc[0][0] = f32x2{accp[0].x + accp[0].y, accp[1].x + accp[1].y};
     acc[1][0] = f32x2{accp[2].x + accp[2].y, accp[3].x + accp[3].y};
   }
-  dense_epilogue<BT, WAVES, ABL, typename OutType<XT>::type>(acc, lds + kCodebookFloats, topx_sum, fold_topx, y, N, col0, b0, nb, lane, wave, sg, lin, tl);
+  dense_epilogue<BT, WAVES, ABL, typename FIN::template Range<XT>::type, FIN>(acc, lds + kCodebookFloats, topx_sum, fold_topx, y, N, col0, b0, nb, lane, wave, sg, lin, tl, fin);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -30,6 +30,7 @@ constexpr int kWaves = SQLLM_WAVES;          // waves per workgroup (512 threads
 constexpr int kTileN = 64;         // output columns per dense tile = 16 lanes x 4 (one dwordx4 each)
 constexpr int kCsrChunk = SQLLM_CSR_CHUNK;  // non-zeros per CSR workgroup (a multiple of 1024: a lane holds a run of 2+)
 constexpr int kCsrSpanMax = 2048;  // CSR rows a chunk may span and still accumulate in LDS
+constexpr int kCsrEdge = 256;      // ... minus this many in the gated pair's kernels (csr_role, ORD: the table of the rows that waves share)
 constexpr int kCsrXtSpan = 191;    // ... and still keep a 64-row tile of sums in LDS (wide batches, transposed vec; half of it: a 128-row tile)
 constexpr int kSparsePassRows = 128;  // batch rows per workgroup of the wide-batch sparse launch
 constexpr int kTopxRows = SQLLM_TOPX_ROWS;  // k's per top-X slab (a multiple of 32)
@@ -130,6 +131,10 @@ inline int mfma_row_blocks(int batch) { return batch <= 16 ? 1 : batch <= 32 ? 2
 hipError_t launch_fused(int bits, const LaunchArgs& a, hipStream_t stream);
 hipError_t launch_linear_bf16(int bits, const LaunchArgs& a, hipStream_t stream);  // the fused linear, bf16 in / bf16 out (a.linear && a.bf16): launch_fused hands such launches on
 extern bool (*g_fused_variant)(int bits, const LaunchArgs& a, hipStream_t stream, hipError_t* err);  // measurement library hook (null in the product)
+// the gated pair (sqllm_gated_f16 / _bf16): a fused-linear launch of exactly two segments, gate and up, on the kernel of
+// sqllm_linear_gated.hip; `pair`: the plane of pair words [batch, N].  A hook that file sets when it is linked in (defined
+// null in sqllm_capi.hip: the host layer links without the kernels, and a missing kernel is an error, not a fallback).
+extern hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

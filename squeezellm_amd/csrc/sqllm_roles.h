@@ -69,15 +69,17 @@ __device__ __forceinline__ void xt_walk(const int* st, const float* __restrict__
 // ------------------------------------------------------------------------------------------------
 // CH: non-zeros per workgroup -- kCsrChunk, or (batch-1 operator launches that exceed the resident slots: sqllm_capi.hip, widen_csr_chunks) twice
 // that: half as many, twice as deep workgroups in front of a multi-round grid.
-template <int T, int BT, typename XT, typename AT, bool XTMODE = false, bool XCOH = false, typename GATE = NoGate, int CH = kCsrChunk>
+// FIN: the finishing step and range rule of a fused linear's column (sqllm_decode.h: ColumnStore, the default)
+template <int T, int BT, typename XT, typename AT, bool XTMODE = false, bool XCOH = false, typename GATE = NoGate, int CH = kCsrChunk,
+          typename FIN = ColumnStore>
 __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
                                          const int* __restrict__ rows, const int* __restrict__ cols,
                                          const float* __restrict__ vals, int nnz, int K, int N, int b0,
                                          int nb, int chunk, float* lds, const Segment* lin, int lin_or_abl_bits = 0,
                                          const float* __restrict__ xT = nullptr, int Bp = 0,
-                                         unsigned long long* tl = nullptr, GATE gate = GATE()) {
+                                         unsigned long long* tl = nullptr, GATE gate = GATE(), FIN fin = FIN()) {
   constexpr bool LIN = sizeof(AT) == 8;
-  using OT = typename OutType<XT>::type;  // fused linear: the 16-bit type of its two ends (range rule and output store)
+  using OT = typename FIN::template Range<XT>::type;  // fused linear: the 16-bit type of its two ends (range rule and output store)
   int tid_ = threadIdx.x;
   // (inside the persistent pass kernel the role runs in a loop over work items: what it derives from the thread id
   // is recomputed per item -- hoisted out of that loop it would be live across every other role of the kernel)
@@ -131,7 +133,11 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
   if (c_hi > N) c_hi = N;
   SQLLM_CSR_STAMP(1)  // round 1 (cols / vals / probes) has landed, both counts done
   const int n = c_hi - c_lo + 1;  // staged row pointers rows[c_lo .. c_hi]; candidate rows: n - 1
-  const bool in_lds = n <= kCsrSpanMax;
+  // FIN::kOrderedCsr (the gated pair): the sums of the rows a wave shares with its neighbours -- its first and its last -- meet in a fixed
+  // order (see row_add below); their table takes the last kCsrEdge floats of the accumulator
+  constexpr bool ORD = FIN::kOrderedCsr;
+  constexpr int CAP = kCsrSpanMax - (ORD ? kCsrEdge : 0);
+  const bool in_lds = n <= CAP;
 
   // ---- round 2 ----
   int* srows = reinterpret_cast<int*>(lds);  // [kCsrSpanMax]
@@ -147,11 +153,12 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
   // gathers of all rows are in flight together.
   int g = 1;
   if (in_lds) {
-    g = kCsrSpanMax / n;
+    g = CAP / n;
     if (g > nb) g = nb;
     if (g < 1) g = 1;
     for (int i = tid; i < n; i += T) srows[i] = rows[c_lo + i];
     for (int i = tid; i < n * g; i += T) sacc[i] = 0.f;  // first group's sums (no barrier of its own)
+    if constexpr (ORD) for (int i = tid; i < 16 * BT; i += T) sacc[CAP + i] = 0.f;
   }
   // transposed-vec mode: sums of the pass's rows, tile[row][local column] (odd stride: the lanes of a
   // wave -- one row each -- write one bank each), zeroed here, flushed coalesced along the columns
@@ -388,10 +395,37 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
   const bool cont_prev = prev_rl == rf;
   const bool flush_head = bnd & (rf >= 0);
   const bool flush_tail = (rl >= 0) & (next_rf != rl);
+  // One LDS add per (wave, row): a row's non-zeros inside a wave leave from one lane.  Rows strictly inside a wave's range therefore
+  // receive ONE add, onto zero: exact.  A wave's first and last row may continue in the neighbouring waves -- a row of more than 256
+  // non-zeros in up to eight -- and fp32 adds of three values and more depend on their order.  ORD: those two sums go to the wave's own
+  // slots edge[wave][first | last][batch row] instead, and one thread per batch row adds the slots to the rows in wave order after the
+  // barrier: the contribution is then the same fp32 value in every run.
+  float* edge = sacc + CAP;                                 // [T / 64][2][BT]
+  int* erow = reinterpret_cast<int*>(edge + 16 * BT);       // [T / 64][2]: the rows of the slots (-1: no valid non-zero in the wave)
+  static_assert(!ORD || (T == 512 && 16 * BT + 16 <= kCsrEdge), "eight waves x two slots");
+  int wfirst = -1, wlast = -1;
+  if constexpr (ORD) {
+    wfirst = __builtin_amdgcn_readfirstlane(lr[0]);
+    int m = rf > rl ? rf : rl;
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1) {
+      const int o = __shfl_xor(m, sft, 64);
+      m = o > m ? o : m;
+    }
+    wlast = m;
+    if (in_lds && (tid & 63) == 0) {
+      erow[2 * (tid >> 6)] = wfirst;
+      erow[2 * (tid >> 6) + 1] = wlast;
+    }
+  }
+  // (ORD only; the other instantiations keep their plain adds, statement for statement)
+#define SQLLM_ROW_ADD(BB, R, V) \
+  atomicAdd(((R) == wfirst || (R) == wlast) ? edge + (2 * (tid >> 6) + ((R) != wfirst ? 1 : 0)) * BT + (BB) : sacc + (BB) * n + (R), V)
   for (int bs = 0; bs < nb; bs += g) {
     const int gb = nb - bs < g ? nb - bs : g;
     if (in_lds && bs > 0) {
       for (int i = tid; i < n * gb; i += T) sacc[i] = 0.f;
+      if constexpr (ORD) for (int i = tid; i < 16 * BT; i += T) edge[i] = 0.f;
       __syncthreads();
     }
     // x of the group's rows for both non-zeros (unconditional loads: rows past the group re-read its last row)
@@ -424,17 +458,29 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
           const float carry = dpp_f32<0x138, 0xf>(t);  // the lane below's inclusive sum
           if (flush_head) {
             const float h = head + (cont_prev ? carry : 0.f);
+            if constexpr (ORD) {
+              if (in_lds) SQLLM_ROW_ADD(bb, rf, h);
+              else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + rf, h);
+            } else
             if (in_lds) atomicAdd(sacc + bb * n + rf, h);
             else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + rf, h);
           }
 #pragma unroll
           for (int i = 1; i < EPT - 1; ++i) {
             if (mid[i]) {
+              if constexpr (ORD) {
+                if (in_lds) SQLLM_ROW_ADD(bb, lr[i], q[i]);
+                else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + lr[i], q[i]);
+              } else
               if (in_lds) atomicAdd(sacc + bb * n + lr[i], q[i]);
               else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + lr[i], q[i]);
             }
           }
           if (flush_tail) {
+            if constexpr (ORD) {
+              if (in_lds) SQLLM_ROW_ADD(bb, rl, t);
+              else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + rl, t);
+            } else
             if (in_lds) atomicAdd(sacc + bb * n + rl, t);
             else acc_add<OT>(y + (size_t)(b0 + bs + bb) * N + c_lo + rl, t);
           }
@@ -444,6 +490,15 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
     if (in_lds) {
       __syncthreads();
       SQLLM_CSR_STAMP(4)  // x gathered, products scanned, row sums in LDS
+      if constexpr (ORD) {
+        if (tid < gb) {
+          for (int e = 0; e < 16; ++e) {
+            const int r = erow[e];
+            if (r >= 0 && !((e & 1) && r == erow[e - 1])) sacc[tid * n + r] += edge[e * BT + tid];
+          }
+        }
+        __syncthreads();
+      }
       if (cabl & 2) continue;
       for (int idx = tid; idx < nm1 * gb && n > 1; idx += T) {
         const int bb = idx / nm1;
@@ -457,7 +512,7 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
             const u64 mine = kCountUnit + to_fixed<OT>(sum);
             flag_nonfinite<OT>(y + at, sum);
             const unsigned target = (unsigned)lin->gm.k_slices + (unsigned)csr_chunks_of_row(r0, r1);
-            column_done<OT>(*lin, y + at, atomicAdd(y + at, mine) + mine, target, at, c_lo + i);
+            fin.template done<OT>(*lin, y + at, atomicAdd(y + at, mine) + mine, target, at, c_lo + i);
           }
         } else {
           if (sum != 0.f) acc_add<OT>(y + at, sum);
@@ -475,7 +530,7 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
         if ((r0 > e0 ? r0 : e0) < (r1 < e1 ? r1 : e1)) {
           const size_t at = (size_t)(b0 + bs) * N + c_lo + i;
           const unsigned target = (unsigned)lin->gm.k_slices + (unsigned)csr_chunks_of_row(r0, r1);
-          column_done<OT>(*lin, y + at, atomicAdd(y + at, kCountUnit) + kCountUnit, target, at, c_lo + i);
+          fin.template done<OT>(*lin, y + at, atomicAdd(y + at, kCountUnit) + kCountUnit, target, at, c_lo + i);
         }
       }
     }
@@ -668,12 +723,12 @@ __device__ __forceinline__ void csr_tile_fold_staged(const float* __restrict__ x
 // use 1 (their register budget); the fused small launch 8 -- row by row, a 16-row launch kept its top-X workgroups (first
 // in the grid) for 17 us, and the dense workgroups that found no slot beside them became a second round
 // (profiles/r05_small_split_timeline.txt).
-template <int T, typename XT, typename AT, bool XCOH = false, typename GATE = NoGate, int RB = 1>
+template <int T, typename XT, typename AT, bool XCOH = false, typename GATE = NoGate, int RB = 1, typename FIN = ColumnStore>
 __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
                                           const float* __restrict__ full_rows,
                                           const int* __restrict__ full_idx, int topX, int K, int N,
                                           int b0, int nb, int slab, float* lds, GATE gate = GATE()) {
-  using OT = typename OutType<XT>::type;  // (see csr_role)
+  using OT = typename FIN::template Range<XT>::type;  // (see csr_role)
   int tid_ = threadIdx.x;
   if constexpr (XCOH) asm volatile("" : "+v"(tid_));  // (see csr_role)
   const int tid = tid_;
@@ -839,5 +894,6 @@ __device__ __forceinline__ void topx_role_xt(const float* __restrict__ xT, int l
 constexpr int kWideSparseLdsFloats = cmax(kCsrSpanMax + cmax(kCsrSpanMax, 64 * (kCsrXtSpan + 1) + 3 * kCsrChunk), kTopxLds);
 
 #undef SQLLM_CSR_STAMP
+#undef SQLLM_ROW_ADD
 
 }  // namespace sqllm

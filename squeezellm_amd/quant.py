@@ -159,6 +159,27 @@ _is_capturing = torch.cuda.is_current_stream_capturing
 _FUSED_ENTRY = {torch.float16: "sqllm_linear_f16", torch.bfloat16: "sqllm_linear_bf16"}
 
 
+def _workspace_of(cache: dict, need: int, device, graph_max: int) -> torch.Tensor:
+    """The workspace rules of QuantLinearLUTFused._workspace (see there) on a module's cache dict, for `need` bytes."""
+    if _is_capturing():
+        ws = cache.get((device, "graph"))
+        if ws is not None and ws.numel() >= need:
+            return ws
+        return torch.zeros(need, dtype=torch.uint8, device=device)  # (not remembered: it belongs to this graph's pool)
+    key = (device, quant_cuda._raw_stream(device.index if device.index is not None else torch.cuda.current_device()))
+    ws = cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.zeros(need, dtype=torch.uint8, device=device)  # zero-filled once
+        cache[key] = ws
+    if need <= graph_max:
+        gws = cache.get((device, "graph"))
+        if gws is None or gws.numel() < need:
+            if gws is not None:
+                cache.setdefault("retired", []).append(gws)
+            cache[(device, "graph")] = torch.zeros(need, dtype=torch.uint8, device=device)
+    return ws
+
+
 class QuantLinearLUTFused(QuantLinearLUT):
     """Opt-in forward for fp16 and bf16 activations: ONE kernel per call (sqllm_linear_f16 / sqllm_linear_bf16) instead of the
     reference's four (`zeros`/`bias.clone()`, `x.float()`, the op, `y.to(fp16)`; quant.py:214-223,
@@ -221,25 +242,8 @@ class QuantLinearLUTFused(QuantLinearLUT):
         share it: replaying two of them CONCURRENTLY on different streams is not supported (set GRAPH_WS_MAX_BYTES = 0
         on the module for private, in-graph workspaces).  Without a prepared buffer (no eager call of this size before
         the capture) the workspace is a zero-filled temporary of the captured region."""
-        cache = self.__dict__.setdefault("_ws", {})
-        need = _lib.linear_workspace_bytes(self.outfeatures, batch)
-        if _is_capturing():
-            ws = cache.get((device, "graph"))
-            if ws is not None and ws.numel() >= need:
-                return ws
-            return torch.zeros(need, dtype=torch.uint8, device=device)  # (not remembered: it belongs to this graph's pool)
-        key = (device, quant_cuda._raw_stream(device.index if device.index is not None else torch.cuda.current_device()))
-        ws = cache.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.zeros(need, dtype=torch.uint8, device=device)  # zero-filled once
-            cache[key] = ws
-        if need <= self.GRAPH_WS_MAX_BYTES:
-            gws = cache.get((device, "graph"))
-            if gws is None or gws.numel() < need:
-                if gws is not None:
-                    cache.setdefault("retired", []).append(gws)
-                cache[(device, "graph")] = torch.zeros(need, dtype=torch.uint8, device=device)
-        return ws
+        return _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.linear_workspace_bytes(self.outfeatures, batch), device,
+                             self.GRAPH_WS_MAX_BYTES)
 
     def _check_csr_once(self) -> None:
         """The fused kernel detects completion by COUNTING the contributions `rows` announces: an
@@ -288,11 +292,14 @@ class QuantLinearLUTFused(QuantLinearLUT):
         workspace pointer are set per call (ONE entry per device and stream whatever row counts arrive: an entry per
         batch would pin a superseded workspace each and grow without bound under variable prompt lengths).  Rebuilt when
         a buffer is replaced, moved or written in place (identity, storage and version counter of every buffer it was
-        built from) or when a routing attribute changes (fold_topx, include_sparse, topX, numvals)."""
+        built from) or when a routing attribute changes (fold_topx, include_sparse, topX, numvals).
+        (QuantGatedLUTFused calls this on plain QuantLinearLUT members too: what it needs beyond the parent's attributes is
+        reached through this class, not through `self`.)"""
         # (straight from the module's buffer dict: nn.Module.__getattr__ costs ~0.5 us per buffer, ten times a dict lookup)
         bufs = self.__dict__["_buffers"]
+        fold_topx = getattr(self, "fold_topx", QuantLinearLUTFused.fold_topx)
         key = (tuple((id(t), t.data_ptr(), t._version) for t in bufs.values() if t is not None),
-               self.fold_topx, self.include_sparse, self.topX, self.numvals)
+               fold_topx, self.include_sparse, self.topX, self.numvals)
         cache = self.__dict__.setdefault("_desc", {})
         hit = cache.get((dev, stream))
         if hit is not None and hit[0] == key:
@@ -304,8 +311,8 @@ class QuantLinearLUTFused(QuantLinearLUT):
         o.bits, o.K, o.N = self.bits, K, N
         o.qweight, o.lookup_table = self.qweight.data_ptr(), self.lookup_table.data_ptr()
         if self.include_sparse and self.numvals > 0:
-            self._check_csr_once()
-        folded = self._csr_with_topx() if self.include_sparse and self.topX > 0 and self.fold_topx else None
+            QuantLinearLUTFused._check_csr_once(self)
+        folded = QuantLinearLUTFused._csr_with_topx(self) if self.include_sparse and self.topX > 0 and fold_topx else None
         keep = [folded]
         if folded is not None:  # one CSR term that contains the top-X rows (decode.fold_topx_into_csr)
             if folded[2].numel():
@@ -356,6 +363,118 @@ def fuse_quant_lut(module: nn.Module) -> int:
         if type(m) is QuantLinearLUT:
             m.__class__ = QuantLinearLUTFused
             n += 1
+    return n
+
+
+_GATED_ENTRY = {torch.float16: "sqllm_gated_f16", torch.bfloat16: "sqllm_gated_bf16"}
+
+
+class QuantGatedLUTFused(nn.Module):
+    """`silu(gate(x)) * up(x)` for fp16 and bf16 GPU activations as ONE kernel (sqllm_gated_f16 / sqllm_gated_bf16) instead of
+    two fused linears and two torch kernels over two [rows, N] temporaries: both sums are formed as in QuantLinearLUTFused,
+    the activation and the product are evaluated in fp32 and the result is rounded once to the activations' type
+    (include/sqllm_hip.h, sqllm_gated: semantics, non-finite values, and the range rule -- a partial sum beyond +-131072 in
+    magnitude makes that sum +-inf for fp16 as well as bf16, never a clamped finite number).
+
+    `gate` and `up` are two QuantLinearLUT / QuantLinearLUTFused modules of equal shape and bit width, held BY REFERENCE:
+    this module owns no buffers, no parameters and no state-dict keys, and does not appear among nobody's children because
+    of them; their folded top-X CSR and one-time CSR check are the members' own (shared with their own fused forward).  It keeps one
+    descriptor per (device, stream) and one workspace by the rules of QuantLinearLUTFused._workspace.  Other dtypes and CPU
+    tensors return F.silu(gate(x)) * up(x); with `gate.dense_min_rows` set, a call of at least that many rows sends both
+    members down their dense route and applies the activation in torch (in fp32, rounded once).  `last_route`: "gated" / "dense" / "fallback".
+
+    Speed: NOT MEASURED yet.  tools/gated_bench.py compares this class with two fused modules + torch silu / mul and with one
+    grouped launch + torch, graph-replayed; it has not been run, and DESIGN.md 4.4 has no table for it.  Expected only: two
+    torch launches and two [rows, N] temporaries fewer, one more atomic round trip per column."""
+
+    GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
+
+    def __init__(self, gate: QuantLinearLUT, up: QuantLinearLUT):
+        super().__init__()
+        for name, m in (("gate", gate), ("up", up)):
+            if not isinstance(m, QuantLinearLUT):
+                raise TypeError(f"{name} must be a QuantLinearLUT or QuantLinearLUTFused, got {type(m).__name__}")
+        if (gate.infeatures, gate.outfeatures) != (up.infeatures, up.outfeatures):
+            raise ValueError(f"gate and up must have the same shape: {gate.infeatures} x {gate.outfeatures} against "
+                             f"{up.infeatures} x {up.outfeatures}")
+        if gate.bits != up.bits:
+            raise ValueError(f"gate and up must have the same bit width: {gate.bits} against {up.bits}")
+        # by reference: nn.Module.__setattr__ would register them as children (and their buffers under this module's keys)
+        self.__dict__["gate"], self.__dict__["up"] = gate, up
+
+    @property
+    def last_route(self):
+        """"gated", "dense" or "fallback": the way the most recent forward went (None before the first)."""
+        return self.__dict__.get("_last_route")
+
+    def _descriptor(self, dev: int, stream: int):
+        """The sqllm_gated of (device, stream): the members' own pre-marshalled descriptors (QuantLinearLUTFused._descriptor:
+        rebuilt when a buffer or a routing attribute of the member changes) copied side by side, rebuilt when either is."""
+        lg = QuantLinearLUTFused._descriptor(self.gate, dev, stream)
+        lu = QuantLinearLUTFused._descriptor(self.up, dev, stream)
+        cache = self.__dict__.setdefault("_desc", {})
+        hit = cache.get((dev, stream))
+        if hit is not None and hit[0] is lg[0] and hit[1] is lu[0]:
+            return hit[2]
+        g = _lib.SqllmGated()
+        g.gate, g.up = lg[0].op, lu[0].op  # (copies)
+        g.gate.mul = g.up.mul = None
+        g.bias_gate, g.bias_up = lg[0].bias, lu[0].bias
+        g.act = _lib.ACT_SILU
+        entry = (g, ctypes.byref(g), (lg, lu))  # (the members' entries keep the folded CSRs alive)
+        cache[(dev, stream)] = (lg[0], lu[0], entry)
+        return entry
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        gate, up = self.gate, self.up
+        if x.dtype not in _GATED_ENTRY or not x.is_cuda:
+            self.__dict__["_last_route"] = "fallback"
+            return torch.nn.functional.silu(gate(x)) * up(x)
+        K, N = gate.infeatures, gate.outfeatures
+        if x.shape[-1] != K:
+            raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
+        x2 = x if x.dim() == 2 else x.reshape(-1, K)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        rows = x2.shape[0]
+        dense_min_rows = getattr(gate, "dense_min_rows", None)
+        if dense_min_rows is not None and rows >= dense_min_rows:
+            self.__dict__["_last_route"] = "dense"
+            dense = QuantLinearLUTFused._forward_dense
+            # (the two 16-bit sums widened: activation and product in fp32, one rounding -- as the kernel evaluates them)
+            return (torch.nn.functional.silu(dense(gate, x, x2).float()) * dense(up, x, x2).float()).to(x.dtype)
+        self.__dict__["_last_route"] = "gated"
+        dev = x.get_device()
+        out = torch.empty((rows, N), dtype=x.dtype, device=x.device)
+        g, ref, _keep = self._descriptor(dev, quant_cuda._raw_stream(dev))
+        batch = 0 if rows == 1 else rows
+        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.gated_workspace_bytes(N, batch), gate.qweight.device,
+                           self.GRAPH_WS_MAX_BYTES)
+        g.gate.batch = g.up.batch = batch
+        g.gate.vec = g.up.vec = x2.data_ptr()
+        g.out, g.workspace = out.data_ptr(), ws.data_ptr()
+        quant_cuda._launch(quant_cuda._fn(_GATED_ENTRY[x.dtype]), dev, (ref,))
+        return out.reshape(*x.shape[:-1], N)
+
+
+def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_proj", down: str = "down_proj") -> int:
+    """Give every submodule of `module` that has the attributes `gate`, `up` and `down` -- gate and up two quantised layers
+    of equal shape and bit width -- and whose `act_fn` is an nn.SiLU the forward `down(gated(x))`, with `gated` a
+    QuantGatedLUTFused over its gate and up (in place; parameters, buffers and state dict untouched).  Anything else is left
+    alone: a submodule without `act_fn`, or with another activation, keeps its forward.  Returns the number converted."""
+    n = 0
+    for m in module.modules():
+        g, u, d = getattr(m, gate, None), getattr(m, up, None), getattr(m, down, None)
+        if d is None or not isinstance(g, QuantLinearLUT) or not isinstance(u, QuantLinearLUT):
+            continue
+        if not isinstance(getattr(m, "act_fn", None), nn.SiLU):
+            continue
+        if (g.infeatures, g.outfeatures, g.bits) != (u.infeatures, u.outfeatures, u.bits):
+            continue
+        gated = QuantGatedLUTFused(g, u)
+        m.__dict__["gated"] = gated  # (not a child: the module tree and the state dict stay as they are)
+        m.forward = (lambda gated, d: lambda x: d(gated(x)))(gated, d)
+        n += 1
     return n
 
 
