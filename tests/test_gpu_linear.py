@@ -174,7 +174,8 @@ def test_linear_full_size_hybrid_w3(gpu):
 def test_linear_counts_every_kind_of_sparse_contribution(gpu, bits, rows):
     """Shapes chosen so that completion counting sees every case: rows spread over several CSR
     chunks (heavy rows), chunks that span more rows than fit in LDS (very sparse region, uncounted
-    adds + a counting pass), empty rows, more than 64 top-X columns, and repeated top-X indices."""
+    adds + a counting pass), empty rows, more than 64 top-X columns, and repeated top-X indices.
+    (tests/test_gpu_csr_span.py runs the role's span classes one by one, on bf16 and the gated pair as well.)"""
     import torch
 
     from squeezellm_amd import quant, synth
