@@ -263,6 +263,58 @@ int sqllm_gated_f16(const sqllm_gated* g, sqllm_stream_t stream);
 int sqllm_gated_bf16(const sqllm_gated* g, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Fused linear with an epilogue: activation and residual add in the linear's own kernel.
+ *
+ * What a model wraps around a linear -- `relu(fc1(x))`, `residual + o_proj(x)`, `residual + down_proj(h)` -- as part of
+ * the finishing step of each output element, instead of one or two element-wise kernels behind it:
+ *
+ *     out[b,n] = OT( act(bias[n] + sum_k W[n,k] * float(x[b,k])) + float(residual[b,n]) )
+ *
+ * `lin` is read exactly as sqllm_linear_f16 / _bf16 read it (OT = the type of x = the type of out and of residual); the
+ * workspace is sqllm_linear_workspace_bytes(&lin.op) bytes, is left zero-filled, and may be shared with plain
+ * sqllm_linear_* launches on the same stream.  Accumulation inside and between contributions is sqllm_linear_*'s.  The
+ * thread that completes a column holds its fp32 value; it applies `act`, adds the residual element and rounds ONCE, to
+ * nearest-even.  The activations are evaluated in fp32 as written here, and the values at +-inf and NaN are what these
+ * formulas give in IEEE fp32 (they are the specification; not every framework's GELU agrees at +inf):
+ *
+ *     act                  | formula                                                 | +inf | -inf | NaN
+ *     ---------------------+---------------------------------------------------------+------+------+-----
+ *     SQLLM_ACT_IDENTITY   | v                                                       | +inf | -inf | NaN
+ *     SQLLM_ACT_RELU       | v > 0 ? v : (v != v ? v : 0)                            | +inf |  0   | NaN
+ *     SQLLM_ACT_SILU       | v / (1 + expf(-v))                                      | +inf | NaN  | NaN
+ *     SQLLM_ACT_GELU       | 0.5 v (1 + erff(v * 0.70710678))                        | +inf | NaN  | NaN
+ *     SQLLM_ACT_GELU_TANH  | 0.5 v (1 + tanhf(0.79788456 (v + 0.044715 v^3)))        | +inf | NaN  | NaN
+ *
+ *   - The residual is added AFTER the activation by plain fp32 addition: +inf + (-inf) = NaN, a NaN residual gives NaN.
+ *   - The range rule is the bf16 rule for BOTH output types, as in the gated kernels: a finite contribution with
+ *     |v| > 131072 sets the infinity flag of its sign and adds nothing.  The fp16 linear clamps there because such an fp16
+ *     result is not finite anyway; here a contribution of 200000 can meet a residual of -180000, and a clamp would return
+ *     a wrong finite number.  So SQLLM_ACT_IDENTITY without a residual equals sqllm_linear_bf16 bit for bit, and equals
+ *     sqllm_linear_f16 wherever every contribution is within +-131072.
+ *   - The corner carved out for sqllm_linear_bf16 is inherited unchanged: a CSR chunk spanning more than 2048 rows adds its
+ *     values uncounted, a flag can be lost there, and the result can be finite and wrong.
+ *   - `residual` may be the output buffer itself (residual == lin.op.mul, the in-place form: each element is read and
+ *     written by the same single thread) and may equal lin.op.vec when K == N (both are only read).  Any other overlap of
+ *     the [batch, N] residual range with the output range is rejected.
+ *
+ * Like every entry point: one kernel, nothing allocated, nothing retained, no synchronisation, capturable as one kernel
+ * node.  Rejected before the device is touched: an act outside the five codes (SQLLM_E_OPTION); a residual that partly
+ * overlaps the output (SQLLM_E_SHAPE); a NULL descriptor (SQLLM_E_NULL); and everything sqllm_linear_* rejects, with its
+ * codes.  (sqllm_gated_* keeps rejecting every act but SQLLM_ACT_SILU.)  There is no group form.
+ * ------------------------------------------------------------------------------------------- */
+#define SQLLM_ACT_IDENTITY 1
+#define SQLLM_ACT_RELU 2
+#define SQLLM_ACT_GELU 3
+#define SQLLM_ACT_GELU_TANH 4
+typedef struct sqllm_linear_ep {
+  sqllm_linear lin;     /* exactly as for sqllm_linear_f16 / _bf16; workspace rules unchanged */
+  const void* residual; /* 16-bit [batch, N] of the output's type, or NULL; may equal lin.op.mul */
+  int32_t act;          /* SQLLM_ACT_*; note that 0 is SiLU */
+} sqllm_linear_ep;
+int sqllm_linear_ep_f16(const sqllm_linear_ep* e, sqllm_stream_t stream);
+int sqllm_linear_ep_bf16(const sqllm_linear_ep* e, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

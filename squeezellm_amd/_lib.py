@@ -50,6 +50,16 @@ class SqllmGated(ctypes.Structure):
 
 
 ACT_SILU = 0  # SQLLM_ACT_SILU
+ACT_IDENTITY = 1  # SQLLM_ACT_IDENTITY ... the epilogue's codes (sqllm_linear_ep_*; the gated pair takes SiLU only)
+ACT_RELU = 2
+ACT_GELU = 3
+ACT_GELU_TANH = 4
+
+
+class SqllmLinearEp(ctypes.Structure):
+    """struct sqllm_linear_ep (include/sqllm_hip.h): a fused linear, the residual (or NULL; may be lin.op.mul) and the activation code."""
+
+    _fields_ = [("lin", SqllmLinear), ("residual", c_void_p), ("act", c_int32)]
 
 
 class SqllmPlan(ctypes.Structure):
@@ -131,6 +141,8 @@ SIGNATURES = {
     "sqllm_gated_workspace_bytes": [POINTER(SqllmOp)],
     "sqllm_gated_f16": [POINTER(SqllmGated), P],
     "sqllm_gated_bf16": [POINTER(SqllmGated), P],
+    "sqllm_linear_ep_f16": [POINTER(SqllmLinearEp), P],
+    "sqllm_linear_ep_bf16": [POINTER(SqllmLinearEp), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],

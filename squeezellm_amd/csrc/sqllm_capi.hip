@@ -17,6 +17,7 @@
 
 namespace sqllm {
 hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated.hip
+hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream) = nullptr;  // set by sqllm_linear_ep.hip
 }
 
 namespace sqllm_host {
@@ -998,9 +999,14 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
 // `bf16` (fused linears only): vec and mul are bf16 -- same route, plan and workspace; the flag travels in LaunchArgs and
 // launch_fused hands such a launch to launch_linear_bf16 (sqllm_linear_bf16.hip), so the host layer calls the launchers it always did.
 // `pair` (sqllm_gated_*: two fused linears, gate and up): the plane of pair words; the launch then goes to the gated kernel.
+// `ep` (sqllm_linear_ep_*: one fused linear): activation code and residual; the launch then goes to the epilogue kernel.
+struct EpilogueArgs {
+  const void* residual;  // 16-bit [batch, N] of the output's type, or null
+  int act;               // SQLLM_ACT_*, validated by the caller
+};
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, const sqllm_linear* lin = nullptr, void* ws = nullptr, int64_t ws_bytes = 0,
-                                    bool ws_entry = false, bool bf16 = false, void* pair = nullptr) {
+                                    bool ws_entry = false, bool bf16 = false, void* pair = nullptr, const EpilogueArgs* ep = nullptr) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
   sqllm_op tmp[sqllm::kMaxSegments];
@@ -1056,6 +1062,10 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
         if (pair) {  // (sqllm_linear_gated.hip; without that file in the link there is no such kernel.  Not decorated: the measurement
                      // library's ablation bits, LDS pad and timeline buffer belong to the kernels it instantiates itself)
           e = sqllm::g_launch_linear_gated ? sqllm::g_launch_linear_gated(op->bits, a, pair, s) : hipErrorNotSupported;
+          break;
+        }
+        if (ep) {  // (sqllm_linear_ep.hip; a missing kernel is an error here too, and the launch is not decorated either)
+          e = sqllm::g_launch_linear_ep ? sqllm::g_launch_linear_ep(op->bits, a, ep->residual, ep->act, s) : hipErrorNotSupported;
           break;
         }
         if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: ablation bits, LDS pad, timeline buffer)
@@ -1163,6 +1173,25 @@ static int launch_gated(const sqllm_gated* g, sqllm_stream_t stream, bool bf16) 
 
 int sqllm_gated_f16(const sqllm_gated* g, sqllm_stream_t stream) { return launch_gated(g, stream, false); }
 int sqllm_gated_bf16(const sqllm_gated* g, sqllm_stream_t stream) { return launch_gated(g, stream, true); }
+
+// one fused linear (same route, plan, validation and workspace), finished by the epilogue kernel
+static int launch_linear_ep(const sqllm_linear_ep* e, sqllm_stream_t stream, bool bf16) {
+  if (!e) return SQLLM_E_NULL;
+  if (e->act < SQLLM_ACT_SILU || e->act > SQLLM_ACT_GELU_TANH) return SQLLM_E_OPTION;
+  const sqllm_op& op = e->lin.op;
+  // the residual may be the output itself (one thread reads and writes an element); any other overlap of the two [batch, N]
+  // ranges is rejected.  (Shapes the linear's own validation is about to reject are left to it.)
+  if (e->residual && op.mul && e->residual != op.mul && op.N > 0) {
+    const uintptr_t r = reinterpret_cast<uintptr_t>(e->residual), o = reinterpret_cast<uintptr_t>(op.mul);
+    const uintptr_t bytes = 2u * (uintptr_t)(op.batch <= 0 ? 1 : op.batch) * (uintptr_t)op.N;
+    if (r < o + bytes && o < r + bytes) return SQLLM_E_SHAPE;
+  }
+  const EpilogueArgs ep = {e->residual, e->act};
+  return launch_group_with_events(nullptr, 1, stream, nullptr, nullptr, &e->lin, nullptr, 0, false, bf16, nullptr, &ep);
+}
+
+int sqllm_linear_ep_f16(const sqllm_linear_ep* e, sqllm_stream_t stream) { return launch_linear_ep(e, stream, false); }
+int sqllm_linear_ep_bf16(const sqllm_linear_ep* e, sqllm_stream_t stream) { return launch_linear_ep(e, stream, true); }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

@@ -135,6 +135,9 @@ extern bool (*g_fused_variant)(int bits, const LaunchArgs& a, hipStream_t stream
 // sqllm_linear_gated.hip; `pair`: the plane of pair words [batch, N].  A hook that file sets when it is linked in (defined
 // null in sqllm_capi.hip: the host layer links without the kernels, and a missing kernel is an error, not a fallback).
 extern hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream);
+// the fused linear with an epilogue (sqllm_linear_ep_f16 / _bf16): a fused-linear launch of exactly one segment on the kernel of
+// sqllm_linear_ep.hip; `residual`: 16-bit [batch, N] of the output's type or null, `act`: SQLLM_ACT_*.  A hook, as above.
+extern hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

@@ -157,6 +157,25 @@ class QuantLinearLUT(nn.Module):
 _is_capturing = torch.cuda.is_current_stream_capturing
 # activation dtypes of the fused forward -> the entry point that takes them (one sqllm_linear descriptor serves both)
 _FUSED_ENTRY = {torch.float16: "sqllm_linear_f16", torch.bfloat16: "sqllm_linear_bf16"}
+# ... and the entry point of the same linear with an epilogue (QuantLinearLUTFused.act, forward's residual / out)
+_EP_ENTRY = {torch.float16: "sqllm_linear_ep_f16", torch.bfloat16: "sqllm_linear_ep_bf16"}
+_EP_ACT = {None: _lib.ACT_IDENTITY, "relu": _lib.ACT_RELU, "silu": _lib.ACT_SILU, "gelu": _lib.ACT_GELU, "gelu_tanh": _lib.ACT_GELU_TANH}
+
+
+def _torch_epilogue(y: torch.Tensor, act, residual, dtype) -> torch.Tensor:
+    """act(y) + residual in fp32 with the formulas of the kernel (include/sqllm_hip.h, sqllm_linear_ep), rounded once to `dtype`."""
+    v = y.float()
+    if act == "relu":
+        v = torch.where(v > 0, v, torch.where(v != v, v, torch.zeros_like(v)))
+    elif act == "silu":
+        v = v / (1 + torch.exp(-v))
+    elif act == "gelu":
+        v = 0.5 * v * (1 + torch.erf(v * 0.70710678))
+    elif act == "gelu_tanh":
+        v = 0.5 * v * (1 + torch.tanh(0.79788456 * (v + 0.044715 * v * v * v)))
+    if residual is not None:
+        v = v + residual.float()
+    return v.to(dtype)
 
 
 def _workspace_of(cache: dict, need: int, device, graph_max: int) -> torch.Tensor:
@@ -198,7 +217,21 @@ class QuantLinearLUTFused(QuantLinearLUT):
     stream, capture-safe, never cached on the module -- so the peak extra memory is ONE layer's matrix
     (2 * infeatures * outfeatures bytes: 142 MB for a 13B gate/up layer).  Recommended value: 128 -- on the 13B shapes
     the dense route measured 2.8 - 6.4x faster at 128 rows and 17 - 34x at 2048 (the figures per shape stand beside the
-    attribute, the table in DESIGN.md 4.5); the break-even lies lower and is not measured.  The default stays None."""
+    attribute, the table in DESIGN.md 4.5); the break-even lies lower and is not measured.  The default stays None.
+
+    Epilogue: with the class or instance attribute `act` set ("relu", "silu", "gelu", "gelu_tanh") and / or a `residual`
+    given to forward, the call is still ONE kernel (sqllm_linear_ep_f16 / _bf16): out = OT(act(linear(x)) + residual),
+    evaluated in fp32 and rounded once (include/sqllm_hip.h, sqllm_linear_ep: the formulas, non-finite values, and the
+    range rule -- a partial sum beyond +-131072 makes the sum +-inf for fp16 too, never a clamped number).  `out` may be a
+    tensor to write into; `out is residual` is the in-place form `h += linear(x)`.  The parent's path for other dtypes applies
+    the same formulas in torch, in fp32 with one rounding.  So does the dense route (`dense_min_rows`), which for such a call
+    stays in fp32 from end to end -- the layer's matrix in fp32 (a temporary of 4 * infeatures * outfeatures bytes, twice the
+    plain dense route's) and torch's fp32 GEMM -- so that its result is within one rounding of the kernel's; its speed against
+    the kernel is not measured.  `last_route` is "fused_ep" for the kernel.
+    Speed against the same module followed by torch relu / add, graph-replayed on an MI355X (tools/epilogue_bench.py, table in
+    DESIGN.md 4.4, raw output profiles/epilogue_bench.txt; 7B / 13B o_proj and down_proj + add, OPT-6.7B fc1 + relu): 1.1 - 2.7 us
+    less per linear at 1 and 4 rows (4 - 27 %); at 16 rows 0 - 7 % less, with three bf16 dense-only points of 40 not faster
+    (+0.9 % at most, inside the spread)."""
 
     # rows from which forward takes the dense route; None (default): never -- every call runs the fused kernel, as before
     # the route existed.
@@ -211,9 +244,13 @@ class QuantLinearLUTFused(QuantLinearLUT):
     # measurement behind it, not the break-even.  The price is the temporary matrix (see the class docstring).
     dense_min_rows = None
 
+    # the activation forward applies to the linear's fp32 result before the residual and the one rounding: None (default:
+    # nothing, today's forward), "relu", "silu", "gelu" (erf form) or "gelu_tanh"
+    act = None
+
     @property
     def last_route(self):
-        """"fused" or "dense": the way the most recent fp16 / bf16 GPU forward of this module went (None before the first)."""
+        """"fused", "fused_ep" (the kernel with the epilogue) or "dense": the way the most recent fp16 / bf16 GPU forward of this module went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def _forward_dense(self, x: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
@@ -329,7 +366,72 @@ class QuantLinearLUTFused(QuantLinearLUT):
             cache[(dev, stream)] = entry
         return entry[1]
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _epilogue_descriptor(self, dev: int, stream: int):
+        """The sqllm_linear_ep of (device, stream): the module's own pre-marshalled sqllm_linear (see _descriptor) copied
+        into it, rebuilt when that one is; residual, act, vec / mul, the batch and the workspace are set per call."""
+        lin = self._descriptor(dev, stream)
+        cache = self.__dict__.setdefault("_ep_desc", {})
+        hit = cache.get((dev, stream))
+        if hit is not None and hit[0] is lin[0]:
+            return hit[1]
+        e = _lib.SqllmLinearEp()
+        e.lin = lin[0]  # (a copy)
+        entry = (e, ctypes.byref(e), lin)  # (the linear's entry keeps the folded CSR alive)
+        cache[(dev, stream)] = (lin[0], entry)
+        return entry
+
+    def _forward_epilogue(self, x: torch.Tensor, residual, out) -> torch.Tensor:
+        act = self.act
+        if act not in _EP_ACT:
+            raise ValueError(f"act must be one of None, 'relu', 'silu', 'gelu', 'gelu_tanh', got {act!r}")
+        K, N = self.infeatures, self.outfeatures
+        if x.shape[-1] != K:
+            raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
+        shape = (*x.shape[:-1], N)
+        for name, t in (("residual", residual), ("out", out)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != x.dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {x.dtype} tensor of shape {shape} on {x.device}")
+        if out is not None and out is not residual and residual is not None and out.data_ptr() != residual.data_ptr():
+            lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * out.element_size()
+            if residual.data_ptr() < hi and lo < residual.data_ptr() + residual.numel() * residual.element_size():
+                raise ValueError("out must be residual itself or must not overlap it")
+        if x.dtype not in _FUSED_ENTRY or not x.is_cuda:
+            y = _torch_epilogue(QuantLinearLUT.forward(self, x), act, residual, x.dtype)
+            return y if out is None else out.copy_(y)
+        x2 = x if x.dim() == 2 else x.reshape(-1, K)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        rows = x2.shape[0]
+        if self.dense_min_rows is not None and rows >= self.dense_min_rows:
+            self.__dict__["_last_route"] = "dense"
+            # fp32 from end to end, so that the ONE rounding of the kernel is the only one here too: the layer's matrix in fp32
+            # (a temporary of this call, 4 * K * N bytes) and torch's fp32 GEMM.  (_forward_dense, the route without an
+            # epilogue, keeps its 16-bit matrix and GEMM: there the sum is rounded to 16 bits either way.)
+            y = torch.nn.functional.linear(x2.float(), self.dequantize(torch.float32)).reshape(shape)
+            if self.bias is not None:
+                y = y + self.bias
+            y = _torch_epilogue(y, act, residual, x.dtype)
+            return y if out is None else out.copy_(y)
+        self.__dict__["_last_route"] = "fused_ep"
+        dev = x.get_device()
+        if out is None:
+            out = torch.empty(shape, dtype=x.dtype, device=x.device)
+        e, ref, _keep = self._epilogue_descriptor(dev, quant_cuda._raw_stream(dev))
+        batch = 0 if rows == 1 else rows
+        ws = self._workspace(batch, self.qweight.device)
+        o = e.lin.op
+        o.batch, o.vec, o.mul = batch, x2.data_ptr(), out.data_ptr()
+        e.lin.workspace = ws.data_ptr()
+        e.residual = None if residual is None else residual.data_ptr()
+        e.act = _EP_ACT[act]
+        quant_cuda._launch(quant_cuda._fn(_EP_ENTRY[x.dtype]), dev, (ref,))
+        return out
+
+    def forward(self, x: torch.Tensor, residual=None, out=None) -> torch.Tensor:
+        if self.act is not None or residual is not None or out is not None:
+            return self._forward_epilogue(x, residual, out)
         if x.dtype not in _FUSED_ENTRY or not x.is_cuda:
             return super().forward(x)
         K, N = self.infeatures, self.outfeatures
@@ -461,7 +563,9 @@ def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_pr
     """Give every submodule of `module` that has the attributes `gate`, `up` and `down` -- gate and up two quantised layers
     of equal shape and bit width -- and whose `act_fn` is an nn.SiLU the forward `down(gated(x))`, with `gated` a
     QuantGatedLUTFused over its gate and up (in place; parameters, buffers and state dict untouched).  Anything else is left
-    alone: a submodule without `act_fn`, or with another activation, keeps its forward.  Returns the number converted."""
+    alone: a submodule without `act_fn`, or with another activation, keeps its forward.  Where `down` is a
+    QuantLinearLUTFused the submodule also gets `forward_residual(x, residual)` = `residual + down(gated(x))` with the add
+    done by down's kernel (QuantLinearLUTFused.forward: residual).  Returns the number converted."""
     n = 0
     for m in module.modules():
         g, u, d = getattr(m, gate, None), getattr(m, up, None), getattr(m, down, None)
@@ -474,6 +578,8 @@ def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_pr
         gated = QuantGatedLUTFused(g, u)
         m.__dict__["gated"] = gated  # (not a child: the module tree and the state dict stay as they are)
         m.forward = (lambda gated, d: lambda x: d(gated(x)))(gated, d)
+        if isinstance(d, QuantLinearLUTFused):  # `residual + down(gated(x))` with the add inside down's kernel
+            m.__dict__["forward_residual"] = (lambda gated, d: lambda x, residual: d(gated(x), residual=residual))(gated, d)
         n += 1
     return n
 
