@@ -429,14 +429,23 @@ const char* sqllm_error_string(int code); /* static string for SQLLM_E_* and hip
  *                     measured default, which depends on the bit width; get_option returns the stored 0): 4-bit 2..4 / 7
  *                     (9 for an op of <= 16 MB of packed weights alone in its launch), 3-bit 2..8 / 9.
  *                     At ONE row (batch 1, or the matvec names) the defaults route by launch shape instead (round 6, sqllm_capi.hip: cols_pays_batch1 --
- *                     dense-only launches of >= 16 MB that are a three-op group, a tall single op or a 3-bit two-op group, and the 7B-class sparse groups,
- *                     take the column-lane kernel); an explicit cols_min_batch = 1 sends every one-row launch there, a huge cols_min_batch none.
+ *                     dense-only launches of >= 16 MB that are a three-op group, a tall single op, a 3-bit two-op group or -- round 7 -- a 4-bit two-op group
+ *                     whose one-row plan is whole ranges per column tile with >= 95 % of their unit slots live (7B gate/up: two ranges of 256 units per tile,
+ *                     -10.6 % against the fused kernel build against build; 13B: one of 640, -13 %; 65B: one of 1024, -10.5 % -- these two measured once each, on the previous build with the cut asked for through "target_wgs"), and the 7B-class sparse groups,
+ *                     take the column-lane kernel; launches with sparse roles otherwise keep the fused kernel: 7B s45 gate/up 15.3 against 19.2 us); an explicit cols_min_batch = 1 sends every one-row launch there, a huge cols_min_batch none.
  *                     With the two cols_* options at their defaults the column-lane kernel is further reserved
  *                     for what it measured faster on: 4-bit, groups of three or more ops (up to 4 rows) and single ops of
  *                     >= 20 MB packed weights (up to 6 rows); 3-bit, >= 16 MB at up to 4 rows or N >= 8192; setting either option
  *                     takes the range at its word.
  *   "cols_groups"     1 (default): a GROUP of ops over one vec (sqllm_launch_group) may take the column-lane kernel
  *                     too, as one launch, judged by the sum of its columns; 0: groups stay on the batch tiles
+ *   "cols_slot_cut"   0 (default): a ONE-ROW launch of the column-lane kernel whose equal ranges would cross column-tile boundaries is cut into whole
+ *                     ranges per tile instead -- the cut that executes the fewest unit slots of the kernel's loop (it works in quanta of 64 units per
+ *                     workgroup at 4 bits, 32 at 3 bits) among those whose workgroups are resident at once; a plan that is tile-aligned already stays.
+ *                     1: every one-row plan is re-cut that way wherever that executes no more slots (measured slower on the 7B down_proj).
+ *                     "target_wgs" / "groups_per_wave" override both: with either set the plan is that of the shared range cut, and the dense-only 4-bit
+ *                     two-op group, whose one-row route depends on this cut, goes back to the fused kernel unless "cols_min_batch" = 1 forces the
+ *                     column-lane kernel (geometry sweeps on that pair set it).
  *   "sparse_transpose" 1 (default): the sparse terms of a batched op (mfma_min_batch rows and more) read a transposed copy of
  *                     vec (lane = batch row, coalesced) out of the caller's workspace (sqllm_launch_ws) or, for the
  *                     workspace-less names, out of stream-ordered scratch; 0: they gather from vec itself, as they do

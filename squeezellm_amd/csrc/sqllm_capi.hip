@@ -464,6 +464,90 @@ void make_plan_cols(const sqllm_op* op, sqllm::KernelGeom* gm, int ops_in_launch
   cut_ranges(gm, op->bits, ops_in_launch, sqllm::kWaves, 3 * cu_count(), (gm->batch + bt - 1) / bt);
 }
 
+// ---- the ONE-ROW cut of the column-lane kernel (sqllm_fused_cols<BITS, 1, 8>) ----
+// Unit slots a workgroup executes for a piece of n units: wave w takes units w, w + kWaves, ... (n_w of them) and runs
+// ceil(ceil(n_w / D) / NB) chunk pairs of NB * D slots each, as the one-row loop of dense_role_cols counts them (the constants: sqllm_kernels.h).
+static long long cols_piece_slots(int bits, long long n) {
+  const int D = sqllm::cols_chunk_units(bits), NB = sqllm::kColsChunksInFlight, W = sqllm::kWaves;
+  auto wave = [&](long long n_w) { return (long long)NB * D * (((n_w + D - 1) / D + NB - 1) / NB); };
+  return (n % W) * wave(n / W + 1) + (W - n % W) * wave(n / W);
+}
+// ... for a column tile of U units cut into tile-aligned ranges of L units (the last one ragged)
+static long long cols_tile_slots(int bits, int U, int L) {
+  const int k = (U + L - 1) / L;
+  return (k - 1) * cols_piece_slots(bits, L) + cols_piece_slots(bits, U - (long long)(k - 1) * L);
+}
+// ... and for a whole op as cut_ranges left it, in the reading the kernel gives the plan (sqllm_ranges.h: units_stride_of).  Contiguous reading: the
+// ranges cross tile boundaries (*crossing; such a range is two pieces: two table builds, two epilogues, a barrier more) and the count is a LOWER bound in
+// O(1) -- every range as one piece; the pieces of a crossing range only add slots.  (This runs in front of every eager launch: no walk over the ranges.)
+static long long cols_plan_slots(int bits, const sqllm::KernelGeom& gm, bool* crossing) {
+  const long long U = gm.units_total, L = gm.units_per_wg, total = gm.col_tiles * U;
+  if (gm.dense_blocks == gm.col_tiles * gm.k_slices) return gm.col_tiles * cols_tile_slots(bits, (int)U, (int)L);
+  *crossing = true;
+  return total / L * cols_piece_slots(bits, L) + cols_piece_slots(bits, total % L);
+}
+
+// The best tile-aligned cut of a one-row launch whose ops have `tiles` column tiles in all and U units per tile, beside `sparse`
+// workgroups: candidates are p = 1, 2, ... ranges per tile of ceil(U / p) units rounded up to whole waves; among those whose workgroups
+// fit the four resident per CU the one with the fewest executed slots wins.  Ties go to the largest workgroup count up to the column-lane kernel's
+// target of three per CU, and only without one to the smallest above it: nearest-to-target was measured on the 13B 4-bit gate/up pair, 864 workgroups
+// (two ranges of 320 units per tile) 19.9 us against 18.6 for 432 (one of 640) -- while under the target more is better: 7B gate/up 688 (2 x 256) 12.7
+// against 14.4 us for 344 (1 x 512), 7B q/k/v 768 (4 x 128) 8.3 against 9.0 for 384 (profiles/cols_batch1_cut_ab.txt).
+// Returns the range length (0: nothing fits) and the slots per tile.
+static int best_aligned_cut(int bits, int U, long long tiles, long long sparse, long long* slots_per_tile) {
+  const int W = sqllm::kWaves;
+  const long long room = 4ll * cu_count() - sparse, want = 3ll * cu_count();
+  int best = 0, prev = 0;
+  long long best_slots = 0;
+  for (int p = 1; p <= U; ++p) {
+    const int L = ((U + p - 1) / p + W - 1) / W * W;
+    if (L == prev) continue;
+    prev = L;
+    const long long k = (U + L - 1) / L, wgs = tiles * k;
+    if (wgs > room || tiles * k * L >= (1ll << 31)) break;  // (more ranges only make both larger; the kernel walks the padded space in 32 bits)
+    const long long slots = cols_tile_slots(bits, U, L);
+    // (candidates come with growing workgroup counts: the last one up to three per CU, else the first above)
+    if (!best || slots < best_slots || (slots == best_slots && wgs <= want)) { best = L; best_slots = slots; }
+    if (L == W) break;
+  }
+  *slots_per_tile = best_slots;
+  return best;
+}
+
+// cut_ranges aims at a workgroup COUNT and takes whole ranges per tile only where that comes within 10 % of it.  At one row the kernel is bound by
+// issue, and what a launch pays for a near miss was measured on the 7B 4-bit gate/up pair (two ranges per tile = 344 per op against 384
+// wanted: 10 x 344 < 9 x 384): ranges of 232 units across tile boundaries -- most workgroups two pieces, 29 units per wave in 32 slots --
+// 15.6 us against 12.7 for two whole-tile ranges of 256 (one range per tile: 14.4; profiles/cols_batch1_cut_ab.txt).  So: where the plan of
+// cut_ranges has ranges that cross tile boundaries, a one-row launch takes the best tile-aligned cut instead, unless that executes more slots.
+// A plan that is tile-aligned already STAYS, whatever its slots: the 7B down_proj (twelve ranges of 120 units per tile, 93.5 % of its slots
+// live, 768 workgroups = three per CU) measured 3.5 % SLOWER on eleven of 128 (97.7 %, 704 workgroups: 8.25 against 7.97 us), and q/k/v on
+// two of 256 instead of four of 128 (both 100 %) 8.5 % slower -- the even three per CU is worth more than the last dead slots.
+// Option cols_slot_cut = 1 is the rule by slots alone, as it was first written down: the best tile-aligned cut wherever it executes no more slots than the
+// plan of cut_ranges, aligned or not (the 7B down_proj then gets its eleven ranges).  Kept for re-measuring on other parts, off by default.
+// Options target_wgs / groups_per_wave: cut_ranges has obeyed them, and that stands.  `gm`: the n ops of the launch as make_plan_cols left them.
+static void cut_ranges_one_row(const sqllm_op* ops, sqllm::KernelGeom* gm, int n) {
+  if (opt(&Knobs::groups_per_wave) > 0 || opt(&Knobs::target_wgs) > 0) return;
+  const int bits = ops[0].bits, U = gm[0].units_total;
+  long long tiles = 0, sparse = 0, today = 0;
+  bool crossing = false;
+  for (int i = 0; i < n; ++i) {
+    tiles += gm[i].col_tiles;
+    sparse += gm[i].dense_block0;
+    today += cols_plan_slots(bits, gm[i], &crossing);
+  }
+  const bool by_slots = opt(&Knobs::cols_slot_cut) != 0;
+  if (!crossing && !by_slots) return;
+  long long slots = 0;
+  const int L = best_aligned_cut(bits, U, tiles, sparse, &slots);
+  // (for a crossing plan `today` is a lower bound -- cols_plan_slots -- so this comparison is biased towards KEEPING the crossing plan)
+  if (!L || tiles * slots > today) return;
+  for (int i = 0; i < n; ++i) {
+    gm[i].units_per_wg = L;
+    gm[i].k_slices = (U + L - 1) / L;
+    gm[i].dense_blocks = gm[i].col_tiles * gm[i].k_slices;  // (the tile-aligned reading: sqllm_ranges.h, units_stride_of)
+  }
+}
+
 int cols_min_batch_of() {
   const int v = opt(&Knobs::cols_min_batch);
   return v > 0 ? v : 2;
@@ -501,13 +585,45 @@ bool cols_pays(const sqllm_op* op, int n_ops) {
 //   13B w4 s45       +27 %             +6.5 %             +2 %             +17 %
 //   13B w3 s45       +27 %             +9.7 %             +5.5 %           +6.1 %
 //   65B w3 s45       +15 %             +0.7 %             -5 %             +13 %
-// Dense-only launches of >= 16 MB win on it -- three-op groups always, a single op if it is tall (K >= 2 N: the square 65B o_proj loses), two-op groups at 3 bits.
+// Round 7, with the kernel's one-row decode loop and the one-row cut (cut_ranges_one_row) -- same protocol, dense-only, graph wall in us, fused | column-lane
+// on the plan of cut_ranges | column-lane on whole-tile ranges (profiles/cols_batch1_cut_ab.txt; the 7B pair in two runs, of which the first alone -- gain 1.64 us against a
+// fused spread of 1.02 -- fell short of the adoption rule, and again build against build: 14.54 -> 13.00; the 13B / 65B rows are ONE process each on the parent build, the whole-tile cut asked for through target_wgs):
+//   7B  w4 gate/up   14.4 / 15.5 | 15.6 (3 x 232 units across tiles)  | 12.7 / 13.0 (2 x 256: -11.5 / -16 % against fused)   1 x 512: 14.4
+//   13B w4 gate/up   21.4        | 20.6 (2 x 360 across tiles)        | 18.6 (1 x 640: -13 %)                                   2 x 320: 19.9
+//   65B w4 gate/up   43.9        | 41.0 (2 x 920 across tiles)        | 39.3 (1 x 1024: -10.5 %)
+//   65B w3 gate/up   35.5        | 36.0 (2 x 232 across tiles)        | 33.5 (1 x 256: -5.7 %)
+//   7B  w4 q/k/v      8.75       |  8.33 (4 x 128, aligned: -4.8 %)   | (2 x 256: 9.04)
+//   7B  w4 down_proj  8.31       |  7.97 (12 x 120, aligned: -4.1 %)  | (11 x 128: 8.25; 16 x 88: 10.4)
+//   7B  w4 s45 gate/up 15.3      | 19.6                               | 19.2 (1 x 512: the sparse workgroups leave no room for two)  -> stays fused
+// So the 4-bit pair's tie / loss in the table above was its CUT (ranges across tile boundaries: two table builds, two epilogues, 29 units in 32 slots), not the kernel.
+// Dense-only launches of >= 16 MB win on it -- three-op groups always, a single op if it is tall (K >= 2 N: the square 65B o_proj loses), two-op groups at 3 bits, and
+// at 4 bits where the plan is whole-tile ranges with >= 95 % of their slots live (7B, 13B, 65B: all 100 %).
 // With sparse roles in the grid (which have none of the fused path's role priorities and wide chunks here) only the 3-bit groups whose K cuts into even ranges
 // (K a multiple of 2048) up to 40 MB do: 7B q/k/v and gate/up -- and the 4-bit 7B q/k/v group, by a little.
-bool cols_pays_batch1(const sqllm_op* sum, int n_ops, bool sparse) {
+bool cols_pays_batch1(const sqllm_op* sum, int n_ops, bool sparse, const sqllm_op* ops) {  // (ops: the launch's ops themselves)
   const double mb = (double)sum->K * sum->N * sum->bits / 8e6;
   if (mb < 16.0) return false;
-  if (!sparse) return n_ops >= 3 || (n_ops == 1 && sum->K >= 2ll * sum->N) || (n_ops == 2 && sum->bits == 3);
+  if (!sparse) {
+    if (n_ops >= 3 || (n_ops == 1 && sum->K >= 2ll * sum->N) || (n_ops == 2 && sum->bits == 3)) return true;
+    if (n_ops != 2 || opt(&Knobs::groups_per_wave) > 0 || opt(&Knobs::target_wgs) > 0) return false;
+    // the 4-bit pair: where its plan is whole-tile ranges with >= 95 % of their slots live (cut_ranges_one_row: 7B two ranges of 256 units per tile,
+    // 13B one of 640, 65B one of 1024 -- all 100 %)
+    // (route_of runs in front of validate_group: a pair that validation will refuse -- a shape validate() rejects, ops that do not share K and bits -- is
+    // not planned here; it keeps the fused route and gets its error code there)
+    for (int i = 0; i < 2; ++i)
+      if (ops[i].bits != 4 || ops[i].K != ops[0].K || ops[i].K <= 0 || ops[i].N <= 0 || ops[i].K % 32 != 0 || ops[i].N % 4 != 0) return false;
+    // (the launch is planned here and again in plan_group: two make_plan calls and at most a few candidates of best_aligned_cut, no walk over ranges)
+    sqllm::KernelGeom gm[2];
+    for (int i = 0; i < 2; ++i) make_plan_cols(&ops[i], &gm[i], 2);
+    cut_ranges_one_row(ops, gm, 2);
+    long long slots = 0, units = 0;
+    bool crossing = false;
+    for (int i = 0; i < 2; ++i) {
+      slots += cols_plan_slots(4, gm[i], &crossing);
+      units += (long long)gm[i].col_tiles * gm[i].units_total;
+    }
+    return !crossing && 100 * units >= 95 * slots;
+  }
   // (4-bit: the three-op group only -- 7B q/k/v -1.7 / -3.5 % on two boxes; its gate/up loses 18 %)
   return sum->K % 2048 == 0 && mb <= 40.0 && n_ops >= (sum->bits == 3 ? 2 : 3);
 }
@@ -515,10 +631,10 @@ bool cols_pays_batch1(const sqllm_op* sum, int n_ops, bool sparse) {
 static bool op_has_sparse(const sqllm_op* op) { return (op->rows && op->nnz > 0) || (op->full_rows && op->topX > 0); }
 
 // the routing test shared by single ops and groups: `sum` = the op, or the group as the one op it is to the kernel (the sum of its columns)
-static bool cols_route(const sqllm_op* sum, int n_ops, bool sparse) {
+static bool cols_route(const sqllm_op* sum, int n_ops, bool sparse, const sqllm_op* ops) {
   const int b = sum->batch <= 0 ? 1 : sum->batch;
   const bool explicit_range = opt(&Knobs::cols_min_batch) > 0 || opt(&Knobs::cols_max_batch) > 0;
-  if (b == 1 && !explicit_range) return cols_pays_batch1(sum, n_ops, sparse);
+  if (b == 1 && !explicit_range) return cols_pays_batch1(sum, n_ops, sparse, ops);
   return b >= cols_min_batch_of() && b <= cols_max_batch_of(sum) && cols_pays(sum, n_ops);
 }
 
@@ -532,10 +648,10 @@ bool group_takes_cols_path(const sqllm_op* ops, int n) {
     sparse = sparse || op_has_sparse(&ops[i]);
   }
   sum.N = N > 0x7fffffff ? 0x7fffffff : (int)N;
-  return !takes_mfma_path(&ops[0], n) && cols_route(&sum, n, sparse);
+  return !takes_mfma_path(&ops[0], n) && cols_route(&sum, n, sparse, ops);
 }
 
-bool takes_cols_path(const sqllm_op* op) { return !takes_mfma_path(op) && cols_route(op, 1, op_has_sparse(op)); }
+bool takes_cols_path(const sqllm_op* op) { return !takes_mfma_path(op) && cols_route(op, 1, op_has_sparse(op), op); }
 
 // ---- the launch planner --------------------------------------------------------------------------------------------------
 // ONE place decides how a group of ops is launched: route_of picks the kernel family, plan_group the geometry.  The launch
@@ -653,6 +769,11 @@ static void plan_group(const sqllm_op* ops, int n, Route route, const ScratchFac
     case kColsGroup:
     case kPerOpCols:
       for (int i = 0; i < n; ++i) make_plan_cols(&ops[i], &p->gm[i], n);
+      // (one row: the launch as a whole is cut again where its ranges cross tile boundaries -- kPerOpCols: every op is a launch of its own)
+      if (p->gm[0].batch == 1) {
+        if (route == kColsGroup) cut_ranges_one_row(ops, p->gm, n);
+        else for (int i = 0; i < n; ++i) cut_ranges_one_row(&ops[i], &p->gm[i], 1);
+      }
       break;
     case kFusedSmall: {
       // The dense ranges are ONE round of workgroups, as many as the chip holds at once: the top-X slabs (8 per op, padded)
@@ -742,6 +863,7 @@ static const Option kOptions[] = {
     {"cu_count", &Knobs::cu_count, 1 << 16},  // for GPU-less planning tests
     {"sparse_last", &Knobs::sparse_last, 1},
     {"cols_groups", &Knobs::cols_groups, 1},
+    {"cols_slot_cut", &Knobs::cols_slot_cut, 1},
     {"mfma_min_batch", &Knobs::mfma_min_batch, 0x7fffffff},  // (a huge value: never)
     {"cols_min_batch", &Knobs::cols_min_batch, 0x7fffffff},
     {"cols_max_batch", &Knobs::cols_max_batch, 0x7fffffff},

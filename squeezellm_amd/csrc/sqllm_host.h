@@ -20,6 +20,7 @@ struct Knobs {
   std::atomic<int> cu_count{0};
   std::atomic<int> sparse_last{0};
   std::atomic<int> cols_groups{1};  // 0: a group of ops never takes the column-lane kernel (as before round 3)
+  std::atomic<int> cols_slot_cut{0};  // one-row column-lane launches: 1 = re-cut every plan by executed slots alone, not only those whose ranges cross tiles (sqllm_capi.hip: cut_ranges_one_row)
   // Routing of the operators by batch size (0 = the measured defaults, which depend on the bit width, the shape and what shares
   // the launch -- sqllm_capi.hip: route_of and the rules it asks; first measured on the 13B gate/up shape, profiles/r02_batch_paths_*.txt):
   //   1 row: the fused kernel, or the column-lane kernel by launch shape (cols_pays_batch1)

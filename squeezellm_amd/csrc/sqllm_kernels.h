@@ -39,6 +39,15 @@ constexpr int kMaxBatchTile = 8;   // batch rows handled per weight pass
 constexpr int kMaxSlices = 120;    // K slices per column tile
 constexpr int kMaxContrib = 63;    // fused linear: contributions one column may receive (6-bit count under the three non-finite flags)
 
+// The decode quantum of the column-lane kernel (sqllm_kernels.hip: dense_role_cols), in ONE place for the kernel and for the planner's one-row
+// cut (sqllm_capi.hip: cut_ranges_one_row): a wave loads cols_chunk_units(bits) units per batch ("chunk") and keeps kColsChunksInFlight chunks in
+// flight; its loop runs whole rounds of them ("chunk pairs"), so a wave executes unit SLOTS in multiples of cols_wave_quantum(bits) and a
+// workgroup in multiples of cols_quantum(bits) = 64 units at 4 bits, 32 at 3 bits.  A slot without a unit costs what a live one does.
+constexpr int kColsChunksInFlight = 2;
+constexpr int cols_chunk_units(int bits) { return bits == 4 ? 4 : 2; }
+constexpr int cols_wave_quantum(int bits) { return kColsChunksInFlight * cols_chunk_units(bits); }
+constexpr int cols_quantum(int bits) { return cols_wave_quantum(bits) * kWaves; }
+
 // LDS floats of one kernel instantiation: max over roles of
 //   dense: codebooks 4 column sub-tables * lut_entries * 32 slots (2 copies of 16 lanes) PLUS the
 //          cross-wave slabs waves * BT * 64, the epilogue ticket and the fused linear's top-X

@@ -471,8 +471,8 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
   constexpr int L = F::kLut, R = F::kRows, KU = F::kK;
   constexpr int ST = cols_stage_k(BT);        // k's per stage
   constexpr int SPU = KU / ST;                // stages per unit
-  constexpr int D = BITS == 4 ? 4 : 2;        // units per load batch ("chunk")
-  constexpr int NB = 2;                       // chunks in flight
+  constexpr int D = cols_chunk_units(BITS);   // units per load batch ("chunk"): 4-bit 4, 3-bit 2
+  constexpr int NB = kColsChunksInFlight;     // chunks in flight (2; sqllm_kernels.h: the planner's one-row cut counts by NB * D * WAVES)
   constexpr int NS = D * SPU;                 // stages per chunk
   constexpr int NP = ST / 2;                  // weight pairs per stage
   constexpr int NA = BT >= 4 ? 1 : 4 / BT;    // accumulators per batch row (FMA chains in flight)
