@@ -29,6 +29,19 @@
  *
  * Shape requirements: K % 32 == 0 and N % 4 == 0 (the reference needed K % 128 == 0 and
  * N % 128 == 0: quant_cuda_kernel.cu:754,776,841-852).  qweight must be 16-byte aligned.
+ *
+ * Non-finite operands.  The reference's kernels are fp32 FMA chains into `mul`: every term of an output
+ * -- its `mul` element, each dense product lookup_table[n][idx] * vec[k], each CSR and each top-X product
+ * -- is formed once, so an output is NaN if a term is NaN or terms of both infinities meet, otherwise the
+ * infinity one of its terms has, otherwise finite; 0 x inf occurs only where the operands hold it.  Every
+ * route follows this for NaN / +-inf in vec, vals, full_rows and mul, at every K and N the shape rule
+ * admits (tests/test_gpu_nonfinite_routes.py): no kernel forms a product of its own out of a clamped
+ * re-read.  ONE narrower case: a +-inf entry of lookup_table, on the routes whose dense term is an fp32
+ * chain or the fp32 matrix instruction -- batch 1 on the fused kernel, the batch tiles, option
+ * mfma_split = 0, and the fused linears below.  There the column of that entry is non-finite in every row,
+ * and it is NaN or that infinity (the reference: that infinity, for a vec of one sign); nothing else is
+ * touched.  (A slot behind the end of a workgroup's K slice re-reads the slice's last unit against a vec of
+ * zeros: 0 x inf where that unit uses the entry.)  A NaN entry gives NaN on every route.
  */
 #ifndef SQLLM_HIP_H
 #define SQLLM_HIP_H

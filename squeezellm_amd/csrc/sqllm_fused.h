@@ -228,7 +228,8 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
   // immediate vmcnt(0)): lanes past N re-read the last valid 16 bytes of the row; steps past the
   // end of THIS workgroup's slice re-read the slice's own last unit (a cache hit -- clamping only
   // to the end of the matrix pulls other slices' rows from HBM: at 2-6 steps per wave that
-  // over-fetch was 30-100 % of the useful traffic).  Such data is never accumulated.
+  // over-fetch was 30-100 % of the useful traffic).  Such data is accumulated TIMES ZERO (the slot's vec is zeroed: step4 / step3*), which is
+  // a no-op for finite weights only -- DESIGN.md, "Clamp sites"; lanes past N compute a real sum that is never stored.
   // Addresses are a wave-uniform base plus a 32-bit byte offset (one v_mul_u32_u24 + add per load;
   // 64-bit index arithmetic cost a v_mad_i64 and a 64-bit shift-add per load in an issue-bound
   // kernel).  The C ABI rejects matrices of 4 GiB or more.

@@ -462,6 +462,9 @@ template <> struct XVec<8> {
   }
 };
 
+// one unit of zeros (32 k's): the vec of a unit that does not exist (dense_role_cols, one row)
+static __device__ __attribute__((aligned(128))) const float kColsZeroVec[32] = {};
+
 template <int BITS, int BT, int WAVES>
 __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, const uint32_t* __restrict__ q,
                                                 float* __restrict__ y, const float* __restrict__ lut, int K, int N,
@@ -493,6 +496,7 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
   ccharp xrow[BT];
 #pragma unroll
   for (int b = 0; b < BT; ++b) xrow[b] = reinterpret_cast<ccharp>(reinterpret_cast<uintptr_t>(x + (size_t)(b0 + (b < nb ? b : nb - 1)) * K));
+  const ccharp xzero = reinterpret_cast<ccharp>(reinterpret_cast<uintptr_t>(&kColsZeroVec[0]));
   uint32_t soff[D][R];
 #pragma unroll
   for (int j = 0; j < D; ++j)
@@ -568,15 +572,16 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
     for (int b = 0; b < BT; ++b)
 #pragma unroll
       for (int a = 0; a < NA; ++a) acc[b][a] = f32x2{0.f, 0.f};
-    struct St { f32x2 v[NP]; XV x[BT]; };
+    struct St { f32x2 v[NP]; XV x[BT]; bool live; };
     // issue stage st of chunk cc (held in buf): lookups + vec loads.  A unit past the wave's last one
     // (its weight words are zeros, but entry 0 of a codebook need not be) looks up the zero row -- the
     // choice is a scalar select of the v_perm selector (4-bit) or one OR per unit (3-bit) -- and
-    // re-reads the vec of the piece's last unit.
+    // re-reads the vec of the piece's last unit; its stage is not accumulated (fmas).
     auto issue = [&](const uint32_t (&buf)[D][R], int st, int cc, St& o) {
       const int j = st / SPU, sub = st % SPU;
       const int i = cc * D + j;
       const bool live = i < n_w;
+      o.live = live;
       if constexpr (BITS == 4) {
         const uint32_t lo = buf[j][0] & 0x0F0F0F0Fu, hi = (buf[j][0] >> 4) & 0x0F0F0F0Fu;
 #define SQ_L(WORD, SEL) *reinterpret_cast<const float __attribute__((address_space(3)))*>(__builtin_amdgcn_perm(WORD, lane_base, SEL))
@@ -600,7 +605,11 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
 #pragma unroll
       for (int b = 0; b < BT; ++b) o.x[b] = XVec<ST>::load(xrow[b], koff);
     };
+    // (2..8 rows) A dead unit's stage is NOT accumulated, by a wave-uniform branch: its weights are the zero row, but its vec is the
+    // re-read vec of the piece's last unit, and zero times an infinite vec element would be NaN in every column of the tile.  (The
+    // one-row loop reads zeros instead: vec_group.)
     auto fmas = [&](const St& o) {
+      if (!o.live) return;
 #pragma unroll
       for (int m = 0; m < NP; ++m)
 #pragma unroll
@@ -615,7 +624,7 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
       // (lgkmcnt(0): scalar loads return out of order) stands in front of the issue that follows the fourth:
       //     [issue s+1] [wait s] [FMAs s]   x2      [issue s+1] [wait s] [vec of group g+1] [FMAs s]      [drain] [issue s+1] [FMAs s]
       // Chunk pairs whose units all exist take the loop without the dead-unit selects; the piece's last pair(s) take the
-      // guarded copy.  The vec offset is clamped in both (the look-ahead behind the last live chunk is a dead unit).
+      // guarded copy.  A dead unit's vec is a line of zeros in the guarded copy; the unguarded one never uses a dead unit's (c_full).
       // Every column's sum runs over k in the same order and on the same accumulators as in the staged loop below.
       constexpr int GS = 32 / ST;                 // stages per vec group
       constexpr int LPS = BITS == 4 ? 2 * NP : NP;  // LDS reads per stage
@@ -643,16 +652,27 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
                 lane_or_dead | field6_x512(buf[j][0], buf[j][1], buf[j][2], sub * NP + m));
         }
       };
-      // vec of the group that starts at stage st0 of chunk cc
-      auto vec_group = [&](int st0, int cc, XV (&xg)[GS]) {
+      // vec of the group that starts at stage st0 of chunk cc.  Guarded copy: a unit past the wave's last one reads a line of ZEROS (xzero) as
+      // its vec, not the piece's last unit again -- its weights are the table's zero row, and zero times an infinite element of a re-read
+      // vec would be NaN in every column of the tile; a scalar select of the base pointer, no vector work.  The unguarded copy never
+      // requests the vec of a dead unit that is used (see c_full below) and keeps the clamp, which only keeps its addresses in bounds.
+      auto vec_group = [&](int st0, int cc, XV (&xg)[GS], auto guard) {
 #pragma unroll
         for (int g = 0; g < GS; ++g) {
           const int j = (st0 + g) / SPU, sub = (st0 + g) % SPU;
           int u = u0 + w + (cc * D + j) * WAVES;
-          if (u > u1 - 1) u = u1 - 1;
-          uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
-          asm volatile("" : "+s"(koff));
-          xg[g] = XVec<ST>::load(xrow[0], koff);
+          if constexpr (decltype(guard)::value) {
+            const bool past = u > u1 - 1;
+            if (past) u = 0;
+            uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
+            asm volatile("" : "+s"(koff));
+            xg[g] = XVec<ST>::load(past ? xzero : xrow[0], koff);
+          } else {
+            if (u > u1 - 1) u = u1 - 1;
+            uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
+            asm volatile("" : "+s"(koff));
+            xg[g] = XVec<ST>::load(xrow[0], koff);
+          }
         }
       };
       auto fma1 = [&](const V& o, const XV& xv) {
@@ -678,8 +698,8 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
               __builtin_amdgcn_s_waitcnt(0xC07F | (LPS << 8));  // lgkmcnt(LPS): everything but the lookups just issued
               if (pos == GS - 2) {
                 __builtin_amdgcn_sched_barrier(0);
-                if (st + 2 == NS) vec_group(0, c + k + 1, xs[set ^ 1]);
-                else vec_group(st + 2, c + k, xs[set ^ 1]);
+                if (st + 2 == NS) vec_group(0, c + k + 1, xs[set ^ 1], guard);
+                else vec_group(st + 2, c + k, xs[set ^ 1], guard);
               }
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -690,12 +710,19 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      vec_group(0, 0, xs[0]);
+      vec_group(0, 0, xs[0], std::true_type{});  // (the first chunk may hold dead units: once per piece)
       __builtin_amdgcn_s_waitcnt(0xC07F);  // (no scalar load in flight when the loop's counted waits begin)
       look(wbuf[0], 0, 0, va, std::true_type{});
       __builtin_amdgcn_sched_barrier(0);
+      // Chunks [0, c_full) take the unguarded copy: pairs whose units all exist AND whose last vec request -- the first group (32 k's:
+      // GU units) of the chunk behind the pair -- holds no dead unit that is used: that chunk is complete in its first group, or the
+      // wave's share ends with the pair (the request is then never used).  4-bit shares that are a whole number of pairs (every 7B /
+      // 13B / 65B range) and every 3-bit share (one unit per group) keep the parent's split.
+      constexpr int GU = 32 / KU;
+      int c_full = n_w / (NB * D) * NB;
+      if (c_full * D != n_w && c_full * D + GU > n_w) c_full -= NB;
       int c = 0;
-      for (; (c + NB) * D <= n_w; c += NB) chunk_pair(c, std::false_type{});
+      for (; c < c_full; c += NB) chunk_pair(c, std::false_type{});
       for (; c < nc; c += NB) chunk_pair(c, std::true_type{});
     } else {
     St sa, sb;

@@ -753,9 +753,9 @@ __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
     float frv[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      int k = k0 + krow + 32 * i;
-      if (k > k1 - 1) k = k1 - 1;  // clamped re-read, masked below
-      frv[i] = live ? full_rows[(size_t)k * topX + c] : 0.f;
+      const int k = k0 + krow + 32 * i;
+      const int kc = k > k1 - 1 ? k1 - 1 : k;  // clamped re-read: its weight is zero HERE and its x zero below (0 x 0; either one alone
+      frv[i] = (live && k < k1) ? full_rows[(size_t)kc * topX + c] : 0.f;  // meets an infinite row k1 - 1 / vec[k1 - 1] as 0 x inf = NaN)
     }
     const int dst = live ? full_idx[c] : 0;
     gate();  // (gated pass: the slab of full_rows is in registers, vec comes after the gate)
@@ -844,10 +844,14 @@ __device__ __forceinline__ void topx_role_xt(const float* __restrict__ xT, int l
   for (int r = 0; r < 16; ++r) p[r] = 0.f;
   for (int s = s0; s < s1; ++s) {
     const int k0 = s * kTopxRows;
+    // K % 32 == 0 (the C ABI's shape check) and krow < 32: the 32 lane rows of a step are past K together.  Such steps are NOT RUN
+    // (a workgroup-uniform trip count; whole slabs keep NI): a zero weight against the re-read xT[K - 1] is 0 x inf = NaN for an
+    // infinite vec.
+    const int ni = K - k0 >= kTopxRows ? NI : (K - k0 + 31) / 32;
 #pragma unroll 4
-    for (int i = 0; i < NI; ++i) {  // (four k's -- 20 loads -- in flight per thread: the role is a chain of round trips)
+    for (int i = 0; i < ni; ++i) {  // (four k's -- 20 loads -- in flight per thread: the role is a chain of round trips)
       const int k = k0 + krow + 32 * i;
-      const int kc = k < K ? k : K - 1;  // clamped re-read, its weight zero
+      const int kc = k < K ? k : K - 1;  // (no k >= K gets here; the clamp keeps the address in bounds whatever K is)
       const float f = (live && k < K) ? full_rows[(size_t)kc * topX + c] : 0.f;
       const float* xk = xT + ((size_t)kc << lr);
       if (rp == 2) {

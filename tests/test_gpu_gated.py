@@ -312,6 +312,62 @@ def test_gated_nonfinite_operands_follow_the_fp32_formula(gpu, bits, poison, row
     _workspaces_clean(mod)
 
 
+@gpu_test
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
+@pytest.mark.parametrize("rows", [1, 3, 8])
+@pytest.mark.parametrize("cls", ["V", "C"])
+@pytest.mark.parametrize("kind", ["dense", "hybrid"])
+@pytest.mark.parametrize("bits", [3, 4])
+def test_gated_nonfinite_operands_where_the_masked_lanes_run(gpu, bits, kind, cls, rows, dtype):
+    """K = 544, N = 132 (dead slots at the end of every slice, a partial last column tile).  The up member carries the poison class of
+    tests/nonfinite_cases.py -- V: +inf at K - 1, -inf at k = 0 and NaN at K - 32 of the shared activations, in different rows; C: +inf,
+    -inf and NaN codebook entries in three columns under strictly positive activations --, the gate is a finite dense layer.  Expected
+    pattern: the term-wise model of that module for g and for u (order-independent, proved against the fp64 oracle on the CPU), put
+    through silu(g) * u: NaN where g is NaN or -inf or u is NaN; otherwise infinite where g is +inf or u is infinite, with the sign of
+    g (of +inf) times the sign of u -- signs of finite sums from the fp64 oracle.  Not compared against another path of the library."""
+    import torch
+
+    from tests import helpers as H
+    from tests import nonfinite_cases as NC
+
+    c = NC.linear_case(bits, kind, rows, cls, NC.to_fp16 if dtype == "float16" else NC.to_bf16)
+    Kn, Nn = NC.LINEAR_SHAPE
+    gate = H.make_case(bits, Kn, Nn, seed=900 + bits)
+    bias_g = np.random.default_rng(901 + bits).normal(0, NC.LINEAR_SCALE, Nn).astype(np.float32)
+    lay_g = dict(H.to_torch(gate, gpu), bias=torch.from_numpy(bias_g.copy()).to(gpu))
+    lay_u = dict(H.to_torch(NC.writable(c["case"]), gpu), bias=torch.from_numpy(c["bias"].copy()).to(gpu))
+    pair = ((lay_g, dict(gate, bias=bias_g), None, "dense"), (lay_u, dict(c["case"], bias=c["bias"]), None, kind))
+    x = torch.from_numpy(c["x16"].copy()).to(gpu).to(getattr(torch, dtype))
+    with np.errstate(all="ignore"):
+        g, u = _sums(pair, x)
+    gn, gp, gm = NC.pattern_model(gate, c["x16"], np.broadcast_to(bias_g, (rows, Nn)), "dense")
+    un, up, um = c["nan"], c["pos"], c["neg"]
+    for model, exact in (((gn, gp, gm), g), ((un, up, um), u)):  # (the oracle's sums agree with the model's pattern: shown on the CPU as well)
+        assert all(np.array_equal(m, e) for m, e in zip(model, NC.pattern_of(exact)))
+    nan = gn | gm | un
+    infinite = (gp | up | um) & ~nan
+    with np.errstate(all="ignore"):
+        sign = np.where(gp, 1.0, np.sign(g)) * np.where(up, 1.0, np.where(um, -1.0, np.sign(u)))
+    assert (sign[infinite] != 0).all() and (cls != "C" or (infinite.sum() == 2 * rows and nan.sum() == rows))
+    want = (nan, infinite & (sign > 0), infinite & (sign < 0))
+    fin = ~(nan | infinite)
+    with np.errstate(all="ignore"):
+        gf, uf = np.where(fin, g, 0.0), np.where(fin, u, 0.0)
+    mod = _module(pair)
+    for rep in range(2):  # second call: the flags and pair words of the first must not linger
+        y = mod(x if rows > 1 else x.reshape(1, 1, Kn)).reshape(rows, Nn)
+        got_np = y.float().cpu().numpy()
+        if cls == "C":  # the dense role's narrower contract (include/sqllm_hip.h): the column of a +-inf codebook entry is NaN or that infinity
+            admit = np.isnan(got_np) & (up | um) & infinite
+            got_np = np.where(admit, np.where(sign > 0, np.inf, -np.inf), got_np)
+        got = NC.pattern_of(got_np)
+        for name, a, b in zip(("NaN", "+inf", "-inf"), got, want):
+            assert np.array_equal(a, b), (f"w{bits} {kind} class {cls} rows={rows} {dtype} call {rep}: {name} pattern differs in {int((a != b).sum())} outputs, "
+                                          f"first at (row, col) {tuple(np.argwhere(a != b)[0])}")
+        _check(y, gf, uf, dtype, where=fin)
+    _workspaces_clean(mod)
+
+
 # ---- 4. the range rule ----
 
 @gpu_test

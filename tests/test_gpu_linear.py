@@ -457,3 +457,26 @@ def test_captured_module_forwards_hold_their_kernels_only(gpu):
             torch.cuda.synchronize()
             for o, w in zip(outs, want):
                 assert torch.equal(o, w)  # (the fused linear is bit-reproducible: integer accumulation)
+
+
+@pytest.mark.parametrize("bits", [3, 4])
+@pytest.mark.parametrize("kind", ["dense", "hybrid"])
+@pytest.mark.parametrize("rows", [1, 3, 8])
+@pytest.mark.parametrize("cls", ["V", "C"])
+def test_fused_linear_nonfinite_operands_where_the_masked_lanes_run(gpu, bits, kind, rows, cls):
+    """Non-finite activations (class V: +inf at K - 1, -inf at k = 0, NaN at K - 32, in different rows) and codebook entries (class C:
+    +inf, -inf and NaN in three columns, under strictly positive activations) at K = 544, N = 132, where every slice of the dense role
+    ends in dead slots and the last column tile is partial.  The expected NaN / +inf / -inf pattern is NOT taken from another path of
+    this library: it is the term-wise model of tests/nonfinite_cases.py on the fp16-born activations plus bias, proved against the
+    fp64 oracle on the CPU (tests/test_nonfinite_cases_cpu.py).  Finite outputs within one fp16 ulp; workspace left zero."""
+    from squeezellm_amd import quant
+    from tests import nonfinite_cases as NC
+
+    def fuse(lay):
+        mod = quant.QuantLinearLUT.from_operands(lay)
+        assert quant.fuse_quant_lut(mod) == 1 and type(mod) is quant.QuantLinearLUTFused
+        return mod
+
+    mod = NC.run_linear(gpu, fuse, bits, kind, rows, cls, "float16")
+    ws = next(iter(mod._ws.values()))
+    assert int(ws.count_nonzero()) == 0, "workspace must be left zero-filled"

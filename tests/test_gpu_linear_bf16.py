@@ -452,3 +452,17 @@ def test_bf16_linear_full_size_hybrid_w4(gpu):
         torch.cuda.synchronize()
         _check_bf16(out.reshape(1, N), exact)
     assert int(ws.count_nonzero()) == 0
+
+
+@pytest.mark.parametrize("bits", [3, 4])
+@pytest.mark.parametrize("kind", ["dense", "hybrid"])
+@pytest.mark.parametrize("rows", [1, 3, 8])
+@pytest.mark.parametrize("cls", ["V", "C"])
+def test_bf16_linear_nonfinite_operands_where_the_masked_lanes_run(gpu, bits, kind, rows, cls):
+    """tests/test_gpu_linear.py's test of the same name in bfloat16: K = 544, N = 132, activations (V) or codebook entries (C) poisoned, the
+    pattern from the term-wise model of tests/nonfinite_cases.py on the bf16-born activations plus bias -- not from the operator path --,
+    finite outputs within one bf16 ulp, workspaces left zero."""
+    from tests import nonfinite_cases as NC
+
+    mod = NC.run_linear(gpu, _fused, bits, kind, rows, cls, "bfloat16")
+    _workspaces_clean(mod)

@@ -143,6 +143,8 @@ def test_route_manifest(tmp_path):
     are there when the label says so.  Rows whose scratch is allocated on the stream cannot be planned without a device: skipped, and
     counted, so that the skip cannot grow unnoticed."""
     from squeezellm_amd import build as B
+    from tests import nonfinite_cases as NC
+    from tests import test_gpu_nonfinite_routes as R
     from tests import test_gpu_precision as G
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -170,6 +172,23 @@ def test_route_manifest(tmp_path):
                     sizes = " ".join(f"{c['N']},{0 if c['vals'] is None else c['vals'].size},{0 if c['full_rows'] is None else c['full_rows'].shape[1]}" for c in ops)
                     opts = " ".join(f"{k}={v}" for k, v in route["options"].items())
                     lines.append(f"{cid} {'null' if route['entry'] == 'ws-null' else 'ws'} {bits} {K} {batch} {len(ops)} {sizes} {opts}")
+    # the shapes and batches of tests/test_gpu_nonfinite_routes.py (K = 544 / 1056, ragged N; every kind, spmv included; the batch-1
+    # column-lane route under its two cuts as well): the same launcher and fields as the label's `expect` -- an op with CSR terms
+    # alone plans as the hybrid one does.  Every label is reached at these shapes: none had to be moved to another.
+    n_precision = len(cases)
+    for route in R.NF_ROUTES:
+        if not route["plannable"]:
+            continue
+        for bits in (3, 4):
+            for kind in NC.KINDS:
+                for K, batch, widths in R.route_launches(route, bits):
+                    ops = [NC._base(bits, K, N, kind)[0] for N in widths]
+                    cid = f"c{len(cases)}"
+                    cases[cid] = (route, bits, kind, K, batch, widths)
+                    sizes = " ".join(f"{c['N']},{0 if c['vals'] is None else c['vals'].size},{0 if c['full_rows'] is None else c['full_rows'].shape[1]}" for c in ops)
+                    opts = " ".join(f"{k}={v}" for k, v in route["options"].items())
+                    lines.append(f"{cid} {'null' if route['entry'] == 'ws-null' else 'ws'} {bits} {K} {batch} {len(ops)} {sizes} {opts}")
+    assert {r["label"] for r in R.NF_ROUTES} >= {r["label"] for r in G.ALL_ROUTES} and len(cases) - n_precision > 300
     out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, (out.returncode, out.stderr[-2000:])
     seen, cur, trace = set(), None, []
@@ -184,7 +203,7 @@ def test_route_manifest(tmp_path):
         route, bits, kind, K, batch, widths = cases[cur]
         what = f"route '{route['label']}' w{bits} {kind} K={K} batch={batch} widths={widths}:\n" + "\n".join(t[:400] for t in trace)
         seen.add(cur)
-        exp = route["expect"][kind]
+        exp = route["expect"]["dense" if kind == "dense" else "hybrid"]
         names = [t.split(" ", 1)[0] for t in trace]
         dense = [_fields(t) for t in trace if t.split(" ", 1)[0] in DENSE_LAUNCHERS]
         per_op = exp["launcher"] in ("launch_batched_mfma", "launch_batched_mfma_split", "launch_batched_mfma_split_all")
@@ -200,7 +219,7 @@ def test_route_manifest(tmp_path):
             if "row_blocks" in exp:  # (LaunchArgs.row_blocks 0: the launcher's own rule, csrc/sqllm_kernels.h: mfma_row_blocks)
                 rb = int(d["row_blocks"]) or (1 if batch <= 16 else 2 if batch <= 32 else 4)
                 assert rb == exp["row_blocks"][batch], what
-        sparse_terms = kind == "hybrid"
+        sparse_terms = kind != "dense"
         assert ("prepare_small" in names) == bool(exp.get("planes") and exp["launcher"] == "launch_small_split"), what
         assert ("transpose_small" in names) == bool(exp.get("xT") and not exp.get("planes") and exp["launcher"] == "launch_small_split"), what
         assert ("split_vec" in names) == bool(exp.get("planes") and exp.get("wide")), what
