@@ -328,6 +328,79 @@ int sqllm_linear_ep_f16(const sqllm_linear_ep* e, sqllm_stream_t stream);
 int sqllm_linear_ep_bf16(const sqllm_linear_ep* e, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attention front: q_proj, k_proj, v_proj and the rotary position embedding of q and k in one kernel.
+ *
+ * For three packed layers q, k, v over the same 16-bit activations x (OT = the type of x and of all three outputs) that
+ * share K, bits and batch -- N may differ per member: grouped-query models have narrower k and v --
+ *
+ *     s_m[b,n]   = bias_m[n] + sum_k W_m[n,k] * float(x[b,k])        m in {q, k, v}; all three weight terms, as sqllm_linear_*
+ *     out_v[b,n] = OT( s_v[b,n] )
+ *     for m in {q, k}, head h, j in [0, D/2), p = positions[b]:
+ *         (lo, hi) = the pair's two columns of s_m[b, :]
+ *         out_m[b, col_lo] = OT( lo * cos[p,j] - hi * sin[p,j] )
+ *         out_m[b, col_hi] = OT( hi * cos[p,j] + lo * sin[p,j] )
+ *
+ *   - Everything is evaluated in fp32 and rounded ONCE, to nearest-even.  (The two products and the sum of an output may
+ *     or may not be contracted into a fused multiply-add; either way it is the same instruction sequence for both columns
+ *     of a pair in every run.)
+ *   - D = head_dim is even and divides N_q and N_k.  `cos` and `sin` are fp32 [n_pos, D/2] in device memory, supplied by
+ *     the caller: the kernel computes no angles, so any base or scaling rule works.  `positions` is int32 [batch] in
+ *     DEVICE memory: a captured graph follows a position the host updates in place.
+ *   - layout SQLLM_ROPE_HALF (0): col_lo = h*D + j, col_hi = h*D + j + D/2 -- the `rotate_half` form of the checkpoints the
+ *     reference loads.  SQLLM_ROPE_INTERLEAVED (1): col_lo = h*D + 2j, col_hi = h*D + 2j + 1.
+ *   - Accumulation inside and between contributions is exactly sqllm_linear_*'s.  The range rule is the bf16 rule for BOTH
+ *     output types, as in the gated and epilogue kernels: a value beyond +-131072 can rotate to a finite fp16 result, and
+ *     a clamp would return a wrong finite number.  The CSR-span corner is inherited with the gated kernels' limit: a chunk
+ *     spanning more than 1792 rows adds its values uncounted, a flag can be lost there, and the result can be finite and wrong.
+ *   - Non-finite values: what the formulas give in IEEE fp32 is the specification (inf * 0 = NaN: an infinite sum makes
+ *     both outputs of its pair NaN wherever the other factor is 0).  A positions[b] outside [0, n_pos) makes every q and k
+ *     output of row b NaN and reads nothing from the tables; v and the other rows are unaffected.
+ *   - Bit-exact equalities that follow: out_v equals sqllm_linear_bf16 (bf16) or sqllm_linear_ep_f16 with
+ *     SQLLM_ACT_IDENTITY and no residual (fp16), bit for bit; with cos = 1, sin = 0 and finite operands so do out_q and out_k.
+ *   - The result is a function of the operands alone: integer sums commute, and the rotation is computed from the same
+ *     two fp32 values whichever column finishes first.  Run to run it is bit-identical.  (Inside a contribution the order
+ *     of additions is fixed as well, as in the gated kernels.  ONE exception, theirs: top-X rows passed as full_rows -- not
+ *     folded into the CSR, as the Python module folds them -- are summed per K slice by eight waves in arrival order;
+ *     such a column's last fp32 bit, and with it an output on a rounding boundary of OT, can differ between runs.)
+ *
+ * `workspace`: sqllm_qkv_rope_workspace_bytes() bytes, 16-byte aligned -- the three members' accumulator planes
+ * (sqllm_linear_workspace_bytes each, in the order q, k, v), then one plane of 64-bit pair words [batch, N/2] for q and one
+ * for k, in which the two finished values of a pair meet -- zero-filled ONCE by the caller and left zero-filled by every
+ * launch; it serves one launch at a time.  Like every entry point: one kernel, nothing allocated, nothing retained, no
+ * synchronisation, capturable as one kernel node.  Rejected before the device is touched:
+ *   members that differ in vec / K / bits / batch, or a non-NULL mul                        SQLLM_E_GROUP
+ *   head_dim odd, < 2, or not a divisor of N_q or N_k; n_pos < 1                            SQLLM_E_SHAPE
+ *   N_q * head_dim or N_k * head_dim above 2^32; batch * N_q or batch * N_k at or above 2^31;
+ *   more than 2^20 rows (the kernel's division-free index arithmetic)                        SQLLM_E_SHAPE
+ *   a NULL descriptor, out, table, positions or workspace                                   SQLLM_E_NULL
+ *   a workspace that is not 16-byte aligned                                                 SQLLM_E_ALIGN
+ *   a layout other than 0 or 1                                                              SQLLM_E_OPTION
+ *   outputs that overlap each other or the workspace                                        SQLLM_E_SHAPE
+ *   and everything sqllm_linear_* rejects, with its codes.
+ * ------------------------------------------------------------------------------------------- */
+#define SQLLM_ROPE_HALF 0
+#define SQLLM_ROPE_INTERLEAVED 1
+typedef struct sqllm_qkv_rope {
+  sqllm_op q, k, v;        /* as for sqllm_linear_*: vec = 16-bit [batch, K], shared; mul must be NULL */
+  const float* bias_q;     /* fp32 [N_m] or NULL */
+  const float* bias_k;
+  const float* bias_v;
+  void* out_q;             /* fp16 / bf16 [batch, N_m], OVERWRITTEN */
+  void* out_k;
+  void* out_v;
+  const float* cos;        /* fp32 [n_pos, head_dim / 2], device memory */
+  const float* sin;
+  const int32_t* positions; /* int32 [batch], device memory */
+  int32_t n_pos;
+  int32_t head_dim;
+  int32_t layout;          /* SQLLM_ROPE_HALF or SQLLM_ROPE_INTERLEAVED; anything else: SQLLM_E_OPTION */
+  void* workspace;         /* sqllm_qkv_rope_workspace_bytes(), zero-filled ONCE, left zero-filled */
+} sqllm_qkv_rope;
+int64_t sqllm_qkv_rope_workspace_bytes(const sqllm_op* q, const sqllm_op* k, const sqllm_op* v); /* three accumulator planes + two pair planes */
+int sqllm_qkv_rope_f16(const sqllm_qkv_rope* r, sqllm_stream_t stream);
+int sqllm_qkv_rope_bf16(const sqllm_qkv_rope* r, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

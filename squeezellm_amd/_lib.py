@@ -62,6 +62,17 @@ class SqllmLinearEp(ctypes.Structure):
     _fields_ = [("lin", SqllmLinear), ("residual", c_void_p), ("act", c_int32)]
 
 
+ROPE_HALF, ROPE_INTERLEAVED = 0, 1  # SQLLM_ROPE_*
+
+
+class SqllmQkvRope(ctypes.Structure):
+    """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
+
+    _fields_ = [("q", SqllmOp), ("k", SqllmOp), ("v", SqllmOp), ("bias_q", c_void_p), ("bias_k", c_void_p), ("bias_v", c_void_p),
+                ("out_q", c_void_p), ("out_k", c_void_p), ("out_v", c_void_p), ("cos", c_void_p), ("sin", c_void_p),
+                ("positions", c_void_p), ("n_pos", c_int32), ("head_dim", c_int32), ("layout", c_int32), ("workspace", c_void_p)]
+
+
 class SqllmPlan(ctypes.Structure):
     """struct sqllm_plan (include/sqllm_hip.h)."""
 
@@ -143,6 +154,9 @@ SIGNATURES = {
     "sqllm_gated_bf16": [POINTER(SqllmGated), P],
     "sqllm_linear_ep_f16": [POINTER(SqllmLinearEp), P],
     "sqllm_linear_ep_bf16": [POINTER(SqllmLinearEp), P],
+    "sqllm_qkv_rope_workspace_bytes": [POINTER(SqllmOp), POINTER(SqllmOp), POINTER(SqllmOp)],
+    "sqllm_qkv_rope_f16": [POINTER(SqllmQkvRope), P],
+    "sqllm_qkv_rope_bf16": [POINTER(SqllmQkvRope), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],
@@ -191,7 +205,8 @@ def load() -> ctypes.CDLL:
         fn.argtypes = argtypes
         fn.restype = (c_char_p if name == "sqllm_error_string" else
                       ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes",
-                                               "sqllm_select_workspace_bytes", "sqllm_gated_workspace_bytes") else c_int)
+                                               "sqllm_select_workspace_bytes", "sqllm_gated_workspace_bytes",
+                                               "sqllm_qkv_rope_workspace_bytes") else c_int)
     if lib.sqllm_abi_version() != 1:
         raise RuntimeError(f"libsqllm_hip.so ABI {lib.sqllm_abi_version()} != 1 expected by this package")
     _lib = lib
@@ -239,6 +254,12 @@ def gated_workspace_bytes(N: int, batch: int = 0) -> int:
     """Bytes of zero-filled device memory one gated pair of this shape needs (no GPU needed)."""
     op = SqllmOp(N=N, batch=batch)
     return int(load().sqllm_gated_workspace_bytes(ctypes.byref(op)))
+
+
+def qkv_rope_workspace_bytes(n_q: int, n_k: int, n_v: int, batch: int = 0) -> int:
+    """Bytes of zero-filled device memory one q/k/v rotary launch of these widths needs (no GPU needed)."""
+    ops = [SqllmOp(N=n, batch=batch) for n in (n_q, n_k, n_v)]
+    return int(load().sqllm_qkv_rope_workspace_bytes(*[ctypes.byref(o) for o in ops]))
 
 
 def workspace_bytes(bits: int, K: int, N: int, batch: int, nnz: int = 0, topX: int = 0, n_ops: int = 1) -> int:

@@ -18,6 +18,7 @@
 namespace sqllm {
 hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated.hip
 hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream) = nullptr;  // set by sqllm_linear_ep.hip
+hipError_t (*g_launch_linear_qkv)(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv.hip
 }
 
 namespace sqllm_host {
@@ -1122,13 +1123,15 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
 // launch_fused hands such a launch to launch_linear_bf16 (sqllm_linear_bf16.hip), so the host layer calls the launchers it always did.
 // `pair` (sqllm_gated_*: two fused linears, gate and up): the plane of pair words; the launch then goes to the gated kernel.
 // `ep` (sqllm_linear_ep_*: one fused linear): activation code and residual; the launch then goes to the epilogue kernel.
+// `qkv` (sqllm_qkv_rope_*: three fused linears, q, k and v): the rotation's operands; the launch then goes to the qkv kernel.
 struct EpilogueArgs {
   const void* residual;  // 16-bit [batch, N] of the output's type, or null
   int act;               // SQLLM_ACT_*, validated by the caller
 };
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, const sqllm_linear* lin = nullptr, void* ws = nullptr, int64_t ws_bytes = 0,
-                                    bool ws_entry = false, bool bf16 = false, void* pair = nullptr, const EpilogueArgs* ep = nullptr) {
+                                    bool ws_entry = false, bool bf16 = false, void* pair = nullptr, const EpilogueArgs* ep = nullptr,
+                                    const sqllm::QkvRope* qkv = nullptr) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
   sqllm_op tmp[sqllm::kMaxSegments];
@@ -1188,6 +1191,10 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
         }
         if (ep) {  // (sqllm_linear_ep.hip; a missing kernel is an error here too, and the launch is not decorated either)
           e = sqllm::g_launch_linear_ep ? sqllm::g_launch_linear_ep(op->bits, a, ep->residual, ep->act, s) : hipErrorNotSupported;
+          break;
+        }
+        if (qkv) {  // (sqllm_linear_qkv.hip; a missing kernel is an error here too, and the launch is not decorated either)
+          e = sqllm::g_launch_linear_qkv ? sqllm::g_launch_linear_qkv(op->bits, a, *qkv, s) : hipErrorNotSupported;
           break;
         }
         if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: ablation bits, LDS pad, timeline buffer)
@@ -1314,6 +1321,72 @@ static int launch_linear_ep(const sqllm_linear_ep* e, sqllm_stream_t stream, boo
 
 int sqllm_linear_ep_f16(const sqllm_linear_ep* e, sqllm_stream_t stream) { return launch_linear_ep(e, stream, false); }
 int sqllm_linear_ep_bf16(const sqllm_linear_ep* e, sqllm_stream_t stream) { return launch_linear_ep(e, stream, true); }
+
+// workspace of the attention front: the three members' accumulator planes, then the pair planes [batch, N / 2] of q and of k
+static int64_t qkv_pair_bytes(const sqllm_op* m) { return align16(8ll * (m->batch <= 0 ? 1 : m->batch) * (m->N / 2)); }
+int64_t sqllm_qkv_rope_workspace_bytes(const sqllm_op* q, const sqllm_op* k, const sqllm_op* v) {
+  if (!q || !k || !v || q->N <= 0 || k->N <= 0 || v->N <= 0) return 0;
+  return sqllm_linear_workspace_bytes(q) + sqllm_linear_workspace_bytes(k) + sqllm_linear_workspace_bytes(v) + qkv_pair_bytes(q) +
+         qkv_pair_bytes(k);
+}
+
+// q, k and v as the three-op group of the fused linear (same route, plan and validation), finished by the qkv kernel
+static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool bf16) {
+  if (!r) return SQLLM_E_NULL;
+  const sqllm_op* m[3] = {&r->q, &r->k, &r->v};
+  void* const out[3] = {r->out_q, r->out_k, r->out_v};
+  for (int i = 0; i < 3; ++i) {
+    if (m[i]->mul) return SQLLM_E_GROUP;
+    if (m[i]->vec != m[0]->vec || m[i]->K != m[0]->K || m[i]->bits != m[0]->bits || m[i]->batch != m[0]->batch) return SQLLM_E_GROUP;
+  }
+  if (r->layout != SQLLM_ROPE_HALF && r->layout != SQLLM_ROPE_INTERLEAVED) return SQLLM_E_OPTION;
+  if (!r->out_q || !r->out_k || !r->out_v || !r->cos || !r->sin || !r->positions || !r->workspace) return SQLLM_E_NULL;
+  if ((reinterpret_cast<uintptr_t>(r->workspace) & 15u) != 0) return SQLLM_E_ALIGN;
+  const int D = r->head_dim;
+  if (D < 2 || (D & 1) || r->n_pos < 1) return SQLLM_E_SHAPE;
+  const int64_t rows = m[0]->batch <= 0 ? 1 : m[0]->batch;
+  // (shapes the linear's own validation is about to reject are left to it)
+  if (r->q.N > 0 && r->k.N > 0 && r->v.N > 0) {
+    for (int i = 0; i < 2; ++i) {
+      if (m[i]->N % D) return SQLLM_E_SHAPE;
+      // the finisher's arithmetic: c / D as a 32-bit multiply-high, b * N in 32 bits, b out of it by an fp32 multiply
+      if ((int64_t)m[i]->N * D > (1ll << 32) || rows * m[i]->N >= (1ll << 31) || rows > (1 << 20)) return SQLLM_E_SHAPE;
+    }
+    const int64_t ws_bytes = sqllm_qkv_rope_workspace_bytes(&r->q, &r->k, &r->v);
+    const uintptr_t w0 = reinterpret_cast<uintptr_t>(r->workspace);
+    for (int i = 0; i < 3; ++i) {
+      const uintptr_t a0 = reinterpret_cast<uintptr_t>(out[i]), a1 = a0 + 2u * (uintptr_t)rows * (uintptr_t)m[i]->N;
+      if (a0 < w0 + (uintptr_t)ws_bytes && w0 < a1) return SQLLM_E_SHAPE;
+      for (int j = 0; j < i; ++j) {
+        const uintptr_t b0 = reinterpret_cast<uintptr_t>(out[j]), b1 = b0 + 2u * (uintptr_t)rows * (uintptr_t)m[j]->N;
+        if (a0 < b1 && b0 < a1) return SQLLM_E_SHAPE;
+      }
+    }
+  }
+  sqllm_linear lin[3];
+  char* ws = static_cast<char*>(r->workspace);
+  const float* bias[3] = {r->bias_q, r->bias_k, r->bias_v};
+  for (int i = 0; i < 3; ++i) {
+    lin[i].op = *m[i];
+    lin[i].op.mul = static_cast<float*>(out[i]);  // (what the linear's validation and fill_args read as the output)
+    lin[i].bias = bias[i];
+    lin[i].workspace = ws;
+    ws += sqllm_linear_workspace_bytes(m[i]);
+  }
+  sqllm::QkvRope qr;
+  qr.pair_q = ws;
+  qr.pair_k = ws + qkv_pair_bytes(&r->q);
+  qr.cos = r->cos;
+  qr.sin = r->sin;
+  qr.positions = r->positions;
+  qr.n_pos = r->n_pos;
+  qr.head_dim = D;
+  qr.interleaved = r->layout == SQLLM_ROPE_INTERLEAVED;
+  return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr);
+}
+
+int sqllm_qkv_rope_f16(const sqllm_qkv_rope* r, sqllm_stream_t stream) { return launch_qkv_rope(r, stream, false); }
+int sqllm_qkv_rope_bf16(const sqllm_qkv_rope* r, sqllm_stream_t stream) { return launch_qkv_rope(r, stream, true); }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

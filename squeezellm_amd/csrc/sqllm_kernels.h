@@ -147,6 +147,18 @@ extern hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* 
 // the fused linear with an epilogue (sqllm_linear_ep_f16 / _bf16): a fused-linear launch of exactly one segment on the kernel of
 // sqllm_linear_ep.hip; `residual`: 16-bit [batch, N] of the output's type or null, `act`: SQLLM_ACT_*.  A hook, as above.
 extern hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream);
+// the attention front (sqllm_qkv_rope_f16 / _bf16): a fused-linear launch of exactly three segments, q, k and v, on the kernel of
+// sqllm_linear_qkv.hip, which rotates q and k by the rotary position embedding as their columns finish.  A hook, as above.
+struct QkvRope {
+  void* pair_q;          // plane of pair words [batch, N_q / 2], all zero between launches
+  void* pair_k;          // ... [batch, N_k / 2]
+  const float* cos;      // fp32 [n_pos, head_dim / 2], device memory
+  const float* sin;
+  const int* positions;  // int32 [batch], device memory
+  int n_pos, head_dim;
+  bool interleaved;      // SQLLM_ROPE_INTERLEAVED (partner next door) instead of SQLLM_ROPE_HALF (partner head_dim / 2 away)
+};
+extern hipError_t (*g_launch_linear_qkv)(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

@@ -1,0 +1,222 @@
+// sqllm_linear_qkv.hip -- the attention front as ONE kernel (include/sqllm_hip.h: sqllm_qkv_rope_f16 / _bf16):
+//
+//     s_m[b, n]  = bias_m[n] + sum_k W_m[n, k] * float(x[b, k])                   m in {q, k, v}
+//     out_v[b, n] = OT( s_v[b, n] )
+//     for m in {q, k}, head h, j in [0, D/2), p = positions[b], (lo, hi) = the pair's two columns of s_m[b, :]:
+//         out_m[b, col_lo] = OT( lo * cos[p, j] - hi * sin[p, j] )
+//         out_m[b, col_hi] = OT( hi * cos[p, j] + lo * sin[p, j] )
+//
+// fp32 throughout, rounded once to OT = the type of x (fp16 or bf16).  The kernel is sqllm_linear_gated.hip's skeleton
+// (pick_segment, role dispatch, dense_role with the top-X rows folded in, csr_role, topx_role, AT = the 64-bit completion
+// word) launched on a group of exactly three segments, q, k and v: route, planner, geometry and validation are
+// kFusedLinear's three-op group.  What is its own is carried by the finishing policy (RopeFinish below):
+//   * the range rule is the bf16 one for BOTH output types (a value beyond +-2^17 can rotate to a finite fp16 result);
+//   * the finisher of a column of v stores, as the epilogue kernel's identity does.  The finisher of a column of q or k
+//     forms its fp32 value, re-zeroes its accumulator word, and does ONE returning 64-bit exchange on the PAIR WORD of
+//     (b, h, j) -- a plane of [batch, N / 2] words per rotated member behind the accumulator planes, all zero between
+//     launches -- depositing kPairTag | bits(v).  An old value of zero: it is the first of the two and leaves.  Otherwise
+//     the old value is its partner column's result: it reads positions[b] and the two table entries, computes BOTH
+//     outputs, stores both and exchanges the pair word back to zero.
+// Gated pairs a column with the same column of the other member; rotary pairs it with another column of the same member:
+// the two finishers may be lanes of one wave (the interleaved layout, or D / 2 < 64) or workgroups apart.  Either way both
+// values travel inside returning agent-scope atomics on one address: no fence, nobody waits, and the rotation sees the
+// same two fp32 values whichever column finishes first.
+//
+// Registers.  Everything the rotation needs beyond the member index -- the pair planes, the tables, positions, the
+// divisors -- stays in the kernel-argument segment until a finisher asks for it (rope_args): held in SGPRs from the
+// kernel's start, those 20 dwords pushed the 2-row and 8-row tiles past their VGPR steps through SGPR parking.  And a
+// finisher divides nothing: c / D is a multiply-high by a reciprocal the host supplies, the batch row comes back out of
+// at - c = b * N by an fp32 multiply (exact for the sizes the host admits), so the tail unrolled once per batch row of a
+// tile is a dozen instructions.
+#include <stddef.h>
+
+#include "sqllm_fused.h"
+
+namespace sqllm {
+
+constexpr u64 kPairTag = 1ull << 32;  // a deposited value is never the empty word, whatever its bits
+
+// by-value kernel argument behind GroupArgs; read through rope_args() only
+struct RopeArgs {
+  u64* pair_q;           // [batch, N_q / 2] pair words, all zero between launches
+  u64* pair_k;           // [batch, N_k / 2]
+  const float* cos;      // fp32 [n_pos, D / 2]
+  const float* sin;
+  const int* positions;  // int32 [batch]
+  int n_pos;
+  int half;              // D / 2
+  uint32_t d_magic;      // floor(2^32 / D) + 1: c / D == mulhi(c, d_magic) for c * D < 2^32 (the host checks N * D)
+  int interleaved;       // 0: partner D / 2 away, 1: partner next door
+  float inv_nq, inv_nk;  // 1 / N of the member, fp32
+};
+// the kernel's explicit arguments as the ABI lays them out (natural alignment, in order)
+struct QkvKernArgs {
+  const void* x;
+  GroupArgs ga;
+  RopeArgs ra;
+};
+constexpr unsigned kRopeArgsOffset = offsetof(QkvKernArgs, ra);
+static_assert(kRopeArgsOffset == sizeof(void*) + sizeof(GroupArgs) && sizeof(RopeArgs) == 64, "the descriptor block ends on the next argument's alignment");
+
+// The rotary arguments, from the kernel-argument segment, no earlier than HERE: the empty asm statement hides where the
+// address came from, so the scalar loads through it cannot be scheduled at the kernel's start and held across the walk.
+// (The cast back names the constant address space: the loads stay scalar.)
+__device__ __forceinline__ const __attribute__((address_space(4))) RopeArgs* rope_args() {
+  uintptr_t p = reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr()) + kRopeArgsOffset;
+  asm volatile("" : "+s"(p));
+  return reinterpret_cast<const __attribute__((address_space(4))) RopeArgs*>(p);
+}
+
+// Column c of a rotated member: the pair's slot in a row of the pair plane, h * D / 2 + j; *is_hi: c is the pair's upper
+// column; *j: the table column; *dist: how far apart the two columns are.  No division: c / D is a multiply-high.
+__device__ __forceinline__ uint32_t locate(const __attribute__((address_space(4))) RopeArgs* ra, int c, bool* is_hi, int* j, int* dist) {
+  const int half = ra->half;
+  const uint32_t h = __umulhi((uint32_t)c, ra->d_magic);
+  const int r = c - (int)h * 2 * half;  // c % D
+  if (ra->interleaved) {
+    *is_hi = c & 1;
+    *j = r >> 1;
+    *dist = 1;
+  } else {
+    *is_hi = r >= half;
+    *j = *is_hi ? r - half : r;
+    *dist = half;
+  }
+  return h * (uint32_t)half + (uint32_t)*j;
+}
+
+// OT: the element type of the outputs; the contributions follow FixRange<__bf16> whatever OT is
+template <typename OT>
+struct RopeFinish {
+  int member;  // this workgroup's segment: 0 = q, 1 = k, 2 = v
+  static constexpr bool kOrderedCsr = true;  // a CSR chunk's parts of a row meet in wave order: the same fp32 value in every run
+  template <typename XT> struct Range { using type = __bf16; };
+  template <typename RT>
+  __device__ __forceinline__ void done(const Segment& sg, u64* word, u64 total, unsigned target, size_t at, int c) const {
+    float v;
+    if (!column_value(sg, total, target, c, &v)) return;
+    atomicExch(word, 0ull);  // result unused: a plain atomic store
+    OT* out = reinterpret_cast<OT*>(sg.out16);
+    if (member == 2) {
+      out[at] = (OT)v;
+      return;
+    }
+    const auto* ra = rope_args();
+    bool is_hi;
+    int j, dist;
+    const uint32_t bn = (uint32_t)(at - (size_t)c);  // b * N (N is even)
+    u64* pw = (member ? ra->pair_k : ra->pair_q) + ((bn >> 1) + locate(ra, c, &is_hi, &j, &dist));
+    const u64 mine = kPairTag | (u64)__builtin_bit_cast(uint32_t, v);
+    const u64 other = __hip_atomic_exchange(SQLLM_GLOBAL(u64, pw), mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (other == 0) return;  // the first of the two: the partner column's finisher completes the pair
+    const float o = __builtin_bit_cast(float, (uint32_t)other);
+    // (located a second time, from a copy of c the compiler cannot see through: four VALU instructions in the one finisher
+    // of a pair instead of three registers held by every finisher across its exchange)
+    int c2 = c;
+    asm volatile("" : "+v"(c2));
+    locate(ra, c2, &is_hi, &j, &dist);
+    const float lo = is_hi ? o : v, hi = is_hi ? v : o;
+    const int b = (int)((float)bn * (member ? ra->inv_nk : ra->inv_nq) + 0.5f);
+    const int p = ra->positions[b];
+    float cs = __builtin_nanf(""), sn = cs;  // a position outside the tables: NaN, and nothing is read
+    if ((unsigned)p < (unsigned)ra->n_pos) {
+      const size_t t = (size_t)p * ra->half + j;
+      cs = ra->cos[t];
+      sn = ra->sin[t];
+    }
+    const size_t at_lo = is_hi ? at - dist : at;
+    out[at_lo] = (OT)(lo * cs - hi * sn);
+    out[at_lo + dist] = (OT)(hi * cs + lo * sn);
+    __hip_atomic_exchange(SQLLM_GLOBAL(u64, pw), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (result unused)
+  }
+};
+
+template <int BITS, int BT, typename OT>
+__global__ void __launch_bounds__(kWaves * 64, fused_min_waves(BITS, BT, 0))
+sqllm_linear_qkv_kernel(const void* xv, const GroupArgs ga, const RopeArgs ra /* read through rope_args() */) {
+  constexpr int WAVES = kWaves;
+  constexpr bool HALF = fused_half_stages(BITS, BT);
+  constexpr int T = WAVES * 64;
+  constexpr int kLds = lds_floats(Fmt<BITS>::kLut, WAVES, BT, BITS == 3 && BT == 1 && SQLLM_HALF_STAGES && SQLLM_PAIR3);
+  __shared__ __attribute__((aligned(16))) float lds[kLds];
+  using XT = OT;
+  using AT = u64;
+  using FIN = RopeFinish<OT>;
+  const XT* x = reinterpret_cast<const XT*>(xv);
+
+  // one round of scalar loads for vec's address, the block table and segment 0 (see sqllm_fused_matvec)
+  Segment sg;
+  const int bid = pick_segment(ga, x, sg);
+  const KernelGeom& gm = sg.gm;
+  const int b0 = blockIdx.y * BT;
+  int nb = gm.batch - b0;
+  if (nb > BT) nb = BT;
+  // (three segments: the host launches nothing else here)
+  const FIN fin{(int)blockIdx.x >= ga.block0[2] ? 2 : (int)blockIdx.x >= ga.block0[1] ? 1 : 0};
+
+  // role by block id within the segment: [sparse | pad | dense] or, with sparse_last, [dense | sparse]
+  int d, sp;
+  if (gm.sparse_last & 1) {
+    d = bid;
+    sp = bid - gm.dense_blocks;
+  } else {
+    d = bid - gm.dense_block0;
+    sp = bid < gm.dense_block0 ? bid : -1;
+  }
+  if (d >= 0 && d < gm.dense_blocks) {
+    dense_role<BITS, BT, WAVES, 0, XT, HALF, false, FIN>(x, reinterpret_cast<const u32x4*>(sg.q), sg.y, sg.lut, gm.K, gm.N, b0, nb, d,
+                                                         gm.col_tiles, gm.units_total, gm.units_per_wg, lds, sg, &sg, fin);
+  } else if (sp >= 0 && sp < gm.csr_blocks) {
+    if (gm.dense_prio == 2) __builtin_amdgcn_s_setprio(1);
+    csr_role<T, BT, XT, AT, false, false, NoGate, kCsrChunk, FIN>(x, reinterpret_cast<AT*>(sg.y), sg.rows, sg.cols, sg.vals, gm.nnz, gm.K, gm.N,
+                                                                  b0, nb, sp, lds, &sg, gm.sparse_last >> 1, nullptr, 0, nullptr, NoGate(), fin);
+  } else if (sp >= gm.csr_blocks && sp < gm.csr_blocks + gm.topx_blocks) {
+    // (never taken when the plan folds the top-X rows into the dense tiles)
+    if (gm.dense_prio == 2) __builtin_amdgcn_s_setprio(1);
+    topx_role<T, XT, AT, false, NoGate, BT, FIN>(x, reinterpret_cast<AT*>(sg.y), sg.full_rows, sg.full_idx, gm.topX, gm.K, gm.N, b0, nb,
+                                                 sp - gm.csr_blocks, lds);
+  }
+}
+
+template <int BITS, int BT, typename OT>
+static hipError_t launch_qkv_inst(const LaunchArgs& a, const RopeArgs& ra, hipStream_t stream) {
+  const int batch = a.ga.seg[0].gm.batch;
+  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
+  auto kern = sqllm_linear_qkv_kernel<BITS, BT, OT>;
+  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, ra);
+}
+
+template <int BITS, typename OT>
+static hipError_t launch_qkv_bits(const LaunchArgs& a, const RopeArgs& ra, hipStream_t stream) {
+  switch (batch_tile(a.ga.seg[0].gm.batch)) {
+    case 1: return launch_qkv_inst<BITS, 1, OT>(a, ra, stream);
+    case 2: return launch_qkv_inst<BITS, 2, OT>(a, ra, stream);
+    case 4: return launch_qkv_inst<BITS, 4, OT>(a, ra, stream);
+    default: return launch_qkv_inst<BITS, 8, OT>(a, ra, stream);
+  }
+}
+
+// q, k and v (segments 0, 1, 2) over one 16-bit vec (a.ga; a.bf16: its type); r: the host's description of the rotation
+static hipError_t launch_linear_qkv(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream) {
+  if (a.ga.n_seg != 3 || !r.pair_q || !r.pair_k || !r.cos || !r.sin || !r.positions || r.head_dim < 2 || (r.head_dim & 1))
+    return hipErrorInvalidValue;
+  RopeArgs ra;
+  ra.pair_q = static_cast<u64*>(r.pair_q);
+  ra.pair_k = static_cast<u64*>(r.pair_k);
+  ra.cos = r.cos;
+  ra.sin = r.sin;
+  ra.positions = r.positions;
+  ra.n_pos = r.n_pos;
+  ra.half = r.head_dim / 2;
+  ra.d_magic = (uint32_t)((1ull << 32) / (uint32_t)r.head_dim) + 1u;
+  ra.interleaved = r.interleaved ? 1 : 0;
+  ra.inv_nq = 1.f / (float)a.ga.seg[0].gm.N;
+  ra.inv_nk = 1.f / (float)a.ga.seg[1].gm.N;
+  if (a.bf16) return bits == 4 ? launch_qkv_bits<4, __bf16>(a, ra, stream) : launch_qkv_bits<3, __bf16>(a, ra, stream);
+  return bits == 4 ? launch_qkv_bits<4, _Float16>(a, ra, stream) : launch_qkv_bits<3, _Float16>(a, ra, stream);
+}
+
+// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
+static const bool g_qkv_registered = (g_launch_linear_qkv = launch_linear_qkv, true);
+
+}  // namespace sqllm

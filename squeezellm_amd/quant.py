@@ -485,9 +485,11 @@ class QuantGatedLUTFused(nn.Module):
     tensors return F.silu(gate(x)) * up(x); with `gate.dense_min_rows` set, a call of at least that many rows sends both
     members down their dense route and applies the activation in torch (in fp32, rounded once).  `last_route`: "gated" / "dense" / "fallback".
 
-    Speed: NOT MEASURED yet.  tools/gated_bench.py compares this class with two fused modules + torch silu / mul and with one
-    grouped launch + torch, graph-replayed; it has not been run, and DESIGN.md 4.4 has no table for it.  Expected only: two
-    torch launches and two [rows, N] temporaries fewer, one more atomic round trip per column."""
+    Speed, graph-replayed on an MI355X (tools/gated_bench.py, table in DESIGN.md 4.4, raw output profiles/gated_linear.txt; 7B
+    and 13B gate / up pairs, w3 / w4, s0 / s45 + top-10, fp16 / bf16): against two fused modules + torch silu / mul, 6 - 23 us
+    less per pair on all 48 points (-41 .. -3.5 %).  Against one grouped launch + torch: 3.0 - 6.2 us less at 1 row, 0.9 - 3.7 us
+    less at 4 rows; at 8 rows NOT faster on 11 of 16 points (every s45 + top-10 point, +2.0 .. +3.7 %; three s0 points inside
+    the spread)."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
 
@@ -580,6 +582,189 @@ def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_pr
         m.forward = (lambda gated, d: lambda x: d(gated(x)))(gated, d)
         if isinstance(d, QuantLinearLUTFused):  # `residual + down(gated(x))` with the add inside down's kernel
             m.__dict__["forward_residual"] = (lambda gated, d: lambda x, residual: d(gated(x), residual=residual))(gated, d)
+        n += 1
+    return n
+
+
+_QKV_ENTRY = {torch.float16: "sqllm_qkv_rope_f16", torch.bfloat16: "sqllm_qkv_rope_bf16"}
+_ROPE_LAYOUT = {"half": _lib.ROPE_HALF, "interleaved": _lib.ROPE_INTERLEAVED}
+
+
+def rope_tables(head_dim: int, n_pos: int, theta: float = 10000.0, device=None):
+    """fp32 (cos, sin) of shape [n_pos, head_dim / 2] for QuantQKVRopeFused: angle[p, j] = p * theta ** (-2 j / head_dim),
+    computed in fp64 and rounded once.  (The kernel computes no angles: tables built by any other base or scaling rule
+    serve as well.)"""
+    if head_dim < 2 or head_dim % 2 or n_pos < 1:
+        raise ValueError(f"head_dim must be even and >= 2 and n_pos >= 1, got {head_dim}, {n_pos}")
+    j = torch.arange(head_dim // 2, dtype=torch.float64)
+    inv_freq = torch.tensor(float(theta), dtype=torch.float64) ** (-2.0 * j / head_dim)
+    ang = torch.arange(n_pos, dtype=torch.float64)[:, None] * inv_freq[None, :]
+    return ang.cos().float().to(device), ang.sin().float().to(device)
+
+
+def _torch_rope(s: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, head_dim: int, layout: str, dtype) -> torch.Tensor:
+    """The rotation of the kernel (include/sqllm_hip.h, sqllm_qkv_rope) on sums s [rows, N] in torch: fp32, rounded once to
+    `dtype`; a position outside the tables makes its row NaN."""
+    rows, N = s.shape
+    half = head_dim // 2
+    p = positions.long()
+    ok = (p >= 0) & (p < cos.shape[0])
+    pc = torch.where(ok, p, torch.zeros_like(p))
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=s.device)
+    c = torch.where(ok[:, None], cos.float()[pc], nan)[:, None, :]  # [rows, 1, half]
+    sn = torch.where(ok[:, None], sin.float()[pc], nan)[:, None, :]
+    v = s.float().reshape(rows, N // head_dim, head_dim)
+    if layout == "half":
+        lo, hi = v[..., :half], v[..., half:]
+        out = torch.cat((lo * c - hi * sn, hi * c + lo * sn), dim=-1)
+    else:
+        lo, hi = v[..., 0::2], v[..., 1::2]
+        out = torch.stack((lo * c - hi * sn, hi * c + lo * sn), dim=-1)
+    return out.reshape(rows, N).to(dtype)
+
+
+class QuantQKVRopeFused(nn.Module):
+    """q_proj, k_proj, v_proj and the rotary position embedding of q and k for fp16 and bf16 GPU activations as ONE kernel
+    (sqllm_qkv_rope_f16 / _bf16) instead of one grouped launch and the string of torch element-wise kernels behind it (the
+    gather of cos and sin, rotate_half, two multiplies and an add, for q and again for k): the three sums are formed as in
+    QuantLinearLUTFused, q and k are rotated in fp32 and everything is rounded once to the activations' type
+    (include/sqllm_hip.h, sqllm_qkv_rope: semantics, layouts, non-finite values, and the range rule -- a partial sum beyond
+    +-131072 in magnitude makes that sum +-inf for fp16 as well as bf16).
+
+    `q`, `k`, `v` are three QuantLinearLUT / QuantLinearLUTFused modules of equal infeatures and bit width (k and v may be
+    narrower than q), held BY REFERENCE: this module owns no buffers, no parameters and no state-dict keys.  `head_dim` is even
+    and divides q's and k's outfeatures; `layout` is "half" (the rotate_half form: partner head_dim / 2 away) or "interleaved"
+    (partner next door).  It keeps one descriptor per (device, stream) and one workspace by the rules of
+    QuantLinearLUTFused._workspace.
+
+    forward(x, positions, cos, sin) -> (q, k, v), each [..., N_m].  `cos`, `sin`: fp32 [n_pos, head_dim / 2] on x's device
+    (rope_tables, or the caller's own).  `positions`: one per row of x, an int32 tensor on x's device, used WITHOUT a copy -- a
+    captured graph follows a position updated in place; int64 is accepted and converted, which costs a kernel (and a captured
+    graph then follows the int64 tensor through that kernel).  A position outside [0, n_pos) makes that row of q and k NaN.
+    Other dtypes and CPU tensors, and calls of at least `q.dense_min_rows` rows (the members' dense route), compute the same
+    formulas in torch, in fp32 with one rounding.  `last_route`: "qkv_rope" / "dense" / "fallback".
+
+    Speed, graph-replayed on an MI355X (tools/qkv_rope_bench.py, table in DESIGN.md 4.4, raw output profiles/qkv_rope_bench.txt;
+    K = 4096, head_dim 128, 3 x 4096 and 4096 + 2 x 1024, w3 / w4, s0 / s45 + top-10, fp16 / bf16, 1 / 4 / 16 rows): 28 - 40 us
+    less per layer than one grouped launch + the rotary step in torch (-79 .. -34 %), 37 - 75 us less than three fused modules +
+    the same step; faster on all 48 points."""
+
+    GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
+
+    def __init__(self, q: QuantLinearLUT, k: QuantLinearLUT, v: QuantLinearLUT, head_dim: int, layout: str = "half"):
+        super().__init__()
+        for name, m in (("q", q), ("k", k), ("v", v)):
+            if not isinstance(m, QuantLinearLUT):
+                raise TypeError(f"{name} must be a QuantLinearLUT or QuantLinearLUTFused, got {type(m).__name__}")
+            if (m.infeatures, m.bits) != (q.infeatures, q.bits):
+                raise ValueError(f"q, k and v must share infeatures and bit width: {name} has {m.infeatures} / w{m.bits} against "
+                                 f"{q.infeatures} / w{q.bits}")
+        if layout not in _ROPE_LAYOUT:
+            raise ValueError(f"layout must be 'half' or 'interleaved', got {layout!r}")
+        head_dim = int(head_dim)
+        if head_dim < 2 or head_dim % 2 or q.outfeatures % head_dim or k.outfeatures % head_dim:
+            raise ValueError(f"head_dim must be even, >= 2 and divide the widths of q and k ({q.outfeatures}, {k.outfeatures}), got {head_dim}")
+        # by reference: nn.Module.__setattr__ would register them as children (and their buffers under this module's keys)
+        self.__dict__["q"], self.__dict__["k"], self.__dict__["v"] = q, k, v
+        self.head_dim, self.layout = head_dim, layout
+
+    @property
+    def last_route(self):
+        """"qkv_rope", "dense" or "fallback": the way the most recent forward went (None before the first)."""
+        return self.__dict__.get("_last_route")
+
+    def _descriptor(self, dev: int, stream: int):
+        """The sqllm_qkv_rope of (device, stream): the members' own pre-marshalled descriptors (QuantLinearLUTFused._descriptor)
+        copied side by side, rebuilt when any of them is."""
+        ls = tuple(QuantLinearLUTFused._descriptor(m, dev, stream) for m in (self.q, self.k, self.v))
+        cache = self.__dict__.setdefault("_desc", {})
+        hit = cache.get((dev, stream))
+        if hit is not None and all(a is b[0] for a, b in zip(hit[0], ls)):
+            return hit[1]
+        r = _lib.SqllmQkvRope()
+        r.q, r.k, r.v = ls[0][0].op, ls[1][0].op, ls[2][0].op  # (copies)
+        r.q.mul = r.k.mul = r.v.mul = None
+        r.bias_q, r.bias_k, r.bias_v = ls[0][0].bias, ls[1][0].bias, ls[2][0].bias
+        entry = (r, ctypes.byref(r), ls)  # (the members' entries keep the folded CSRs alive)
+        cache[(dev, stream)] = (tuple(l[0] for l in ls), entry)
+        return entry
+
+    def forward(self, x: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor):
+        q, k, v = self.q, self.k, self.v
+        K, D, half = q.infeatures, self.head_dim, self.head_dim // 2
+        if x.shape[-1] != K:
+            raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
+        x2 = x if x.dim() == 2 else x.reshape(-1, K)
+        rows = x2.shape[0]
+        for name, t in (("cos", cos), ("sin", sin)):
+            if t.dim() != 2 or t.shape[1] != half or t.shape[0] < 1 or t.shape != cos.shape or t.device != x.device:
+                raise ValueError(f"{name} must be [n_pos, {half}] on {x.device}, got {tuple(t.shape)} on {t.device}")
+        if positions.dtype not in (torch.int32, torch.int64) or positions.numel() != rows or positions.device != x.device:
+            raise ValueError(f"positions must be {rows} int32 (or int64) values on {x.device}")
+        lead = x.shape[:-1]
+        dense_min_rows = getattr(q, "dense_min_rows", None)
+        kernel = x.dtype in _QKV_ENTRY and x.is_cuda
+        if not kernel or (dense_min_rows is not None and rows >= dense_min_rows):
+            pos = positions.reshape(-1)
+            if kernel:
+                self.__dict__["_last_route"] = "dense"
+                if not x2.is_contiguous():
+                    x2 = x2.contiguous()
+                # fp32 from end to end, as the epilogue's dense route: the ONE rounding of the kernel is the only one here too
+                sums = []
+                for m in (q, k, v):
+                    s = torch.nn.functional.linear(x2.float(), m.dequantize(torch.float32))
+                    sums.append(s if m.bias is None else s + m.bias)
+            else:
+                self.__dict__["_last_route"] = "fallback"
+                sums = [QuantLinearLUT.forward(m, x2) for m in (q, k, v)]
+            oq = _torch_rope(sums[0], pos, cos, sin, D, self.layout, x.dtype)
+            ok = _torch_rope(sums[1], pos, cos, sin, D, self.layout, x.dtype)
+            return oq.reshape(*lead, -1), ok.reshape(*lead, -1), sums[2].to(x.dtype).reshape(*lead, -1)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or not cos.is_contiguous() or not sin.is_contiguous():
+            raise ValueError("cos and sin must be contiguous fp32 tensors")
+        pos = positions.reshape(-1)
+        if pos.dtype != torch.int32:
+            pos = pos.to(torch.int32)  # (a kernel)
+        if not pos.is_contiguous():
+            pos = pos.contiguous()
+        self.__dict__["_last_route"] = "qkv_rope"
+        dev = x.get_device()
+        outs = [torch.empty((rows, m.outfeatures), dtype=x.dtype, device=x.device) for m in (q, k, v)]
+        r, ref, _keep = self._descriptor(dev, quant_cuda._raw_stream(dev))
+        batch = 0 if rows == 1 else rows
+        ws = _workspace_of(self.__dict__.setdefault("_ws", {}),
+                           _lib.qkv_rope_workspace_bytes(q.outfeatures, k.outfeatures, v.outfeatures, batch), q.qweight.device,
+                           self.GRAPH_WS_MAX_BYTES)
+        r.q.batch = r.k.batch = r.v.batch = batch
+        r.q.vec = r.k.vec = r.v.vec = x2.data_ptr()
+        r.out_q, r.out_k, r.out_v = outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr()
+        r.cos, r.sin, r.positions = cos.data_ptr(), sin.data_ptr(), pos.data_ptr()
+        r.n_pos, r.head_dim, r.layout = cos.shape[0], D, _ROPE_LAYOUT[self.layout]
+        r.workspace = ws.data_ptr()
+        quant_cuda._launch(quant_cuda._fn(_QKV_ENTRY[x.dtype]), dev, (ref,))
+        return tuple(o.reshape(*lead, -1) for o in outs)
+
+
+def fuse_qkv_rope(module: nn.Module, q: str = "q_proj", k: str = "k_proj", v: str = "v_proj", head_dim=None) -> int:
+    """Give every submodule of `module` that has the attributes `q`, `k` and `v` -- three quantised layers of equal
+    infeatures and bit width -- an attribute `qkv_rope`, a QuantQKVRopeFused over them (not a child: the module tree, the
+    state dict and every `forward` stay as they are; an attention forward calls `self.qkv_rope(x, positions, cos, sin)`
+    where it called the three projections and the rotary step).  `head_dim`: the submodule's own `head_dim`
+    attribute where None.  Submodules without one, or whose widths it does not divide, are left alone.  Returns the count."""
+    n = 0
+    for m in module.modules():
+        mq, mk, mv = getattr(m, q, None), getattr(m, k, None), getattr(m, v, None)
+        if not all(isinstance(t, QuantLinearLUT) for t in (mq, mk, mv)):
+            continue
+        if any((t.infeatures, t.bits) != (mq.infeatures, mq.bits) for t in (mk, mv)):
+            continue
+        d = head_dim if head_dim is not None else getattr(m, "head_dim", None)
+        if not isinstance(d, int) or d < 2 or d % 2 or mq.outfeatures % d or mk.outfeatures % d:
+            continue
+        m.__dict__["qkv_rope"] = QuantQKVRopeFused(mq, mk, mv, d)
         n += 1
     return n
 
