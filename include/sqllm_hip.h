@@ -401,6 +401,52 @@ int sqllm_qkv_rope_f16(const sqllm_qkv_rope* r, sqllm_stream_t stream);
 int sqllm_qkv_rope_bf16(const sqllm_qkv_rope* r, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Norm fronts: the RMSNorm in front of gate/up and in front of q/k/v, as a prologue of those two kernels.
+ *
+ * For 16-bit activations x [batch, K] (fp16 or bf16, OT = its type) -- the UN-normalised hidden state --, a norm weight
+ * g [K] of the same 16-bit type and eps:
+ *
+ *     ms[b]   = (1/K) * sum_k float(x[b,k])^2
+ *     r[b]    = 1.0f / sqrtf(ms[b] + eps)                  fp32, correctly rounded divide and square root
+ *     xn[b,k] = float(x[b,k]) * float(g[k]) * r[b]         fp32 (the two products in this order), NEVER rounded to 16 bits
+ *
+ * and the kernel is exactly sqllm_gated_* / sqllm_qkv_rope_* with float(x[b,k]) replaced by xn[b,k] in all three weight
+ * terms: dense, CSR and top-X (folded into the CSR or passed as full_rows).
+ *
+ *   - The sums that enter the fixed-point words are sums over xn.  The range rule (+-131072, the bf16 rule), the flags,
+ *     the 63-contribution limit, the ordered CSR adds, the finishers and every documented corner of the parent entry are
+ *     unchanged: what overflows, and what the bias meets, is the normalised sum.
+ *   - ms[b] is summed in fp32 in ONE fixed order, the same in every workgroup of every launch, so every column of a row
+ *     sees the same r[b] bits: thread t of 512 adds the squares (exact in fp32) of elements [8t, 8t + 8) of every round of
+ *     4096 elements, in ascending k, into one accumulator; the 64 lanes of a wave meet in a butterfly (lane distances 32,
+ *     16, 8, 4, 2, 1); the eight wave sums are added in wave order; the total is divided by float(K).  The result is a
+ *     function of the operands alone and bit-identical run to run, with the parent entry's one exception (full_rows).
+ *   - Non-finite values follow the fp32 formulas in IEEE arithmetic.  A NaN in row b makes every output of row b NaN.  A
+ *     sum of squares that overflows fp32 (an infinite x[b,k] included) gives r[b] = 0; xn is then 0 where x is finite and
+ *     NaN where x is infinite.  WHERE a finite row overflows depends on the order above: a row whose exact sum of squares
+ *     is within a few units in the last place of FLT_MAX may overflow in another order and not in this one.
+ *   - This is not bit-identical to the norm as the checkpoints' modules write it in torch (upcast, pow, mean, + eps,
+ *     rsqrt, mul, DOWNCAST, mul weight), which rounds x * r to 16 bits and the product with the weight to 16 bits again
+ *     before the linear reads it, and whose rsqrt need not be correctly rounded: the fused form keeps xn in fp32 and is
+ *     the closer of the two to the exact value, by up to two 16-bit roundings per element of xn.
+ *   - vec need not be aligned beyond its elements, as for sqllm_linear_*.
+ *
+ * Workspace sizes and rules are the parent entry's, and one workspace may serve norm and plain launches alternately.  Each
+ * call is one kernel: nothing allocated, capturable as one kernel node.  Rejected before the device is touched: first
+ * a NULL norm descriptor or weight (SQLLM_E_NULL), then eps negative or not finite (SQLLM_E_OPTION); after those, everything
+ * the parent entry rejects, with its own codes, and a weight whose [K] range overlaps an output or the workspace
+ * (SQLLM_E_SHAPE).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_rmsnorm {
+  const void* weight; /* 16-bit [K], the type of x, device memory */
+  float eps;          /* >= 0 and finite */
+} sqllm_rmsnorm;
+int sqllm_gated_norm_f16(const sqllm_gated* g, const sqllm_rmsnorm* norm, sqllm_stream_t stream);
+int sqllm_gated_norm_bf16(const sqllm_gated* g, const sqllm_rmsnorm* norm, sqllm_stream_t stream);
+int sqllm_qkv_rope_norm_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, sqllm_stream_t stream);
+int sqllm_qkv_rope_norm_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

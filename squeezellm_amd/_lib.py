@@ -65,6 +65,12 @@ class SqllmLinearEp(ctypes.Structure):
 ROPE_HALF, ROPE_INTERLEAVED = 0, 1  # SQLLM_ROPE_*
 
 
+class SqllmRmsNorm(ctypes.Structure):
+    """struct sqllm_rmsnorm (include/sqllm_hip.h): the norm weight (16-bit [K], the type of x) and eps of a norm front."""
+
+    _fields_ = [("weight", c_void_p), ("eps", ctypes.c_float)]
+
+
 class SqllmQkvRope(ctypes.Structure):
     """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
 
@@ -157,6 +163,10 @@ SIGNATURES = {
     "sqllm_qkv_rope_workspace_bytes": [POINTER(SqllmOp), POINTER(SqllmOp), POINTER(SqllmOp)],
     "sqllm_qkv_rope_f16": [POINTER(SqllmQkvRope), P],
     "sqllm_qkv_rope_bf16": [POINTER(SqllmQkvRope), P],
+    "sqllm_gated_norm_f16": [POINTER(SqllmGated), POINTER(SqllmRmsNorm), P],
+    "sqllm_gated_norm_bf16": [POINTER(SqllmGated), POINTER(SqllmRmsNorm), P],
+    "sqllm_qkv_rope_norm_f16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), P],
+    "sqllm_qkv_rope_norm_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],

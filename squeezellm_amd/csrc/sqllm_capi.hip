@@ -19,6 +19,8 @@ namespace sqllm {
 hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated.hip
 hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream) = nullptr;  // set by sqllm_linear_ep.hip
 hipError_t (*g_launch_linear_qkv)(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv.hip
+hipError_t (*g_launch_linear_gated_norm)(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated_norm.hip
+hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm.hip
 }
 
 namespace sqllm_host {
@@ -1124,6 +1126,7 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
 // `pair` (sqllm_gated_*: two fused linears, gate and up): the plane of pair words; the launch then goes to the gated kernel.
 // `ep` (sqllm_linear_ep_*: one fused linear): activation code and residual; the launch then goes to the epilogue kernel.
 // `qkv` (sqllm_qkv_rope_*: three fused linears, q, k and v): the rotation's operands; the launch then goes to the qkv kernel.
+// `vn` (sqllm_gated_norm_* / sqllm_qkv_rope_norm_*, with `pair` / `qkv`): vec is un-normalised, the launch goes to the norm front's kernel.
 struct EpilogueArgs {
   const void* residual;  // 16-bit [batch, N] of the output's type, or null
   int act;               // SQLLM_ACT_*, validated by the caller
@@ -1131,7 +1134,7 @@ struct EpilogueArgs {
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, const sqllm_linear* lin = nullptr, void* ws = nullptr, int64_t ws_bytes = 0,
                                     bool ws_entry = false, bool bf16 = false, void* pair = nullptr, const EpilogueArgs* ep = nullptr,
-                                    const sqllm::QkvRope* qkv = nullptr) {
+                                    const sqllm::QkvRope* qkv = nullptr, const sqllm::VecNorm* vn = nullptr) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
   sqllm_op tmp[sqllm::kMaxSegments];
@@ -1186,6 +1189,8 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
       case kFusedLinear:
         if (pair) {  // (sqllm_linear_gated.hip; without that file in the link there is no such kernel.  Not decorated: the measurement
                      // library's ablation bits, LDS pad and timeline buffer belong to the kernels it instantiates itself)
+          if (vn) e = sqllm::g_launch_linear_gated_norm ? sqllm::g_launch_linear_gated_norm(op->bits, a, pair, *vn, s) : hipErrorNotSupported;
+          else
           e = sqllm::g_launch_linear_gated ? sqllm::g_launch_linear_gated(op->bits, a, pair, s) : hipErrorNotSupported;
           break;
         }
@@ -1194,6 +1199,8 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
           break;
         }
         if (qkv) {  // (sqllm_linear_qkv.hip; a missing kernel is an error here too, and the launch is not decorated either)
+          if (vn) e = sqllm::g_launch_linear_qkv_norm ? sqllm::g_launch_linear_qkv_norm(op->bits, a, *qkv, *vn, s) : hipErrorNotSupported;
+          else
           e = sqllm::g_launch_linear_qkv ? sqllm::g_launch_linear_qkv(op->bits, a, *qkv, s) : hipErrorNotSupported;
           break;
         }
@@ -1279,7 +1286,21 @@ int64_t sqllm_gated_workspace_bytes(const sqllm_op* gate) {
 }
 
 // gate and up as the two-op group of the fused linear (same route, plan and validation), finished by the gated kernel
-static int launch_gated(const sqllm_gated* g, sqllm_stream_t stream, bool bf16) {
+// The norm fronts' own checks, ahead of the parent's: the descriptor and its weight, then eps.
+static int check_rmsnorm(const sqllm_rmsnorm* nm) {
+  if (!nm || !nm->weight) return SQLLM_E_NULL;
+  if (!(nm->eps >= 0.f) || nm->eps > 3.402823466e38f) return SQLLM_E_OPTION;  // (negative, NaN, infinite)
+  return SQLLM_OK;
+}
+// the norm weight [K] against a range the launch writes (an output, the workspace)
+static bool norm_weight_overlaps(const sqllm_rmsnorm* nm, int K, const void* p, int64_t bytes) {
+  const uintptr_t w0 = reinterpret_cast<uintptr_t>(nm->weight), w1 = w0 + 2u * (uintptr_t)K;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(p);
+  return w0 < a0 + (uintptr_t)bytes && a0 < w1;
+}
+
+// `nm` (sqllm_gated_norm_*): vec is the un-normalised hidden state and the kernel is the norm front's
+static int launch_gated(const sqllm_gated* g, sqllm_stream_t stream, bool bf16, const sqllm_rmsnorm* nm = nullptr) {
   if (!g) return SQLLM_E_NULL;
   if (g->act != SQLLM_ACT_SILU) return SQLLM_E_OPTION;
   const sqllm_op &a = g->gate, &b = g->up;
@@ -1297,11 +1318,31 @@ static int launch_gated(const sqllm_gated* g, sqllm_stream_t stream, bool bf16) 
   lin[1].bias = g->bias_up;
   lin[0].workspace = g->workspace;
   lin[1].workspace = static_cast<char*>(g->workspace) + plane;
+  if (nm) {
+    // (shapes the linear's own validation is about to reject are left to it)
+    if (a.K > 0 && a.N > 0) {
+      const int64_t rows = a.batch <= 0 ? 1 : a.batch;
+      if (norm_weight_overlaps(nm, a.K, g->out, 2 * rows * a.N) || norm_weight_overlaps(nm, a.K, g->workspace, sqllm_gated_workspace_bytes(&a)))
+        return SQLLM_E_SHAPE;
+    }
+    const sqllm::VecNorm vn = {nm->weight, nm->eps};
+    return launch_group_with_events(nullptr, 2, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, static_cast<char*>(g->workspace) + 2 * plane,
+                                    nullptr, nullptr, &vn);
+  }
   return launch_group_with_events(nullptr, 2, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, static_cast<char*>(g->workspace) + 2 * plane);
 }
 
 int sqllm_gated_f16(const sqllm_gated* g, sqllm_stream_t stream) { return launch_gated(g, stream, false); }
 int sqllm_gated_bf16(const sqllm_gated* g, sqllm_stream_t stream) { return launch_gated(g, stream, true); }
+
+int sqllm_gated_norm_f16(const sqllm_gated* g, const sqllm_rmsnorm* nm, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_gated(g, stream, false, nm);
+}
+int sqllm_gated_norm_bf16(const sqllm_gated* g, const sqllm_rmsnorm* nm, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_gated(g, stream, true, nm);
+}
 
 // one fused linear (same route, plan, validation and workspace), finished by the epilogue kernel
 static int launch_linear_ep(const sqllm_linear_ep* e, sqllm_stream_t stream, bool bf16) {
@@ -1331,7 +1372,8 @@ int64_t sqllm_qkv_rope_workspace_bytes(const sqllm_op* q, const sqllm_op* k, con
 }
 
 // q, k and v as the three-op group of the fused linear (same route, plan and validation), finished by the qkv kernel
-static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool bf16) {
+// `nm` (sqllm_qkv_rope_norm_*): vec is the un-normalised hidden state and the kernel is the norm front's
+static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool bf16, const sqllm_rmsnorm* nm = nullptr) {
   if (!r) return SQLLM_E_NULL;
   const sqllm_op* m[3] = {&r->q, &r->k, &r->v};
   void* const out[3] = {r->out_q, r->out_k, r->out_v};
@@ -1361,7 +1403,9 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
         const uintptr_t b0 = reinterpret_cast<uintptr_t>(out[j]), b1 = b0 + 2u * (uintptr_t)rows * (uintptr_t)m[j]->N;
         if (a0 < b1 && b0 < a1) return SQLLM_E_SHAPE;
       }
+      if (nm && m[0]->K > 0 && norm_weight_overlaps(nm, m[0]->K, out[i], 2 * rows * m[i]->N)) return SQLLM_E_SHAPE;
     }
+    if (nm && m[0]->K > 0 && norm_weight_overlaps(nm, m[0]->K, r->workspace, ws_bytes)) return SQLLM_E_SHAPE;
   }
   sqllm_linear lin[3];
   char* ws = static_cast<char*>(r->workspace);
@@ -1382,11 +1426,24 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
   qr.n_pos = r->n_pos;
   qr.head_dim = D;
   qr.interleaved = r->layout == SQLLM_ROPE_INTERLEAVED;
+  if (nm) {
+    const sqllm::VecNorm vn = {nm->weight, nm->eps};
+    return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr, &vn);
+  }
   return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr);
 }
 
 int sqllm_qkv_rope_f16(const sqllm_qkv_rope* r, sqllm_stream_t stream) { return launch_qkv_rope(r, stream, false); }
 int sqllm_qkv_rope_bf16(const sqllm_qkv_rope* r, sqllm_stream_t stream) { return launch_qkv_rope(r, stream, true); }
+
+int sqllm_qkv_rope_norm_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, false, nm);
+}
+int sqllm_qkv_rope_norm_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, true, nm);
+}
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

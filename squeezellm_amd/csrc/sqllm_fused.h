@@ -60,13 +60,18 @@
 
 namespace sqllm {
 
+// LDS floats of the dense role's codebooks (dense_role: kCodebookFloats); the cross-wave slabs follow them
+constexpr int codebook_floats(int bits, bool pair) { return pair ? 4 * 64 * 32 : bits == 4 ? 2048 : 1024; }
+
 // ------------------------------------------------------------------------------------------------
 // Dense epilogue (shared by the dense-role variants): fold the 4 lane rows, then the waves through
 // LDS, one atomic per column.  `slabs` = LDS area [WAVES][BT][64] floats followed by the ticket.
 // ------------------------------------------------------------------------------------------------
 // OT: the 16-bit type of a fused linear's output (sqllm_decode.h: FixRange, column_done); the fp16 default elsewhere
 // FIN: the finishing step of a fused linear's column (sqllm_decode.h: ColumnStore, the default -- column_done)
-template <int BT, int WAVES, int ABL, typename OT = _Float16, typename FIN = ColumnStore>
+// ISLIN: `lin` is known not to be null (the norm fronts, always fused linears: comparing the segment descriptor's address with null at run
+// time kept the whole descriptor in scratch memory there); the default asks the pointer, as ever
+template <int BT, int WAVES, int ABL, typename OT = _Float16, typename FIN = ColumnStore, bool ISLIN = false>
 __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float* slabs, const float* topx_sum,
                                                bool fold_topx, float* __restrict__ y, int N, int col0, int b0,
                                                int nb, int lane, int wave, const Segment& sg, const Segment* lin,
@@ -127,7 +132,7 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
   if (c < N) {
     u64 total[BT];
     unsigned target = 0;
-    if (lin) {  // contributions this column receives: K slices + the CSR chunks its row is spread over
+    if (ISLIN || lin) {  // contributions this column receives: K slices + the CSR chunks its row is spread over
       target = (unsigned)lin->gm.k_slices;
       if (lin->gm.csr_blocks) target += (unsigned)csr_chunks_of_row(lin->rows[c], lin->rows[c + 1]);
     }
@@ -139,7 +144,7 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
         for (int w = 0; w < WAVES; ++w) sum += red[(w * BT + b) * kTileN + lane];
         const size_t at = (size_t)(b0 + b) * N + c;
         if (fold_topx) sum += topx_sum[b * kTileN + lane];
-        if (lin) {
+        if (ISLIN || lin) {
           const u64 mine = kCountUnit + to_fixed<OT>(sum);
           flag_nonfinite<OT>(reinterpret_cast<u64*>(y) + at, sum);
           total[b] = atomicAdd(reinterpret_cast<u64*>(y) + at, mine) + mine;
@@ -149,7 +154,7 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
       }
     }
     SQLLM_PROBE(tl, 3, lane == 0);  // atomics issued by the combining wave
-    if (lin) {  // all the round trips are in flight before the first result is looked at
+    if (ISLIN || lin) {  // all the round trips are in flight before the first result is looked at
 #pragma unroll
       for (int b = 0; b < BT; ++b) {
         const size_t at = (size_t)(b0 + b) * N + c;
@@ -179,11 +184,12 @@ __device__ __forceinline__ void dense_epilogue(const f32x2 (&acc)[2][BT], float*
 // address arithmetic cost more VALU than the overlap returns), and up to 32 waves per CU at different
 // phases keep the memory pipe busy.
 // ------------------------------------------------------------------------------------------------
-template <int BITS, int BT, int WAVES, int ABL, typename XT, bool HALF = false, bool SHORT = false, typename FIN = ColumnStore>
+// VP: the vec policy (sqllm_roles.h: PlainVec, the default; RmsVec scales every element of vec by g[k] * r[b] as it is loaded)
+template <int BITS, int BT, int WAVES, int ABL, typename XT, bool HALF = false, bool SHORT = false, typename FIN = ColumnStore, typename VP = PlainVec>
 __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* __restrict__ y,
                                            const float* lut, int K, int N, int b0, int nb, int bid,
                                            int n_col_tiles, int units_total, int units_per_wg, float* lds,
-                                           const Segment& sg, const Segment* lin, FIN fin = FIN()) {
+                                           const Segment& sg, const Segment* lin, FIN fin = FIN(), VP vp = VP()) {
   using F = Fmt<BITS>;
   constexpr uint32_t XB = sizeof(XT);  // bytes per element of vec (4: operator ABI, 2: fused linear, fp16 or bf16)
   // Clean slate for the compiler's wait-count model: the other roles sit upstream of this one in
@@ -266,6 +272,8 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
           if (uu > u_last) uu = u_last;
           const uint32_t off = XB * (8u * (uint32_t)uu + (i16 & 7));
           xs[s2][b] = (ABL & 16) ? 1.f + i16 : (float)*reinterpret_cast<const XT*>(xbase[b] + off);
+          // (norm prologue: the norm weight sits at the same offset of g as the element in its row of vec)
+          if constexpr (VP::kNorm) xs[s2][b] = xs[s2][b] * (float)*reinterpret_cast<const XT*>(reinterpret_cast<const char*>(vp.g) + off) * vp.row(b);
         }
       } else {
 #pragma unroll
@@ -275,6 +283,11 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
           const uint32_t off = XB * (32u * (uint32_t)uu + i16);
           xs[2 * s][b] = (float)*reinterpret_cast<const XT*>(xbase[b] + off);
           xs[2 * s + 1][b] = (float)*reinterpret_cast<const XT*>(xbase[b] + off + 16 * XB);
+          if constexpr (VP::kNorm) {
+            const char* gb = reinterpret_cast<const char*>(vp.g);
+            xs[2 * s][b] = xs[2 * s][b] * (float)*reinterpret_cast<const XT*>(gb + off) * vp.row(b);
+            xs[2 * s + 1][b] = xs[2 * s + 1][b] * (float)*reinterpret_cast<const XT*>(gb + off + 16 * XB) * vp.row(b);
+          }
         }
       }
     }
@@ -328,11 +341,12 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
   // folding measured 6 % slower there (the matched workgroups become the tail of the launch).
   // timeline probe (sqllm_probe.h; nothing in the product): wave 0 stamps entry / barrier passed / decode done, the
   // combining wave stamps the end
-  unsigned long long* tl = lin ? nullptr : SQLLM_PROBE_PTR(sg);
+  unsigned long long* tl = (VP::kNorm || lin) ? nullptr : SQLLM_PROBE_PTR(sg);
   SQLLM_PROBE(tl, 0, tid == 0);
   // Branches first: between the loads below and the codebook staging there must be NO control
   // flow, or the staging waits for every outstanding load (vmcnt(0)) instead of its own.
   constexpr int kCodebookFloats = PAIR ? 4 * 64 * 128 / 4 : 4 * SUBB / 4;  // the four column sub-tables
+  static_assert(kCodebookFloats == codebook_floats(BITS, PAIR), "sqllm_norm_front.h parks its partial sums behind the codebooks");
   float* topx_sum = lds + kCodebookFloats + WAVES * BT * kTileN + 4;  // [BT][64], fused linear only
   // epilogue ticket (the dword after the slabs) and, 4 dwords on, the BT * 64 top-X sums
   for (int i = tid; i < 4 + BT * kTileN; i += WAVES * 64) lds[kCodebookFloats + WAVES * BT * kTileN + i] = 0.f;
@@ -433,6 +447,10 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
         for (int b = 0; b < BT; ++b) {
           float p = 0.f;
           for (int k = k_beg + wave * 64 + lane; k < k_end; k += WAVES * 64)
+            if constexpr (VP::kNorm)
+              p = __builtin_fmaf(sg.full_rows[(size_t)k * topX + j],
+                                 (float)x[(size_t)(b0 + (b < nb ? b : nb - 1)) * K + k] * vp.gk(k) * vp.row(b), p);
+            else
             p = __builtin_fmaf(sg.full_rows[(size_t)k * topX + j],
                                (float)x[(size_t)(b0 + (b < nb ? b : nb - 1)) * K + k], p);
           p = wave_sum(p);
@@ -457,7 +475,7 @@ __device__ __forceinline__ void dense_role(const XT* x, const u32x4* q, float* _
     acc[0][0] = f32x2{accp[0].x + accp[0].y, accp[1].x + accp[1].y};
     acc[1][0] = f32x2{accp[2].x + accp[2].y, accp[3].x + accp[3].y};
   }
-  dense_epilogue<BT, WAVES, ABL, typename FIN::template Range<XT>::type, FIN>(acc, lds + kCodebookFloats, topx_sum, fold_topx, y, N, col0, b0, nb, lane, wave, sg, lin, tl, fin);
+  dense_epilogue<BT, WAVES, ABL, typename FIN::template Range<XT>::type, FIN, VP::kNorm>(acc, lds + kCodebookFloats, topx_sum, fold_topx, y, N, col0, b0, nb, lane, wave, sg, lin, tl, fin);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -159,6 +159,15 @@ struct QkvRope {
   bool interleaved;      // SQLLM_ROPE_INTERLEAVED (partner next door) instead of SQLLM_ROPE_HALF (partner head_dim / 2 away)
 };
 extern hipError_t (*g_launch_linear_qkv)(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream);
+// the norm fronts (sqllm_gated_norm_* / sqllm_qkv_rope_norm_*): the two launches above with RMSNorm as a prologue, on the kernels of
+// sqllm_linear_gated_norm.hip / sqllm_linear_qkv_norm.hip -- every element of vec is read as float(x) * float(weight[k]) * r[row].
+// Hooks, as above.
+struct VecNorm {
+  const void* weight;  // 16-bit [K] of vec's type, device memory
+  float eps;
+};
+extern hipError_t (*g_launch_linear_gated_norm)(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream);
+extern hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

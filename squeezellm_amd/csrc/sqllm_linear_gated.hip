@@ -7,7 +7,7 @@
 // The kernel is sqllm_linear_bf16_kernel's skeleton (pick_segment, role dispatch, dense_role with the top-X rows folded in,
 // csr_role, topx_role, AT = the 64-bit completion word) launched on a group of exactly two segments, segment 0 = gate and
 // segment 1 = up: route, planner, geometry and validation are kFusedLinear's two-op group.  Two things are its own, both
-// carried by the finishing policy the roles are instantiated with (PairFinish below; sqllm_decode.h: ColumnStore is the default):
+// carried by the finishing policy the roles are instantiated with (PairFinish, sqllm_pair_finish.h; sqllm_decode.h: ColumnStore is the default):
 //   * the range rule is the bf16 one for BOTH output types (FixRange<__bf16>: a finite contribution beyond +-2^17 sets the
 //     infinity flag of its sign and adds nothing).  The fp16 linear clamps there because such an fp16 result is not finite
 //     anyway; here g = 200000, u = 0.05 has a finite fp16 product and a clamp would return a wrong finite number;
@@ -22,32 +22,9 @@
 // polling, no launch-wide counter: whoever arrives second finishes -- and the result is a function of the operands alone:
 // the integer sums commute and the last step sees the same two fp32 values whichever member finishes first.
 #include "sqllm_fused.h"
+#include "sqllm_pair_finish.h"
 
 namespace sqllm {
-
-constexpr u64 kPairTag = 1ull << 32;  // a deposited value is never the empty word, whatever its bits
-
-// OT: the element type of `out` (the store); the contributions follow FixRange<__bf16> whatever OT is
-template <typename OT>
-struct PairFinish {
-  u64* pair;   // [batch, N] pair words, all zero between launches
-  int member;  // this workgroup's segment: 0 = gate, 1 = up
-  static constexpr bool kOrderedCsr = true;  // a CSR chunk's parts of a row meet in wave order: the same fp32 value in every run
-  template <typename XT> struct Range { using type = __bf16; };
-  template <typename RT>
-  __device__ __forceinline__ void done(const Segment& sg, u64* word, u64 total, unsigned target, size_t at, int c) const {
-    float v;
-    if (!column_value(sg, total, target, c, &v)) return;
-    atomicExch(word, 0ull);  // result unused: a plain atomic store
-    const u64 mine = kPairTag | (u64)__builtin_bit_cast(uint32_t, v);
-    const u64 other = __hip_atomic_exchange(SQLLM_GLOBAL(u64, pair + at), mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (other == 0) return;  // the first of the two: the other member's finisher completes the pair
-    const float o = __builtin_bit_cast(float, (uint32_t)other);
-    const float g = member ? o : v, u = member ? v : o;
-    reinterpret_cast<OT*>(sg.out16)[at] = (OT)((g / (1.f + expf(-g))) * u);
-    __hip_atomic_exchange(SQLLM_GLOBAL(u64, pair + at), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (result unused)
-  }
-};
 
 template <int BITS, int BT, typename OT>
 __global__ void __launch_bounds__(kWaves * 64, fused_min_waves(BITS, BT, 0))

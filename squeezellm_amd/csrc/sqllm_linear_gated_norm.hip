@@ -1,0 +1,96 @@
+// sqllm_linear_gated_norm.hip -- the gated front of an MLP with its RMSNorm in front, as ONE kernel (include/sqllm_hip.h:
+// sqllm_gated_norm_f16 / _bf16): sqllm_linear_gated.hip's kernel, statement for statement, with
+//
+//     xn[b, k] = float(x[b, k]) * float(g[k]) * r[b],      r[b] = 1 / sqrt(mean_k float(x[b, k])^2 + eps)
+//
+// in the place of float(x[b, k]) in all three weight terms (sqllm_norm_front.h: every workgroup works out r[] for its own
+// rows at entry; sqllm_roles.h: RmsVec scales the elements where the roles load them).  Range rule, flags, ordered CSR adds
+// and the finisher (sqllm_pair_finish.h) are the parent's: the sums that enter the fixed-point words are sums over xn.
+#include "sqllm_fused.h"
+#include "sqllm_norm_front.h"
+#include "sqllm_pair_finish.h"
+
+namespace sqllm {
+
+template <int BITS, int BT, typename OT>
+__global__ void __launch_bounds__(kWaves * 64, norm_min_waves(BITS, BT))
+sqllm_linear_gated_norm_kernel(const void* xv, const GroupArgs ga, u64* pair, const NormArgs na) {
+  constexpr int WAVES = kWaves;
+  constexpr bool HALF = fused_half_stages(BITS, BT);
+  constexpr int T = WAVES * 64;
+  constexpr bool PAIR3 = BITS == 3 && BT == 1 && SQLLM_HALF_STAGES && SQLLM_PAIR3;
+  constexpr int kLds = lds_floats(Fmt<BITS>::kLut, WAVES, BT, PAIR3);
+  __shared__ __attribute__((aligned(16))) float lds[kLds];
+  using XT = OT;
+  using AT = u64;
+  using FIN = PairFinish<OT>;
+  using VP = RmsVec<XT, BT>;
+  const XT* x = reinterpret_cast<const XT*>(xv);
+
+  // one round of scalar loads for vec's address, the block table and segment 0 (see sqllm_fused_matvec)
+  Segment sg;
+  const int bid = pick_segment(ga, x, sg);
+  const KernelGeom& gm = sg.gm;
+  const int b0 = blockIdx.y * BT;
+  int nb = gm.batch - b0;
+  if (nb > BT) nb = BT;
+  const FIN fin{pair, (int)blockIdx.x >= ga.block0[1] ? 1 : 0};  // (two segments: the host launches nothing else here)
+  VP vp;
+  vp.g = reinterpret_cast<const XT*>(na.g);
+  static_assert(codebook_floats(BITS, PAIR3) >= kTopxLds && codebook_floats(BITS, PAIR3) + WAVES * BT <= kLds, "norm_rows: where the partial sums lie");
+  vp.rv = norm_rows<BT>(x, ga.seg[0].gm.K /* (the members share K) */, b0, nb, na.eps, lds + codebook_floats(BITS, PAIR3));
+
+  // role by block id within the segment: [sparse | pad | dense] or, with sparse_last, [dense | sparse]
+  int d, sp;
+  if (gm.sparse_last & 1) {
+    d = bid;
+    sp = bid - gm.dense_blocks;
+  } else {
+    d = bid - gm.dense_block0;
+    sp = bid < gm.dense_block0 ? bid : -1;
+  }
+  if (d >= 0 && d < gm.dense_blocks) {
+    dense_role<BITS, BT, WAVES, 0, XT, HALF, false, FIN, VP>(x, reinterpret_cast<const u32x4*>(sg.q), sg.y, sg.lut, gm.K, gm.N, b0, nb, d,
+                                                             gm.col_tiles, gm.units_total, gm.units_per_wg, lds, sg, &sg, fin, vp);
+  } else if (sp >= 0 && sp < gm.csr_blocks) {
+    if (gm.dense_prio == 2) __builtin_amdgcn_s_setprio(1);
+    csr_role<T, BT, XT, AT, false, false, NoGate, kCsrChunk, FIN, VP>(x, reinterpret_cast<AT*>(sg.y), sg.rows, sg.cols, sg.vals, gm.nnz, gm.K, gm.N,
+                                                                      b0, nb, sp, lds, &sg, gm.sparse_last >> 1, nullptr, 0, nullptr, NoGate(), fin, vp);
+  } else if (sp >= gm.csr_blocks && sp < gm.csr_blocks + gm.topx_blocks) {
+    // (never taken when the plan folds the top-X rows into the dense tiles)
+    if (gm.dense_prio == 2) __builtin_amdgcn_s_setprio(1);
+    topx_role<T, XT, AT, false, NoGate, BT, FIN, VP>(x, reinterpret_cast<AT*>(sg.y), sg.full_rows, sg.full_idx, gm.topX, gm.K, gm.N, b0, nb,
+                                                     sp - gm.csr_blocks, lds, NoGate(), vp);
+  }
+}
+
+template <int BITS, int BT, typename OT>
+static hipError_t launch_gated_norm_inst(const LaunchArgs& a, void* pair, const NormArgs& na, hipStream_t stream) {
+  const int batch = a.ga.seg[0].gm.batch;
+  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
+  auto kern = sqllm_linear_gated_norm_kernel<BITS, BT, OT>;
+  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, static_cast<u64*>(pair), na);
+}
+
+template <int BITS, typename OT>
+static hipError_t launch_gated_norm_bits(const LaunchArgs& a, void* pair, const NormArgs& na, hipStream_t stream) {
+  switch (batch_tile(a.ga.seg[0].gm.batch)) {
+    case 1: return launch_gated_norm_inst<BITS, 1, OT>(a, pair, na, stream);
+    case 2: return launch_gated_norm_inst<BITS, 2, OT>(a, pair, na, stream);
+    case 4: return launch_gated_norm_inst<BITS, 4, OT>(a, pair, na, stream);
+    default: return launch_gated_norm_inst<BITS, 8, OT>(a, pair, na, stream);
+  }
+}
+
+// gate (segment 0) and up (segment 1) over one un-normalised 16-bit vec (a.ga; a.bf16: its type); vn: the norm's weight and eps
+static hipError_t launch_linear_gated_norm(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream) {
+  if (a.ga.n_seg != 2 || !pair || !vn.weight) return hipErrorInvalidValue;
+  const NormArgs na = {vn.weight, vn.eps};
+  if (a.bf16) return bits == 4 ? launch_gated_norm_bits<4, __bf16>(a, pair, na, stream) : launch_gated_norm_bits<3, __bf16>(a, pair, na, stream);
+  return bits == 4 ? launch_gated_norm_bits<4, _Float16>(a, pair, na, stream) : launch_gated_norm_bits<3, _Float16>(a, pair, na, stream);
+}
+
+// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
+static const bool g_gated_norm_registered = (g_launch_linear_gated_norm = launch_linear_gated_norm, true);
+
+}  // namespace sqllm

@@ -9,7 +9,7 @@
 // fp32 throughout, rounded once to OT = the type of x (fp16 or bf16).  The kernel is sqllm_linear_gated.hip's skeleton
 // (pick_segment, role dispatch, dense_role with the top-X rows folded in, csr_role, topx_role, AT = the 64-bit completion
 // word) launched on a group of exactly three segments, q, k and v: route, planner, geometry and validation are
-// kFusedLinear's three-op group.  What is its own is carried by the finishing policy (RopeFinish below):
+// kFusedLinear's three-op group.  What is its own is carried by the finishing policy (RopeFinish, sqllm_rope_finish.h):
 //   * the range rule is the bf16 one for BOTH output types (a value beyond +-2^17 can rotate to a finite fp16 result);
 //   * the finisher of a column of v stores, as the epilogue kernel's identity does.  The finisher of a column of q or k
 //     forms its fp32 value, re-zeroes its accumulator word, and does ONE returning 64-bit exchange on the PAIR WORD of
@@ -31,24 +31,10 @@
 #include <stddef.h>
 
 #include "sqllm_fused.h"
+#include "sqllm_rope_finish.h"
 
 namespace sqllm {
 
-constexpr u64 kPairTag = 1ull << 32;  // a deposited value is never the empty word, whatever its bits
-
-// by-value kernel argument behind GroupArgs; read through rope_args() only
-struct RopeArgs {
-  u64* pair_q;           // [batch, N_q / 2] pair words, all zero between launches
-  u64* pair_k;           // [batch, N_k / 2]
-  const float* cos;      // fp32 [n_pos, D / 2]
-  const float* sin;
-  const int* positions;  // int32 [batch]
-  int n_pos;
-  int half;              // D / 2
-  uint32_t d_magic;      // floor(2^32 / D) + 1: c / D == mulhi(c, d_magic) for c * D < 2^32 (the host checks N * D)
-  int interleaved;       // 0: partner D / 2 away, 1: partner next door
-  float inv_nq, inv_nk;  // 1 / N of the member, fp32
-};
 // the kernel's explicit arguments as the ABI lays them out (natural alignment, in order)
 struct QkvKernArgs {
   const void* x;
@@ -57,79 +43,7 @@ struct QkvKernArgs {
 };
 constexpr unsigned kRopeArgsOffset = offsetof(QkvKernArgs, ra);
 static_assert(kRopeArgsOffset == sizeof(void*) + sizeof(GroupArgs) && sizeof(RopeArgs) == 64, "the descriptor block ends on the next argument's alignment");
-
-// The rotary arguments, from the kernel-argument segment, no earlier than HERE: the empty asm statement hides where the
-// address came from, so the scalar loads through it cannot be scheduled at the kernel's start and held across the walk.
-// (The cast back names the constant address space: the loads stay scalar.)
-__device__ __forceinline__ const __attribute__((address_space(4))) RopeArgs* rope_args() {
-  uintptr_t p = reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr()) + kRopeArgsOffset;
-  asm volatile("" : "+s"(p));
-  return reinterpret_cast<const __attribute__((address_space(4))) RopeArgs*>(p);
-}
-
-// Column c of a rotated member: the pair's slot in a row of the pair plane, h * D / 2 + j; *is_hi: c is the pair's upper
-// column; *j: the table column; *dist: how far apart the two columns are.  No division: c / D is a multiply-high.
-__device__ __forceinline__ uint32_t locate(const __attribute__((address_space(4))) RopeArgs* ra, int c, bool* is_hi, int* j, int* dist) {
-  const int half = ra->half;
-  const uint32_t h = __umulhi((uint32_t)c, ra->d_magic);
-  const int r = c - (int)h * 2 * half;  // c % D
-  if (ra->interleaved) {
-    *is_hi = c & 1;
-    *j = r >> 1;
-    *dist = 1;
-  } else {
-    *is_hi = r >= half;
-    *j = *is_hi ? r - half : r;
-    *dist = half;
-  }
-  return h * (uint32_t)half + (uint32_t)*j;
-}
-
-// OT: the element type of the outputs; the contributions follow FixRange<__bf16> whatever OT is
-template <typename OT>
-struct RopeFinish {
-  int member;  // this workgroup's segment: 0 = q, 1 = k, 2 = v
-  static constexpr bool kOrderedCsr = true;  // a CSR chunk's parts of a row meet in wave order: the same fp32 value in every run
-  template <typename XT> struct Range { using type = __bf16; };
-  template <typename RT>
-  __device__ __forceinline__ void done(const Segment& sg, u64* word, u64 total, unsigned target, size_t at, int c) const {
-    float v;
-    if (!column_value(sg, total, target, c, &v)) return;
-    atomicExch(word, 0ull);  // result unused: a plain atomic store
-    OT* out = reinterpret_cast<OT*>(sg.out16);
-    if (member == 2) {
-      out[at] = (OT)v;
-      return;
-    }
-    const auto* ra = rope_args();
-    bool is_hi;
-    int j, dist;
-    const uint32_t bn = (uint32_t)(at - (size_t)c);  // b * N (N is even)
-    u64* pw = (member ? ra->pair_k : ra->pair_q) + ((bn >> 1) + locate(ra, c, &is_hi, &j, &dist));
-    const u64 mine = kPairTag | (u64)__builtin_bit_cast(uint32_t, v);
-    const u64 other = __hip_atomic_exchange(SQLLM_GLOBAL(u64, pw), mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (other == 0) return;  // the first of the two: the partner column's finisher completes the pair
-    const float o = __builtin_bit_cast(float, (uint32_t)other);
-    // (located a second time, from a copy of c the compiler cannot see through: four VALU instructions in the one finisher
-    // of a pair instead of three registers held by every finisher across its exchange)
-    int c2 = c;
-    asm volatile("" : "+v"(c2));
-    locate(ra, c2, &is_hi, &j, &dist);
-    const float lo = is_hi ? o : v, hi = is_hi ? v : o;
-    const int b = (int)((float)bn * (member ? ra->inv_nk : ra->inv_nq) + 0.5f);
-    const int p = ra->positions[b];
-    float cs = __builtin_nanf(""), sn = cs;  // a position outside the tables: NaN, and nothing is read
-    if ((unsigned)p < (unsigned)ra->n_pos) {
-      const size_t t = (size_t)p * ra->half + j;
-      cs = ra->cos[t];
-      sn = ra->sin[t];
-    }
-    const size_t at_lo = is_hi ? at - dist : at;
-    out[at_lo] = (OT)(lo * cs - hi * sn);
-    out[at_lo + dist] = (OT)(hi * cs + lo * sn);
-    __hip_atomic_exchange(SQLLM_GLOBAL(u64, pw), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (result unused)
-  }
-};
+static_assert(kRopeArgsOffset == kRopeArgsAt, "rope_args() reads the third argument");
 
 template <int BITS, int BT, typename OT>
 __global__ void __launch_bounds__(kWaves * 64, fused_min_waves(BITS, BT, 0))
@@ -200,18 +114,7 @@ static hipError_t launch_qkv_bits(const LaunchArgs& a, const RopeArgs& ra, hipSt
 static hipError_t launch_linear_qkv(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream) {
   if (a.ga.n_seg != 3 || !r.pair_q || !r.pair_k || !r.cos || !r.sin || !r.positions || r.head_dim < 2 || (r.head_dim & 1))
     return hipErrorInvalidValue;
-  RopeArgs ra;
-  ra.pair_q = static_cast<u64*>(r.pair_q);
-  ra.pair_k = static_cast<u64*>(r.pair_k);
-  ra.cos = r.cos;
-  ra.sin = r.sin;
-  ra.positions = r.positions;
-  ra.n_pos = r.n_pos;
-  ra.half = r.head_dim / 2;
-  ra.d_magic = (uint32_t)((1ull << 32) / (uint32_t)r.head_dim) + 1u;
-  ra.interleaved = r.interleaved ? 1 : 0;
-  ra.inv_nq = 1.f / (float)a.ga.seg[0].gm.N;
-  ra.inv_nk = 1.f / (float)a.ga.seg[1].gm.N;
+  const RopeArgs ra = make_rope_args(a, r);
   if (a.bf16) return bits == 4 ? launch_qkv_bits<4, __bf16>(a, ra, stream) : launch_qkv_bits<3, __bf16>(a, ra, stream);
   return bits == 4 ? launch_qkv_bits<4, _Float16>(a, ra, stream) : launch_qkv_bits<3, _Float16>(a, ra, stream);
 }

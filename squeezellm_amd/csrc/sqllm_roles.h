@@ -14,6 +14,31 @@ struct NoGate {
   __device__ __forceinline__ void operator()() const {}
 };
 
+// Vec policy of a role: what happens to an element of vec where it is read.  PlainVec, the default, is the element itself:
+// every `if constexpr (VP::kNorm)` below folds away and the role is statement for statement what it was.
+struct PlainVec {
+  static constexpr bool kNorm = false;
+  __device__ __forceinline__ float gk(size_t) const { return 1.f; }
+  __device__ __forceinline__ float row(int) const { return 1.f; }
+};
+// RMSNorm as a prologue (sqllm_norm_front.h): a role reads xn[b, k] = float(x[b, k]) * float(g[k]) * r[b] wherever it read
+// float(x[b, k]) -- the products in that order, fp32, nothing rounded to 16 bits.  r[] is indexed by the row of the batch
+// tile and holds the last valid row's value for the rows past it: the clamp sites re-read that row.  It lives in the lanes
+// of ONE vector register, the same in every wave (lane b: r[b]): r[b] is a v_readlane, for a constant row as for a row
+// index only known at run time (uniform).  (As an array, or as scalar members picked by a chain of selects, the compiler
+// kept the policy -- and the segment descriptor with it -- in scratch memory.)
+template <typename XT, int BT>
+struct RmsVec {
+  static constexpr bool kNorm = true;
+  static_assert(BT <= 64, "one lane per row of the tile");
+  const XT* g;  // [K]
+  float rv;     // lane b: r[b]
+  __device__ __forceinline__ float gk(size_t k) const { return (float)g[k]; }
+  __device__ __forceinline__ float row(int b) const {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv), b));
+  }
+};
+
 // One wave's share of a chunk in transposed-vec mode at 32 rows or fewer (see csr_role): st = the wave's WN
 // non-zeros in LDS as [column | value bits | local row] planes kCsrChunk apart; R rows per pass -> 64 / R lane
 // groups, each walking a contiguous run of WN * R / 64 non-zeros; row sums go to tile[row][local column] with an
@@ -70,15 +95,17 @@ __device__ __forceinline__ void xt_walk(const int* st, const float* __restrict__
 // CH: non-zeros per workgroup -- kCsrChunk, or (batch-1 operator launches that exceed the resident slots: sqllm_capi.hip, widen_csr_chunks) twice
 // that: half as many, twice as deep workgroups in front of a multi-round grid.
 // FIN: the finishing step and range rule of a fused linear's column (sqllm_decode.h: ColumnStore, the default)
+// VP: the vec policy (PlainVec, the default: the element as it is; RmsVec: the RMSNorm prologue's g[cols[i]] * r[b] at the gather)
 template <int T, int BT, typename XT, typename AT, bool XTMODE = false, bool XCOH = false, typename GATE = NoGate, int CH = kCsrChunk,
-          typename FIN = ColumnStore>
+          typename FIN = ColumnStore, typename VP = PlainVec>
 __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
                                          const int* __restrict__ rows, const int* __restrict__ cols,
                                          const float* __restrict__ vals, int nnz, int K, int N, int b0,
                                          int nb, int chunk, float* lds, const Segment* lin, int lin_or_abl_bits = 0,
                                          const float* __restrict__ xT = nullptr, int Bp = 0,
-                                         unsigned long long* tl = nullptr, GATE gate = GATE(), FIN fin = FIN()) {
+                                         unsigned long long* tl = nullptr, GATE gate = GATE(), FIN fin = FIN(), VP vp = VP()) {
   constexpr bool LIN = sizeof(AT) == 8;
+  static_assert(!VP::kNorm || !XTMODE, "the norm prologue scales the gathers of vec itself");
   using OT = typename FIN::template Range<XT>::type;  // fused linear: the 16-bit type of its two ends (range rule and output store)
   int tid_ = threadIdx.x;
   // (inside the persistent pass kernel the role runs in a loop over work items: what it derives from the thread id
@@ -147,6 +174,14 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
   gate();  // (gated pass: vec is not read before the producing group is complete; cols / vals / probes are already here)
 #pragma unroll
   for (int i = 0; i < EPT; ++i) xg[i] = XTMODE ? 0.f : ld_x<XCOH>(x + (size_t)b0 * K + col[i]);  // first batch row's gather
+  float gv[VP::kNorm ? EPT : 1];  // (norm prologue: the norm weight of each non-zero's column, the same for every batch row)
+  if constexpr (VP::kNorm) {
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) {
+      gv[i] = vp.gk(col[i]);
+      xg[i] = xg[i] * gv[i] * vp.row(0);
+    }
+  }
   // Batch rows go through in groups of `g`: as many as have room for their n row sums each in the
   // LDS accumulator (all of them for typical chunks, which span 50-100 rows), so a batched op
   // pays the zero / accumulate / flush round and its barriers once, not once per row, and the x
@@ -435,6 +470,8 @@ __device__ __forceinline__ void csr_role(const XT* x, AT* __restrict__ y,
 #pragma unroll
       for (int bb = 0; bb < BT; ++bb) {
         const int bi = bs + (bb < gb ? bb : gb - 1);
+        if constexpr (VP::kNorm) xv[i][bb] = (bs == 0 && bb == 0) ? xg[i] : ld_x<XCOH>(x + (size_t)(b0 + bi) * K + col[i]) * gv[i] * vp.row(bi);
+        else
         xv[i][bb] = (bs == 0 && bb == 0) ? xg[i] : ld_x<XCOH>(x + (size_t)(b0 + bi) * K + col[i]);
         if (cabl & 8) xv[i][bb] = 1.f + bb;  // (measurement: no gathers)
       }
@@ -723,11 +760,11 @@ __device__ __forceinline__ void csr_tile_fold_staged(const float* __restrict__ x
 // use 1 (their register budget); the fused small launch 8 -- row by row, a 16-row launch kept its top-X workgroups (first
 // in the grid) for 17 us, and the dense workgroups that found no slot beside them became a second round
 // (profiles/r05_small_split_timeline.txt).
-template <int T, typename XT, typename AT, bool XCOH = false, typename GATE = NoGate, int RB = 1, typename FIN = ColumnStore>
+template <int T, typename XT, typename AT, bool XCOH = false, typename GATE = NoGate, int RB = 1, typename FIN = ColumnStore, typename VP = PlainVec>
 __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
                                           const float* __restrict__ full_rows,
                                           const int* __restrict__ full_idx, int topX, int K, int N,
-                                          int b0, int nb, int slab, float* lds, GATE gate = GATE()) {
+                                          int b0, int nb, int slab, float* lds, GATE gate = GATE(), VP vp = VP()) {
   using OT = typename FIN::template Range<XT>::type;  // (see csr_role)
   int tid_ = threadIdx.x;
   if constexpr (XCOH) asm volatile("" : "+v"(tid_));  // (see csr_role)
@@ -769,6 +806,8 @@ __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
           const int k = k0 + krow + 32 * i;
+          if constexpr (VP::kNorm) q = __builtin_fmaf(frv[i], k < k1 ? ld_x<XCOH>(xb + k) * vp.gk(k) * vp.row(b) : 0.f, q);
+          else
           q = __builtin_fmaf(frv[i], k < k1 ? ld_x<XCOH>(xb + k) : 0.f, q);
         }
         p[r] = q;
@@ -809,7 +848,7 @@ __device__ __forceinline__ void topx_role(const XT* x, AT* __restrict__ y,
     for (int e = tid; e < nel; e += T) {
       const int kk = e / topX;
       const int c = e - kk * topX;
-      const float p = fr[e] * ld_x<XCOH>(xb + kk);
+      const float p = VP::kNorm ? fr[e] * (ld_x<XCOH>(xb + kk) * vp.gk(k0 + kk) * vp.row(b)) : fr[e] * ld_x<XCOH>(xb + kk);
       if (in_lds) atomicAdd(sacc + c, p); else acc_add<OT>(yb + full_idx[c], p);
     }
     if (in_lds) {

@@ -471,6 +471,39 @@ def fuse_quant_lut(module: nn.Module) -> int:
 _GATED_ENTRY = {torch.float16: "sqllm_gated_f16", torch.bfloat16: "sqllm_gated_bf16"}
 
 
+_GATED_NORM_ENTRY = {torch.float16: "sqllm_gated_norm_f16", torch.bfloat16: "sqllm_gated_norm_bf16"}
+_QKV_NORM_ENTRY = {torch.float16: "sqllm_qkv_rope_norm_f16", torch.bfloat16: "sqllm_qkv_rope_norm_bf16"}
+
+
+def _check_norm_weight(x: torch.Tensor, norm_weight: torch.Tensor, K: int, norm_eps: float) -> torch.Tensor:
+    """The norm weight of a norm front: [K], of x's dtype, on x's device (anything else: ValueError); returned contiguous."""
+    if not isinstance(norm_weight, torch.Tensor) or norm_weight.dtype != x.dtype or norm_weight.device != x.device:
+        raise ValueError(f"norm_weight must be a {x.dtype} tensor on {x.device}, got "
+                         f"{getattr(norm_weight, 'dtype', type(norm_weight).__name__)} on {getattr(norm_weight, 'device', None)}")
+    if norm_weight.dim() != 1 or norm_weight.numel() != K:
+        raise ValueError(f"norm_weight must have {K} elements, got {tuple(norm_weight.shape)}")
+    if not (norm_eps >= 0.0) or norm_eps == float("inf"):
+        raise ValueError(f"norm_eps must be finite and >= 0, got {norm_eps}")
+    return norm_weight if norm_weight.is_contiguous() else norm_weight.contiguous()
+
+
+def _torch_rmsnorm(x2: torch.Tensor, norm_weight: torch.Tensor, norm_eps: float) -> torch.Tensor:
+    """xn of the norm fronts (include/sqllm_hip.h, sqllm_rmsnorm) in torch: fp32, NOT rounded to x's type."""
+    xf = x2.float()
+    r = 1.0 / torch.sqrt(xf.pow(2).mean(dim=-1, keepdim=True) + norm_eps)
+    return xf * norm_weight.float() * r
+
+
+def _norm_ref(cache: dict, key, norm_weight: torch.Tensor, norm_eps: float):
+    """The sqllm_rmsnorm of (device, stream), filled for this call; the ctypes reference to it."""
+    hit = cache.get(key)
+    if hit is None:
+        nm = _lib.SqllmRmsNorm()
+        hit = cache[key] = (nm, ctypes.byref(nm))
+    hit[0].weight, hit[0].eps = norm_weight.data_ptr(), norm_eps
+    return hit[1]
+
+
 class QuantGatedLUTFused(nn.Module):
     """`silu(gate(x)) * up(x)` for fp16 and bf16 GPU activations as ONE kernel (sqllm_gated_f16 / sqllm_gated_bf16) instead of
     two fused linears and two torch kernels over two [rows, N] temporaries: both sums are formed as in QuantLinearLUTFused,
@@ -489,7 +522,19 @@ class QuantGatedLUTFused(nn.Module):
     and 13B gate / up pairs, w3 / w4, s0 / s45 + top-10, fp16 / bf16): against two fused modules + torch silu / mul, 6 - 23 us
     less per pair on all 48 points (-41 .. -3.5 %).  Against one grouped launch + torch: 3.0 - 6.2 us less at 1 row, 0.9 - 3.7 us
     less at 4 rows; at 8 rows NOT faster on 11 of 16 points (every s45 + top-10 point, +2.0 .. +3.7 %; three s0 points inside
-    the spread)."""
+    the spread).
+
+    forward(x, norm_weight=None, norm_eps=1e-6).  With a `norm_weight` ([K], x's dtype and device; anything else is a
+    ValueError) x is the UN-normalised hidden state and the RMSNorm in front of the MLP is a prologue of the same kernel
+    (sqllm_gated_norm_f16 / _bf16; include/sqllm_hip.h, sqllm_rmsnorm: xn = float(x) * float(weight) * r in fp32, never
+    rounded to 16 bits, which is NOT bit-identical to a torch norm module in front -- that one rounds xn twice).  The
+    fallback and the dense route compute the same formulas in torch, in fp32 with one rounding.  `last_route` is then
+    "gated_norm".  Without a weight nothing changes: same entry point, same bits.  Speed, graph-replayed (tools/norm_front_bench.py,
+    table in DESIGN.md 4.4, raw output profiles/norm_front_bench.txt; 7B and 13B gate / up): at 1 row the prologue costs 1.5 - 4.5 us
+    where torch.nn.functional.rms_norm in front costs 4.2 - 6.2 us and the norm as the checkpoints' modules write it 17 - 20 us --
+    faster than either on all 16 points; at 4 rows NOT faster than rms_norm on 8 of 16 points (every s45 + top-10 point, +3.6 us at
+    most); at 16 rows NOT faster on any of 16 (+3.8 .. +29.2 us: every workgroup sums the squares of all its tile's rows) -- keep
+    rms_norm in front there."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
 
@@ -508,7 +553,7 @@ class QuantGatedLUTFused(nn.Module):
 
     @property
     def last_route(self):
-        """"gated", "dense" or "fallback": the way the most recent forward went (None before the first)."""
+        """"gated", "gated_norm", "dense" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def _descriptor(self, dev: int, stream: int):
@@ -529,12 +574,20 @@ class QuantGatedLUTFused(nn.Module):
         cache[(dev, stream)] = (lg[0], lu[0], entry)
         return entry
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, norm_weight=None, norm_eps: float = 1e-6) -> torch.Tensor:
         gate, up = self.gate, self.up
+        K, N = gate.infeatures, gate.outfeatures
+        if norm_weight is not None:
+            if x.shape[-1] != K:
+                raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
+            norm_weight = _check_norm_weight(x, norm_weight, K, norm_eps)
         if x.dtype not in _GATED_ENTRY or not x.is_cuda:
             self.__dict__["_last_route"] = "fallback"
+            if norm_weight is not None:  # (fp32 from end to end, one rounding)
+                xn = _torch_rmsnorm(x.reshape(-1, K), norm_weight, norm_eps)
+                y = torch.nn.functional.silu(QuantLinearLUT.forward(gate, xn).float()) * QuantLinearLUT.forward(up, xn).float()
+                return y.to(x.dtype).reshape(*x.shape[:-1], N)
             return torch.nn.functional.silu(gate(x)) * up(x)
-        K, N = gate.infeatures, gate.outfeatures
         if x.shape[-1] != K:
             raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
         x2 = x if x.dim() == 2 else x.reshape(-1, K)
@@ -544,20 +597,32 @@ class QuantGatedLUTFused(nn.Module):
         dense_min_rows = getattr(gate, "dense_min_rows", None)
         if dense_min_rows is not None and rows >= dense_min_rows:
             self.__dict__["_last_route"] = "dense"
+            if norm_weight is not None:  # (fp32 from end to end: the kernel's one rounding is the only one here too)
+                xn = _torch_rmsnorm(x2, norm_weight, norm_eps)
+                sums = []
+                for m in (gate, up):
+                    t = torch.nn.functional.linear(xn, m.dequantize(torch.float32))
+                    sums.append(t if m.bias is None else t + m.bias)
+                return (torch.nn.functional.silu(sums[0]) * sums[1]).to(x.dtype).reshape(*x.shape[:-1], N)
             dense = QuantLinearLUTFused._forward_dense
             # (the two 16-bit sums widened: activation and product in fp32, one rounding -- as the kernel evaluates them)
             return (torch.nn.functional.silu(dense(gate, x, x2).float()) * dense(up, x, x2).float()).to(x.dtype)
-        self.__dict__["_last_route"] = "gated"
+        self.__dict__["_last_route"] = "gated" if norm_weight is None else "gated_norm"
         dev = x.get_device()
         out = torch.empty((rows, N), dtype=x.dtype, device=x.device)
-        g, ref, _keep = self._descriptor(dev, quant_cuda._raw_stream(dev))
+        stream = quant_cuda._raw_stream(dev)
+        g, ref, _keep = self._descriptor(dev, stream)
         batch = 0 if rows == 1 else rows
         ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.gated_workspace_bytes(N, batch), gate.qweight.device,
                            self.GRAPH_WS_MAX_BYTES)
         g.gate.batch = g.up.batch = batch
         g.gate.vec = g.up.vec = x2.data_ptr()
         g.out, g.workspace = out.data_ptr(), ws.data_ptr()
-        quant_cuda._launch(quant_cuda._fn(_GATED_ENTRY[x.dtype]), dev, (ref,))
+        if norm_weight is not None:
+            nref = _norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps)
+            quant_cuda._launch(quant_cuda._fn(_GATED_NORM_ENTRY[x.dtype]), dev, (ref, nref))
+        else:
+            quant_cuda._launch(quant_cuda._fn(_GATED_ENTRY[x.dtype]), dev, (ref,))
         return out.reshape(*x.shape[:-1], N)
 
 
@@ -647,7 +712,18 @@ class QuantQKVRopeFused(nn.Module):
     Speed, graph-replayed on an MI355X (tools/qkv_rope_bench.py, table in DESIGN.md 4.4, raw output profiles/qkv_rope_bench.txt;
     K = 4096, head_dim 128, 3 x 4096 and 4096 + 2 x 1024, w3 / w4, s0 / s45 + top-10, fp16 / bf16, 1 / 4 / 16 rows): 28 - 40 us
     less per layer than one grouped launch + the rotary step in torch (-79 .. -34 %), 37 - 75 us less than three fused modules +
-    the same step; faster on all 48 points."""
+    the same step; faster on all 48 points.
+
+    forward(x, positions, cos, sin, norm_weight=None, norm_eps=1e-6).  With a `norm_weight` ([K], x's dtype and device;
+    anything else is a ValueError) x is the UN-normalised hidden state and the RMSNorm in front of the attention is a
+    prologue of the same kernel (sqllm_qkv_rope_norm_f16 / _bf16; include/sqllm_hip.h, sqllm_rmsnorm: xn in fp32, never
+    rounded to 16 bits -- NOT bit-identical to a torch norm module in front).  The fallback and the dense route compute the
+    same formulas in torch, in fp32 with one rounding; `last_route` is then "qkv_rope_norm".  Without a weight nothing
+    changes: same entry point, same bits.  Speed, graph-replayed (tools/norm_front_bench.py, table in DESIGN.md 4.4, raw output
+    profiles/norm_front_bench.txt; 7B and 13B q / k / v): at 1 row the prologue costs 0.7 - 3.0 us where
+    torch.nn.functional.rms_norm in front costs 4.3 - 5.9 us and the norm as the checkpoints' modules write it 18 - 21 us -- faster
+    than either on all 16 points; at 4 rows NOT faster than rms_norm on 2 of 16 points (+0.4 us at most); at 16 rows NOT faster on
+    any of 16 (+2.4 .. +22.0 us: every workgroup sums the squares of all its tile's rows) -- keep rms_norm in front there."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
 
@@ -670,7 +746,7 @@ class QuantQKVRopeFused(nn.Module):
 
     @property
     def last_route(self):
-        """"qkv_rope", "dense" or "fallback": the way the most recent forward went (None before the first)."""
+        """"qkv_rope", "qkv_rope_norm", "dense" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def _descriptor(self, dev: int, stream: int):
@@ -689,11 +765,14 @@ class QuantQKVRopeFused(nn.Module):
         cache[(dev, stream)] = (tuple(l[0] for l in ls), entry)
         return entry
 
-    def forward(self, x: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor):
+    def forward(self, x: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, norm_weight=None,
+                norm_eps: float = 1e-6):
         q, k, v = self.q, self.k, self.v
         K, D, half = q.infeatures, self.head_dim, self.head_dim // 2
         if x.shape[-1] != K:
             raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
+        if norm_weight is not None:
+            norm_weight = _check_norm_weight(x, norm_weight, K, norm_eps)
         x2 = x if x.dim() == 2 else x.reshape(-1, K)
         rows = x2.shape[0]
         for name, t in (("cos", cos), ("sin", sin)):
@@ -712,12 +791,14 @@ class QuantQKVRopeFused(nn.Module):
                     x2 = x2.contiguous()
                 # fp32 from end to end, as the epilogue's dense route: the ONE rounding of the kernel is the only one here too
                 sums = []
+                xin = x2.float() if norm_weight is None else _torch_rmsnorm(x2, norm_weight, norm_eps)
                 for m in (q, k, v):
-                    s = torch.nn.functional.linear(x2.float(), m.dequantize(torch.float32))
+                    s = torch.nn.functional.linear(xin, m.dequantize(torch.float32))
                     sums.append(s if m.bias is None else s + m.bias)
             else:
                 self.__dict__["_last_route"] = "fallback"
-                sums = [QuantLinearLUT.forward(m, x2) for m in (q, k, v)]
+                xin = x2 if norm_weight is None else _torch_rmsnorm(x2, norm_weight, norm_eps)  # (fp32 sums from fp32 xn)
+                sums = [QuantLinearLUT.forward(m, xin) for m in (q, k, v)]
             oq = _torch_rope(sums[0], pos, cos, sin, D, self.layout, x.dtype)
             ok = _torch_rope(sums[1], pos, cos, sin, D, self.layout, x.dtype)
             return oq.reshape(*lead, -1), ok.reshape(*lead, -1), sums[2].to(x.dtype).reshape(*lead, -1)
@@ -730,10 +811,11 @@ class QuantQKVRopeFused(nn.Module):
             pos = pos.to(torch.int32)  # (a kernel)
         if not pos.is_contiguous():
             pos = pos.contiguous()
-        self.__dict__["_last_route"] = "qkv_rope"
+        self.__dict__["_last_route"] = "qkv_rope" if norm_weight is None else "qkv_rope_norm"
         dev = x.get_device()
         outs = [torch.empty((rows, m.outfeatures), dtype=x.dtype, device=x.device) for m in (q, k, v)]
-        r, ref, _keep = self._descriptor(dev, quant_cuda._raw_stream(dev))
+        stream = quant_cuda._raw_stream(dev)
+        r, ref, _keep = self._descriptor(dev, stream)
         batch = 0 if rows == 1 else rows
         ws = _workspace_of(self.__dict__.setdefault("_ws", {}),
                            _lib.qkv_rope_workspace_bytes(q.outfeatures, k.outfeatures, v.outfeatures, batch), q.qweight.device,
@@ -744,7 +826,11 @@ class QuantQKVRopeFused(nn.Module):
         r.cos, r.sin, r.positions = cos.data_ptr(), sin.data_ptr(), pos.data_ptr()
         r.n_pos, r.head_dim, r.layout = cos.shape[0], D, _ROPE_LAYOUT[self.layout]
         r.workspace = ws.data_ptr()
-        quant_cuda._launch(quant_cuda._fn(_QKV_ENTRY[x.dtype]), dev, (ref,))
+        if norm_weight is not None:
+            nref = _norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps)
+            quant_cuda._launch(quant_cuda._fn(_QKV_NORM_ENTRY[x.dtype]), dev, (ref, nref))
+        else:
+            quant_cuda._launch(quant_cuda._fn(_QKV_ENTRY[x.dtype]), dev, (ref,))
         return tuple(o.reshape(*lead, -1) for o in outs)
 
 
@@ -766,6 +852,55 @@ def fuse_qkv_rope(module: nn.Module, q: str = "q_proj", k: str = "k_proj", v: st
             continue
         m.__dict__["qkv_rope"] = QuantQKVRopeFused(mq, mk, mv, d)
         n += 1
+    return n
+
+
+def _norm_of(m):
+    """(weight, eps) of an RMSNorm-like module: a `weight` and a `variance_epsilon` (or `eps`); None for anything else."""
+    w = getattr(m, "weight", None)
+    eps = getattr(m, "variance_epsilon", None)
+    if eps is None:
+        eps = getattr(m, "eps", None)
+    if not isinstance(w, torch.Tensor) or w.dim() != 1 or eps is None or getattr(m, "bias", None) is not None:
+        return None
+    return w, float(eps)
+
+
+def fuse_norm_fronts(module: nn.Module, input_norm: str = "input_layernorm", post_norm: str = "post_attention_layernorm",
+                     down_name: str = "down_proj") -> int:
+    """Hand the two RMSNorms of every decoder layer of `module` to the kernels behind them.  On every submodule that has
+      * an attribute `input_norm` -- a norm with a 1-D `weight`, no bias and a `variance_epsilon` (or `eps`) -- next to a
+        child that carries `qkv_rope` (fuse_qkv_rope), that child gets `front_norm` = (weight, eps);
+      * an attribute `post_norm` of the same kind next to a child that carries `gated` (fuse_gated_mlps), that child gets
+        `front_norm` = (weight, eps), `forward_normed(x)` = down(gated(x, weight, eps)) -- down: its attribute `down_name` -- x the UN-normalised hidden
+        state -- and, where it has `forward_residual`, `forward_normed_residual(x, residual)`.
+    The weight is attached BY REFERENCE, through `__dict__`: module tree, state dict and every existing `forward` are
+    untouched; the decoder layer's own forward chooses to call the normed forms (INTEGRATION.md shows it).  LayerNorm
+    (a bias, a mean) is not RMSNorm and is left alone.  Returns the number of fronts attached."""
+    n = 0
+    for layer in module.modules():
+        for norm_name, mark in ((input_norm, "qkv_rope"), (post_norm, "gated")):
+            nm = _norm_of(getattr(layer, norm_name, None)) if hasattr(layer, norm_name) else None
+            if nm is None:
+                continue
+            for child in layer.children():
+                fused = child.__dict__.get(mark)
+                if fused is None:
+                    continue
+                K = fused.q.infeatures if mark == "qkv_rope" else fused.gate.infeatures
+                if nm[0].numel() != K:
+                    continue
+                child.__dict__["front_norm"] = nm
+                if mark == "gated":
+                    down = getattr(child, down_name, None)  # (the layer fuse_gated_mlps put behind the gated front)
+                    if down is None:
+                        del child.__dict__["front_norm"]
+                        continue
+                    child.__dict__["forward_normed"] = (lambda g, d, nm: lambda x: d(g(x, nm[0], nm[1])))(fused, down, nm)
+                    if "forward_residual" in child.__dict__:
+                        child.__dict__["forward_normed_residual"] = (
+                            lambda g, d, nm: lambda x, residual: d(g(x, nm[0], nm[1]), residual=residual))(fused, down, nm)
+                n += 1
     return n
 
 
