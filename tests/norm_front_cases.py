@@ -152,15 +152,16 @@ EPS = 1e-6
 SMALL_ROW, MASSIVE_ROW = 3, 2
 
 
-def activations(rows, K, dtype, seed=0, massive=True):
+def activations(rows, K, dtype, seed=0, massive=True, scales=ROW_SCALES):
     """x [rows, K] and g [K] as float64 arrays of values that are exact in `dtype`: rows scaled by distinct factors (cycled),
     one of them around 2^-10 (eps = 1e-6 moves its r by tens of percent), four channels of one row around 200 (the
-    massive-activation case), g = 1 + N(0, 0.25)"""
+    massive-activation case), g = 1 + N(0, 0.25).  `scales`: the cycle of row factors (tests/test_gpu_csr_span_fronts.py passes
+    eight, one per row of the widest batch tile)"""
     import torch
 
     gen = torch.Generator().manual_seed(1234 + 17 * rows + K + seed)
     x = torch.randn((rows, K), generator=gen, dtype=torch.float64)
-    x = x * torch.tensor([ROW_SCALES[b % len(ROW_SCALES)] for b in range(rows)], dtype=torch.float64)[:, None]
+    x = x * torch.tensor([scales[b % len(scales)] for b in range(rows)], dtype=torch.float64)[:, None]
     if massive and rows > MASSIVE_ROW:
         for i, k in enumerate((1, K // 3, K // 2 + 5, K - 2)):
             x[MASSIVE_ROW, k] = (200.0 + 7 * i) * (-1) ** i

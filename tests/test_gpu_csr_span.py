@@ -7,8 +7,12 @@ linear) or kCsrSpanMax - kCsrEdge = 1792 (the gated kernels, whose last 256 accu
     fallback     n > CAP              searches in global memory, one uncounted fixed-point add per non-zero, a counting pass
 
 The suites of tests/test_gpu_linear_bf16.py and tests/test_gpu_gated.py (K = 1024, N = 456: every chunk spans about 90 rows) only
-ever run the first.  Here the layers are "span ladders": synth.make_layer's dense operands and bias at K = 512, N = 8192 with a
-CSR built from a per-row count vector (ladder_counts) whose 11 chunks span 16 ... 2211 rows.
+ever run the first, and so do those of tests/test_gpu_qkv_rope.py and tests/test_gpu_norm_front.py (N <= 456).  Here the layers
+are "span ladders": synth.make_layer's dense operands and bias at K = 512, N = 8192 with a CSR built from a per-row count vector
+(ladder_counts) whose 11 chunks span 16 ... 2211 rows.  This file runs the fp16 / bf16 linears and the gated pair on them;
+tests/test_gpu_linear_ep.py runs the epilogue linear on ladder "a"; tests/test_gpu_csr_span_fronts.py runs the attention front and
+both norm fronts (qkv_rope, gated_norm, qkv_rope_norm: CAP = 1792 like the gated pair) with this file's ladders, class model and
+helpers, which it imports.
 
 Two ladders, "a" and "b", differ in the seed and in four of the six heavy rows, so their chunk boundaries differ; they are the gate
 and the up of the gated pair, and the fp16 / bf16 linears run on BOTH of them.  The class conditions of section 1 below are
