@@ -447,6 +447,57 @@ int sqllm_qkv_rope_norm_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, 
 int sqllm_qkv_rope_norm_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attention front writing k and v straight into the KV cache: sqllm_qkv_rope_* / sqllm_qkv_rope_norm_* whose finishers
+ * store the elements of k and v into a cache as well as, or instead of, into out_k / out_v.  One kernel takes the place of
+ * the front and the two copies into the cache that follow it.
+ *
+ *   - Same values.  Everything sqllm_qkv_rope_* / sqllm_qkv_rope_norm_* specify holds word for word: the sums, the
+ *     rotation, the one rounding, the range rule, the flags, every documented corner, the workspace size and rules, and
+ *     one kernel that allocates nothing and is capturable as one kernel node.
+ *   - Where k and v go.  With s = slots[b], 0 <= s < n_slots, and column n = h * head_dim + d of member k (resp. v): the
+ *     element that out_k[b, n] receives is stored with the SAME BITS at k_cache[s * slot_stride + h * head_stride + d]
+ *     (resp. v_cache).  Offsets are 64-bit.  The cache gets exactly what the output would get, the NaN row of an
+ *     out-of-range position included.  `slots` is int32 [batch] in DEVICE memory: a captured graph follows slots the host
+ *     updates in place.
+ *   - Optional outputs.  out_k and out_v may each be NULL in these four entries: only the cache then receives that
+ *     member.  Non-NULL, both are written.  out_q stays required; q is never cached.
+ *   - Out-of-range slots.  With slots[b] outside [0, n_slots) -- the usual -1 padding -- nothing of row b is written to
+ *     either cache; row b's out_* are unaffected.  Nothing outside the addressed elements is ever written.
+ *   - Duplicate slots.  Two rows with the same slot leave, element by element, one of the two rows' values: the caller's
+ *     error, not detected.
+ *   - N_k == N_v, and head_dim divides N_v (H = N_v / head_dim kv heads).
+ *   - The two standard layouts.  Slot-major [n_slots, H, D]: slot_stride = H*D, head_stride = D; a paged
+ *     [blocks, block, H, D] is the same thing.  Head-major static [B, H, S, D]: slot = b*H*S + p, slot_stride = D,
+ *     head_stride = S*D, n_slots = (B-1)*H*S + S.  Overlapping addressing such as the second is the caller's business: the
+ *     kernel only evaluates the formula.
+ *
+ * Rejected before the device is touched: first the parent entry's own rejections (its list above, the norm's in front
+ * where there is one), in its order and with its codes, except that a NULL out_k / out_v is admitted; then
+ *   a NULL cache descriptor, k_cache, v_cache or slots                                      SQLLM_E_NULL
+ *   n_slots < 1, or a stride < head_dim                                                     SQLLM_E_SHAPE
+ *   N_k != N_v, or N_v not a multiple of head_dim                                           SQLLM_E_SHAPE
+ *   a stride at or above 2^32 that is ever multiplied (slot_stride with n_slots > 1, head_stride with H > 1: the kernel
+ *   forms its 64-bit offsets out of 32 x 32 -> 64-bit products), or an extent at or above 2^62 elements
+ *                                                                                           SQLLM_E_SHAPE
+ *   a cache extent that overlaps the other cache, the workspace, any non-NULL output, vec or the norm weight
+ *                                                                                           SQLLM_E_SHAPE
+ *   and, behind those, everything sqllm_linear_* rejects, with its codes.
+ * The extent is [base, base + (n_slots-1)*slot_stride + (H-1)*head_stride + head_dim) elements.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_kv_cache {
+  void* k_cache;          /* 16-bit elements of x's type, device memory */
+  void* v_cache;
+  const int32_t* slots;   /* int32 [batch], DEVICE memory: a captured graph follows slots updated in place */
+  int32_t n_slots;        /* >= 1 */
+  int64_t slot_stride;    /* elements between consecutive slots,            >= head_dim */
+  int64_t head_stride;    /* elements between consecutive kv heads of a slot, >= head_dim */
+} sqllm_kv_cache;
+int sqllm_qkv_rope_cache_f16(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, sqllm_stream_t stream);
+int sqllm_qkv_rope_cache_bf16(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, sqllm_stream_t stream);
+int sqllm_qkv_rope_norm_cache_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, const sqllm_kv_cache* c, sqllm_stream_t stream);
+int sqllm_qkv_rope_norm_cache_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, const sqllm_kv_cache* c, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

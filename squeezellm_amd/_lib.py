@@ -71,6 +71,14 @@ class SqllmRmsNorm(ctypes.Structure):
     _fields_ = [("weight", c_void_p), ("eps", ctypes.c_float)]
 
 
+class SqllmKvCache(ctypes.Structure):
+    """struct sqllm_kv_cache (include/sqllm_hip.h): where the cache entries of the attention front store k and v -- element
+    [slots[b] * slot_stride + head * head_stride + d] of each cache, strides in elements."""
+
+    _fields_ = [("k_cache", c_void_p), ("v_cache", c_void_p), ("slots", c_void_p), ("n_slots", ctypes.c_int32),
+                ("slot_stride", ctypes.c_int64), ("head_stride", ctypes.c_int64)]
+
+
 class SqllmQkvRope(ctypes.Structure):
     """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
 
@@ -167,6 +175,10 @@ SIGNATURES = {
     "sqllm_gated_norm_bf16": [POINTER(SqllmGated), POINTER(SqllmRmsNorm), P],
     "sqllm_qkv_rope_norm_f16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), P],
     "sqllm_qkv_rope_norm_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), P],
+    "sqllm_qkv_rope_cache_f16": [POINTER(SqllmQkvRope), POINTER(SqllmKvCache), P],
+    "sqllm_qkv_rope_cache_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmKvCache), P],
+    "sqllm_qkv_rope_norm_cache_f16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), POINTER(SqllmKvCache), P],
+    "sqllm_qkv_rope_norm_cache_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), POINTER(SqllmKvCache), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],

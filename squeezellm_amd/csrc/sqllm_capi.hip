@@ -21,6 +21,8 @@ hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* resi
 hipError_t (*g_launch_linear_qkv)(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv.hip
 hipError_t (*g_launch_linear_gated_norm)(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated_norm.hip
 hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm.hip
+hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_cache.hip
+hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm_cache.hip
 }
 
 namespace sqllm_host {
@@ -1127,6 +1129,7 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
 // `ep` (sqllm_linear_ep_*: one fused linear): activation code and residual; the launch then goes to the epilogue kernel.
 // `qkv` (sqllm_qkv_rope_*: three fused linears, q, k and v): the rotation's operands; the launch then goes to the qkv kernel.
 // `vn` (sqllm_gated_norm_* / sqllm_qkv_rope_norm_*, with `pair` / `qkv`): vec is un-normalised, the launch goes to the norm front's kernel.
+// `kc` (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*, with `qkv`): the KV cache, checked by the caller; the launch goes to the cache-writing kernel.
 struct EpilogueArgs {
   const void* residual;  // 16-bit [batch, N] of the output's type, or null
   int act;               // SQLLM_ACT_*, validated by the caller
@@ -1134,7 +1137,7 @@ struct EpilogueArgs {
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, const sqllm_linear* lin = nullptr, void* ws = nullptr, int64_t ws_bytes = 0,
                                     bool ws_entry = false, bool bf16 = false, void* pair = nullptr, const EpilogueArgs* ep = nullptr,
-                                    const sqllm::QkvRope* qkv = nullptr, const sqllm::VecNorm* vn = nullptr) {
+                                    const sqllm::QkvRope* qkv = nullptr, const sqllm::VecNorm* vn = nullptr, const sqllm::KvCache* kc = nullptr) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
   sqllm_op tmp[sqllm::kMaxSegments];
@@ -1199,6 +1202,12 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
           break;
         }
         if (qkv) {  // (sqllm_linear_qkv.hip; a missing kernel is an error here too, and the launch is not decorated either)
+          if (kc) {  // (sqllm_linear_qkv_cache.hip / sqllm_linear_qkv_norm_cache.hip)
+            if (vn) e = sqllm::g_launch_linear_qkv_norm_cache ? sqllm::g_launch_linear_qkv_norm_cache(op->bits, a, *qkv, *kc, *vn, s) : hipErrorNotSupported;
+            else
+            e = sqllm::g_launch_linear_qkv_cache ? sqllm::g_launch_linear_qkv_cache(op->bits, a, *qkv, *kc, s) : hipErrorNotSupported;
+            break;
+          }
           if (vn) e = sqllm::g_launch_linear_qkv_norm ? sqllm::g_launch_linear_qkv_norm(op->bits, a, *qkv, *vn, s) : hipErrorNotSupported;
           else
           e = sqllm::g_launch_linear_qkv ? sqllm::g_launch_linear_qkv(op->bits, a, *qkv, s) : hipErrorNotSupported;
@@ -1371,9 +1380,48 @@ int64_t sqllm_qkv_rope_workspace_bytes(const sqllm_op* q, const sqllm_op* k, con
          qkv_pair_bytes(k);
 }
 
+// two byte ranges that share a byte
+static bool ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), b0 = reinterpret_cast<uintptr_t>(q);
+  return a0 < b0 + (uintptr_t)q_bytes && b0 < a0 + (uintptr_t)p_bytes;
+}
+
+// The cache entries' own checks (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*): the descriptor `c` against the call `r` it
+// comes with, which has passed launch_qkv_rope's own checks -- behind those and in front of the linear's validation, to which
+// widths it is about to reject are left (`widths_ok`).
+static int check_kv_cache(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, const sqllm_rmsnorm* nm, bool widths_ok) {
+  if (!c || !c->k_cache || !c->v_cache || !c->slots) return SQLLM_E_NULL;
+  const int64_t D = r->head_dim;
+  if (c->n_slots < 1 || c->slot_stride < D || c->head_stride < D) return SQLLM_E_SHAPE;
+  if (!widths_ok) return SQLLM_OK;
+  if (r->k.N != r->v.N || r->v.N % D) return SQLLM_E_SHAPE;
+  const int64_t H = r->v.N / D;
+  // the kernel forms its 64-bit offsets out of 32 x 32 -> 64-bit products: a stride that is ever multiplied lies below 2^32
+  if ((c->n_slots > 1 && c->slot_stride >= (1ll << 32)) || (H > 1 && c->head_stride >= (1ll << 32))) return SQLLM_E_SHAPE;
+  // (in 128 bits: strides up to 2^63 are still to be rejected by the overlap rule, not to wrap)
+  const unsigned __int128 extent = (unsigned __int128)(c->n_slots - 1) * (uint64_t)c->slot_stride + (unsigned __int128)(H - 1) * (uint64_t)c->head_stride + (uint64_t)D;
+  if (extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
+  const int64_t bytes = 2 * (int64_t)extent;
+  const int64_t rows = r->q.batch <= 0 ? 1 : r->q.batch;
+  if (ranges_overlap(c->k_cache, bytes, c->v_cache, bytes)) return SQLLM_E_SHAPE;
+  void* const cache[2] = {c->k_cache, c->v_cache};
+  const void* const out[3] = {r->out_q, r->out_k, r->out_v};
+  const int64_t out_bytes[3] = {2 * rows * r->q.N, 2 * rows * r->k.N, 2 * rows * r->v.N};
+  for (int i = 0; i < 2; ++i) {
+    if (ranges_overlap(cache[i], bytes, r->workspace, sqllm_qkv_rope_workspace_bytes(&r->q, &r->k, &r->v))) return SQLLM_E_SHAPE;
+    for (int j = 0; j < 3; ++j)
+      if (out[j] && ranges_overlap(cache[i], bytes, out[j], out_bytes[j])) return SQLLM_E_SHAPE;
+    if (r->q.vec && r->q.K > 0 && ranges_overlap(cache[i], bytes, r->q.vec, 2 * rows * r->q.K)) return SQLLM_E_SHAPE;
+    if (nm && r->q.K > 0 && norm_weight_overlaps(nm, r->q.K, cache[i], bytes)) return SQLLM_E_SHAPE;
+  }
+  return SQLLM_OK;
+}
+
 // q, k and v as the three-op group of the fused linear (same route, plan and validation), finished by the qkv kernel
 // `nm` (sqllm_qkv_rope_norm_*): vec is the un-normalised hidden state and the kernel is the norm front's
-static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool bf16, const sqllm_rmsnorm* nm = nullptr) {
+// `cache_entry` (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*): k and v go to the KV cache `c`, and out_k / out_v may be NULL
+static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool bf16, const sqllm_rmsnorm* nm = nullptr, bool cache_entry = false,
+                           const sqllm_kv_cache* c = nullptr) {
   if (!r) return SQLLM_E_NULL;
   const sqllm_op* m[3] = {&r->q, &r->k, &r->v};
   void* const out[3] = {r->out_q, r->out_k, r->out_v};
@@ -1382,7 +1430,7 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
     if (m[i]->vec != m[0]->vec || m[i]->K != m[0]->K || m[i]->bits != m[0]->bits || m[i]->batch != m[0]->batch) return SQLLM_E_GROUP;
   }
   if (r->layout != SQLLM_ROPE_HALF && r->layout != SQLLM_ROPE_INTERLEAVED) return SQLLM_E_OPTION;
-  if (!r->out_q || !r->out_k || !r->out_v || !r->cos || !r->sin || !r->positions || !r->workspace) return SQLLM_E_NULL;
+  if (!r->out_q || (!cache_entry && (!r->out_k || !r->out_v)) || !r->cos || !r->sin || !r->positions || !r->workspace) return SQLLM_E_NULL;
   if ((reinterpret_cast<uintptr_t>(r->workspace) & 15u) != 0) return SQLLM_E_ALIGN;
   const int D = r->head_dim;
   if (D < 2 || (D & 1) || r->n_pos < 1) return SQLLM_E_SHAPE;
@@ -1397,9 +1445,11 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
     const int64_t ws_bytes = sqllm_qkv_rope_workspace_bytes(&r->q, &r->k, &r->v);
     const uintptr_t w0 = reinterpret_cast<uintptr_t>(r->workspace);
     for (int i = 0; i < 3; ++i) {
+      if (!out[i]) continue;  // (a cache entry without this output)
       const uintptr_t a0 = reinterpret_cast<uintptr_t>(out[i]), a1 = a0 + 2u * (uintptr_t)rows * (uintptr_t)m[i]->N;
       if (a0 < w0 + (uintptr_t)ws_bytes && w0 < a1) return SQLLM_E_SHAPE;
       for (int j = 0; j < i; ++j) {
+        if (!out[j]) continue;
         const uintptr_t b0 = reinterpret_cast<uintptr_t>(out[j]), b1 = b0 + 2u * (uintptr_t)rows * (uintptr_t)m[j]->N;
         if (a0 < b1 && b0 < a1) return SQLLM_E_SHAPE;
       }
@@ -1407,12 +1457,27 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
     }
     if (nm && m[0]->K > 0 && norm_weight_overlaps(nm, m[0]->K, r->workspace, ws_bytes)) return SQLLM_E_SHAPE;
   }
+  sqllm::KvCache kc = {};
+  if (cache_entry) {
+    const int rc = check_kv_cache(r, c, nm, r->q.N > 0 && r->k.N > 0 && r->v.N > 0);
+    if (rc != SQLLM_OK) return rc;
+    kc.k_cache = c->k_cache;
+    kc.v_cache = c->v_cache;
+    kc.slots = c->slots;
+    kc.n_slots = c->n_slots;
+    kc.slot_stride = c->slot_stride;
+    kc.head_stride = c->head_stride;
+    kc.write_out_k = r->out_k != nullptr;
+    kc.write_out_v = r->out_v != nullptr;
+  }
   sqllm_linear lin[3];
   char* ws = static_cast<char*>(r->workspace);
   const float* bias[3] = {r->bias_q, r->bias_k, r->bias_v};
   for (int i = 0; i < 3; ++i) {
     lin[i].op = *m[i];
-    lin[i].op.mul = static_cast<float*>(out[i]);  // (what the linear's validation and fill_args read as the output)
+    // (what the linear's validation and fill_args read as the output.  A cache entry without this output: the workspace
+    // stands in for the validation, and the launcher takes it out again -- KvCache::write_out_*, sqllm_cache_finish.h)
+    lin[i].op.mul = static_cast<float*>(out[i] ? out[i] : r->workspace);
     lin[i].bias = bias[i];
     lin[i].workspace = ws;
     ws += sqllm_linear_workspace_bytes(m[i]);
@@ -1426,11 +1491,12 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
   qr.n_pos = r->n_pos;
   qr.head_dim = D;
   qr.interleaved = r->layout == SQLLM_ROPE_INTERLEAVED;
+  const sqllm::KvCache* kcp = cache_entry ? &kc : nullptr;
   if (nm) {
     const sqllm::VecNorm vn = {nm->weight, nm->eps};
-    return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr, &vn);
+    return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr, &vn, kcp);
   }
-  return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr);
+  return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr, nullptr, kcp);
 }
 
 int sqllm_qkv_rope_f16(const sqllm_qkv_rope* r, sqllm_stream_t stream) { return launch_qkv_rope(r, stream, false); }
@@ -1443,6 +1509,21 @@ int sqllm_qkv_rope_norm_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, sq
 int sqllm_qkv_rope_norm_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, sqllm_stream_t stream) {
   const int rc = check_rmsnorm(nm);
   return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, true, nm);
+}
+
+int sqllm_qkv_rope_cache_f16(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, sqllm_stream_t stream) {
+  return launch_qkv_rope(r, stream, false, nullptr, true, c);
+}
+int sqllm_qkv_rope_cache_bf16(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, sqllm_stream_t stream) {
+  return launch_qkv_rope(r, stream, true, nullptr, true, c);
+}
+int sqllm_qkv_rope_norm_cache_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, const sqllm_kv_cache* c, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, false, nm, true, c);
+}
+int sqllm_qkv_rope_norm_cache_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, const sqllm_kv_cache* c, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, true, nm, true, c);
 }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {

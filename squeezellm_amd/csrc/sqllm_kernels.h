@@ -168,6 +168,19 @@ struct VecNorm {
 };
 extern hipError_t (*g_launch_linear_gated_norm)(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream);
 extern hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream);
+// the attention front writing k and v into a KV cache (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*): the two q/k/v launches
+// above on the kernels of sqllm_linear_qkv_cache.hip / sqllm_linear_qkv_norm_cache.hip, whose finishers store the elements of
+// k and v at cache + slots[b] * slot_stride + head * head_stride + d as well as, or instead of, in the outputs.  Hooks, as above.
+struct KvCache {
+  void* k_cache;         // 16-bit elements of the outputs' type, device memory
+  void* v_cache;
+  const int* slots;      // int32 [batch], device memory
+  int n_slots;
+  int64_t slot_stride, head_stride;  // in elements
+  bool write_out_k, write_out_v;     // false: the caller gave no such output, and the segment's out16 is a stand-in to be ignored
+};
+extern hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream);
+extern hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

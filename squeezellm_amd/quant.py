@@ -688,6 +688,55 @@ def _torch_rope(s: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin
     return out.reshape(rows, N).to(dtype)
 
 
+_QKV_CACHE_ENTRY = {torch.float16: "sqllm_qkv_rope_cache_f16", torch.bfloat16: "sqllm_qkv_rope_cache_bf16"}
+_QKV_NORM_CACHE_ENTRY = {torch.float16: "sqllm_qkv_rope_norm_cache_f16", torch.bfloat16: "sqllm_qkv_rope_norm_cache_bf16"}
+
+
+def kv_cache_view(cache: torch.Tensor, layout: str = "nhd") -> torch.Tensor:
+    """The 3-D view [n_slots, H_kv, head_dim] of a KV cache that QuantQKVRopeFused.forward takes as `k_cache` / `v_cache`
+    (no copy; strides 0 and 1 of the view become slot_stride and head_stride of include/sqllm_hip.h, sqllm_kv_cache).
+      "nhd":  slot-major [n_slots, H, D], or paged [blocks, block, H, D] with slot = block_index * block + offset;
+      "bhsd": head-major static [B, H, S, D] with slot = b * H * S + p (static_cache_slots): an OVERLAPPING as_strided view
+              of H rows S * D apart for each of (B - 1) * H * S + S slots D apart."""
+    if cache.stride(-1) != 1:
+        raise ValueError("the last dimension of a KV cache must be contiguous")
+    if layout == "nhd":
+        if cache.dim() == 3:
+            return cache
+        if cache.dim() == 4 and cache.stride(0) == cache.shape[1] * cache.stride(1):
+            return cache.as_strided((cache.shape[0] * cache.shape[1], cache.shape[2], cache.shape[3]), (cache.stride(1), cache.stride(2), 1),
+                                    cache.storage_offset())
+        raise ValueError(f"an 'nhd' cache is [n_slots, H, D] or a paged [blocks, block, H, D] whose blocks lie block * stride(1) apart, got "
+                         f"{tuple(cache.shape)} with strides {cache.stride()}")
+    if layout == "bhsd":
+        if cache.dim() != 4 or not cache.is_contiguous():
+            raise ValueError(f"a 'bhsd' cache is a contiguous [B, H, S, D], got {tuple(cache.shape)} with strides {cache.stride()}")
+        B, H, S, D = cache.shape
+        return cache.as_strided(((B - 1) * H * S + S, H, D), (D, S * D, 1), cache.storage_offset())
+    raise ValueError(f"layout must be 'nhd' or 'bhsd', got {layout!r}")
+
+
+def static_cache_slots(positions: torch.Tensor, n_kv_heads: int, max_seq: int) -> torch.Tensor:
+    """int32 slots of a head-major static cache [B, H, S, D] seen through kv_cache_view(cache, "bhsd"): row b at position p
+    goes to slot b * H * S + p.  (A position outside [0, S) would land in a neighbouring head's or row's slots: it gets -1,
+    an out-of-range slot, which writes nothing.)"""
+    p = positions.reshape(-1).long()
+    slot = torch.arange(p.numel(), device=p.device) * (int(n_kv_heads) * int(max_seq)) + p
+    return torch.where((p >= 0) & (p < max_seq), slot, torch.full_like(slot, -1)).to(torch.int32)
+
+
+def _torch_cache_write(cache: torch.Tensor, slots: torch.Tensor, rows_: torch.Tensor) -> None:
+    """cache[slots[b]] = rows_[b] for the slots inside [0, n_slots), in torch (the dense and fallback routes): by element
+    offsets into a flat view of the cache's extent, so that an overlapping as_strided view (kv_cache_view "bhsd") works too."""
+    n_slots, H, D = cache.shape
+    s = slots.reshape(-1).long()
+    ok = (s >= 0) & (s < n_slots)
+    ss, hs = cache.stride(0), cache.stride(1)
+    flat = cache.as_strided(((n_slots - 1) * ss + (H - 1) * hs + D,), (1,), cache.storage_offset())
+    at = (s[ok][:, None, None] * ss + torch.arange(H, device=s.device)[None, :, None] * hs + torch.arange(D, device=s.device)[None, None, :])
+    flat.index_put_((at.reshape(-1),), rows_.reshape(-1, H, D)[ok].reshape(-1))
+
+
 class QuantQKVRopeFused(nn.Module):
     """q_proj, k_proj, v_proj and the rotary position embedding of q and k for fp16 and bf16 GPU activations as ONE kernel
     (sqllm_qkv_rope_f16 / _bf16) instead of one grouped launch and the string of torch element-wise kernels behind it (the
@@ -723,7 +772,21 @@ class QuantQKVRopeFused(nn.Module):
     profiles/norm_front_bench.txt; 7B and 13B q / k / v): at 1 row the prologue costs 0.7 - 3.0 us where
     torch.nn.functional.rms_norm in front costs 4.3 - 5.9 us and the norm as the checkpoints' modules write it 18 - 21 us -- faster
     than either on all 16 points; at 4 rows NOT faster than rms_norm on 2 of 16 points (+0.4 us at most); at 16 rows NOT faster on
-    any of 16 (+2.4 .. +22.0 us: every workgroup sums the squares of all its tile's rows) -- keep rms_norm in front there."""
+    any of 16 (+2.4 .. +22.0 us: every workgroup sums the squares of all its tile's rows) -- keep rms_norm in front there.
+
+    forward(..., k_cache=None, v_cache=None, slots=None, return_kv=True).  With a KV cache the same kernel stores k and v
+    into it as their columns finish (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*; include/sqllm_hip.h, sqllm_kv_cache):
+    row b's k and v go to k_cache[slots[b]] and v_cache[slots[b]], bit for bit what the returned k and v hold.  `k_cache`,
+    `v_cache`: 3-D views [n_slots, H_kv, head_dim] (kv_cache_view) of x's dtype and device, of equal shape and strides,
+    stride(-1) == 1, H_kv * head_dim == N_k == N_v; overlapping as_strided views are allowed.  `slots`: one per row, int32 on
+    x's device, used WITHOUT a copy (int64 is converted, which costs a kernel, as for positions); a slot outside
+    [0, n_slots) -- the usual -1 padding -- writes nothing; two rows with one slot leave one of the two rows' values.  All three
+    or none: anything else is a ValueError.  `return_kv=False` (only with a cache): k and v go to the cache alone and the call
+    returns (q, None, None).  The dense and fallback routes make the same writes in torch; `last_route` is unchanged.  What it
+    saves, graph-replayed (tools/kv_cache_bench.py, table in DESIGN.md 4.4, raw output profiles/kv_cache_bench.txt; the shapes of
+    qkv_rope_bench.py, a slot-major cache): two index_copy_ behind the parent cost 5.6 - 7.2 us per layer at any row count, the
+    scattered stores 0.1 - 0.4 us at 1 row and 1.4 - 4.4 us at 16 -- 5.4 - 6.1 us less per layer at 1 row, 2.7 - 5.3 us less at 16,
+    faster than the copies on all 48 points."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
 
@@ -765,8 +828,36 @@ class QuantQKVRopeFused(nn.Module):
         cache[(dev, stream)] = (tuple(l[0] for l in ls), entry)
         return entry
 
+    def _check_cache(self, x: torch.Tensor, rows: int, k_cache, v_cache, slots, return_kv: bool) -> bool:
+        """The cache arguments of forward: all three or none, and the views as the class docstring wants them."""
+        given = [t is not None for t in (k_cache, v_cache, slots)]
+        if not any(given):
+            if not return_kv:
+                raise ValueError("return_kv=False needs a KV cache: k and v would go nowhere")
+            return False
+        if not all(given):
+            raise ValueError("k_cache, v_cache and slots go together: give all three or none")
+        D, N = self.head_dim, self.k.outfeatures
+        if self.v.outfeatures != N:
+            raise ValueError(f"a KV cache needs k and v of one width, got {N} and {self.v.outfeatures}")
+        for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if not isinstance(t, torch.Tensor) or t.dtype != x.dtype or t.device != x.device:
+                raise ValueError(f"{name} must be a {x.dtype} tensor on {x.device}, got {getattr(t, 'dtype', type(t).__name__)} on "
+                                 f"{getattr(t, 'device', None)}")
+            if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] * t.shape[2] != N or t.shape[2] != D or t.stride(2) != 1:
+                raise ValueError(f"{name} must be a view [n_slots, {N // D}, {D}] with a contiguous last dimension, got {tuple(t.shape)} "
+                                 f"with strides {t.stride()}")
+        if k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride():
+            raise ValueError(f"k_cache and v_cache must have equal shape and strides, got {tuple(k_cache.shape)} / {k_cache.stride()} and "
+                             f"{tuple(v_cache.shape)} / {v_cache.stride()}")
+        if k_cache.stride(0) < D or (k_cache.stride(1) < D and k_cache.shape[1] > 1):
+            raise ValueError(f"the strides of a cache view must be at least head_dim = {D}, got {k_cache.stride()}")
+        if not isinstance(slots, torch.Tensor) or slots.dtype not in (torch.int32, torch.int64) or slots.numel() != rows or slots.device != x.device:
+            raise ValueError(f"slots must be {rows} int32 (or int64) values on {x.device}")
+        return True
+
     def forward(self, x: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, norm_weight=None,
-                norm_eps: float = 1e-6):
+                norm_eps: float = 1e-6, k_cache=None, v_cache=None, slots=None, return_kv: bool = True):
         q, k, v = self.q, self.k, self.v
         K, D, half = q.infeatures, self.head_dim, self.head_dim // 2
         if x.shape[-1] != K:
@@ -775,6 +866,7 @@ class QuantQKVRopeFused(nn.Module):
             norm_weight = _check_norm_weight(x, norm_weight, K, norm_eps)
         x2 = x if x.dim() == 2 else x.reshape(-1, K)
         rows = x2.shape[0]
+        cached = self._check_cache(x, rows, k_cache, v_cache, slots, return_kv)
         for name, t in (("cos", cos), ("sin", sin)):
             if t.dim() != 2 or t.shape[1] != half or t.shape[0] < 1 or t.shape != cos.shape or t.device != x.device:
                 raise ValueError(f"{name} must be [n_pos, {half}] on {x.device}, got {tuple(t.shape)} on {t.device}")
@@ -801,7 +893,13 @@ class QuantQKVRopeFused(nn.Module):
                 sums = [QuantLinearLUT.forward(m, xin) for m in (q, k, v)]
             oq = _torch_rope(sums[0], pos, cos, sin, D, self.layout, x.dtype)
             ok = _torch_rope(sums[1], pos, cos, sin, D, self.layout, x.dtype)
-            return oq.reshape(*lead, -1), ok.reshape(*lead, -1), sums[2].to(x.dtype).reshape(*lead, -1)
+            ov = sums[2].to(x.dtype)
+            if cached:
+                _torch_cache_write(k_cache, slots, ok)
+                _torch_cache_write(v_cache, slots, ov)
+                if not return_kv:
+                    return oq.reshape(*lead, -1), None, None
+            return oq.reshape(*lead, -1), ok.reshape(*lead, -1), ov.reshape(*lead, -1)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
         if cos.dtype != torch.float32 or sin.dtype != torch.float32 or not cos.is_contiguous() or not sin.is_contiguous():
@@ -813,7 +911,7 @@ class QuantQKVRopeFused(nn.Module):
             pos = pos.contiguous()
         self.__dict__["_last_route"] = "qkv_rope" if norm_weight is None else "qkv_rope_norm"
         dev = x.get_device()
-        outs = [torch.empty((rows, m.outfeatures), dtype=x.dtype, device=x.device) for m in (q, k, v)]
+        outs = [torch.empty((rows, m.outfeatures), dtype=x.dtype, device=x.device) if return_kv or m is q else None for m in (q, k, v)]
         stream = quant_cuda._raw_stream(dev)
         r, ref, _keep = self._descriptor(dev, stream)
         batch = 0 if rows == 1 else rows
@@ -822,16 +920,35 @@ class QuantQKVRopeFused(nn.Module):
                            self.GRAPH_WS_MAX_BYTES)
         r.q.batch = r.k.batch = r.v.batch = batch
         r.q.vec = r.k.vec = r.v.vec = x2.data_ptr()
-        r.out_q, r.out_k, r.out_v = outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr()
+        r.out_q, r.out_k, r.out_v = [o.data_ptr() if o is not None else None for o in outs]
         r.cos, r.sin, r.positions = cos.data_ptr(), sin.data_ptr(), pos.data_ptr()
         r.n_pos, r.head_dim, r.layout = cos.shape[0], D, _ROPE_LAYOUT[self.layout]
         r.workspace = ws.data_ptr()
-        if norm_weight is not None:
-            nref = _norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps)
+        nref = None if norm_weight is None else _norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps)
+        if cached:
+            sl = slots.reshape(-1)
+            if sl.dtype != torch.int32:
+                sl = sl.to(torch.int32)  # (a kernel)
+            if not sl.is_contiguous():
+                sl = sl.contiguous()
+            kcs = self.__dict__.setdefault("_kv", {})
+            hit = kcs.get((dev, stream))
+            if hit is None:
+                c = _lib.SqllmKvCache()
+                hit = kcs[(dev, stream)] = (c, ctypes.byref(c))
+            c, cref = hit
+            c.k_cache, c.v_cache, c.slots = k_cache.data_ptr(), v_cache.data_ptr(), sl.data_ptr()
+            c.n_slots, c.slot_stride = k_cache.shape[0], k_cache.stride(0)
+            c.head_stride = k_cache.stride(1) if k_cache.shape[1] > 1 else D  # (one head: its stride is anything, and never used)
+            if nref is not None:
+                quant_cuda._launch(quant_cuda._fn(_QKV_NORM_CACHE_ENTRY[x.dtype]), dev, (ref, nref, cref))
+            else:
+                quant_cuda._launch(quant_cuda._fn(_QKV_CACHE_ENTRY[x.dtype]), dev, (ref, cref))
+        elif nref is not None:
             quant_cuda._launch(quant_cuda._fn(_QKV_NORM_ENTRY[x.dtype]), dev, (ref, nref))
         else:
             quant_cuda._launch(quant_cuda._fn(_QKV_ENTRY[x.dtype]), dev, (ref,))
-        return tuple(o.reshape(*lead, -1) for o in outs)
+        return tuple(o.reshape(*lead, -1) if o is not None else None for o in outs)
 
 
 def fuse_qkv_rope(module: nn.Module, q: str = "q_proj", k: str = "k_proj", v: str = "v_proj", head_dim=None) -> int:
