@@ -498,6 +498,69 @@ int sqllm_qkv_rope_norm_cache_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* 
 int sqllm_qkv_rope_norm_cache_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, const sqllm_kv_cache* c, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Decode attention over the KV cache the attention front writes: ONE new query per sequence, attending to the keys the
+ * cache holds for that sequence.  The consumer of sqllm_kv_cache's layout; the step between the front's out_q and o_proj.
+ *
+ *   - Addressing.  Key p of row b lives in slot  block_table[b, p / block_size] * block_size + p % block_size  (64-bit), and
+ *     element (slot, kv head h, d) at slot*slot_stride + h*head_stride + d of k_cache / v_cache, as in sqllm_kv_cache.  One
+ *     form covers both layouts of the front: a paged [blocks, block, H, D] takes the usual table; the head-major static
+ *     [B, H, S, D] (slot_stride = D, head_stride = S*D) takes block_size = S, max_blocks = 1, block_table[b, 0] = b * H,
+ *     which is slot = b*H*S + p.  block_size is any positive int32, not only a power of two.  block_table and seq_lens are
+ *     DEVICE memory: a captured graph follows lengths and tables updated in place.  seq_lens[b] = position + 1 when the
+ *     front wrote the new token in the same step: the new key attends to itself.
+ *   - Values.  Query head h uses kv head h / (n_q_heads / n_kv_heads).  For the keys p = 0 .. seq_lens[b]-1:
+ *         s[p]      = scale * sum_d float(q[d]) * float(k[p,d])          fp32
+ *         m         = max_p s[p],   w[p] = expf(s[p] - m)                fp32, max-subtracted
+ *         out[d]    = (sum_p w[p] * float(v[p,d])) / (sum_p w[p])        fp32, rounded ONCE to the output type
+ *   - Order.  The sequence is cut into partitions of SQLLM_ATTN_PARTITION = 256 keys (keys [256 i, 256 i + 256)); every
+ *     partition is reduced in an order that depends on head_dim, n_q_heads / n_kv_heads and the keys' indices alone, and the
+ *     partitions' (max, sum, acc) are combined in ascending partition order.  Row b's output bits are a function of row b's
+ *     own operands and the descriptor's shape fields only: not of the other rows, not of the batch size, not of timing;
+ *     bit-identical run to run.  Launch geometry depends on host fields (max_blocks * block_size) and never on device data.
+ *   - Slots not addressed by (block_table, seq_lens) are never read in a way that can influence a result: whatever bits
+ *     they hold, NaN included, the output bits are the same.  Nothing outside the cache extent is ever read.
+ *   - Nothing but out[b, 0 .. n_q_heads*head_dim) of every row and the workspace is written.
+ *   - seq_lens[b] <= 0: the row of out is +0.
+ *   - Row b of out is NaN for all heads when seq_lens[b] > max_blocks * block_size, or when a table entry used by row b
+ *     addresses any slot outside [0, n_slots) -- the front's rule for an out-of-range position.
+ *   - A NaN among the attended elements of q or k makes that head's outputs NaN.  A NaN in attended v[p, d] makes column d
+ *     of the heads of that kv group NaN.  Infinities follow IEEE arithmetic on the formulas above (an infinite score gives
+ *     inf - inf) and are not pinned further.
+ *   - Workspace: sqllm_attn_decode_workspace_bytes() bytes, 4-byte aligned, CONTENTS IRRELEVANT: every word that is read
+ *     was written by the same call.  (max, sum, acc[head_dim]) in fp32 per (row, query head, partition).
+ *   - Each call allocates nothing and is capturable: TWO kernel nodes (partials, then combine), ONE when
+ *     max_blocks * block_size <= SQLLM_ATTN_PARTITION.
+ *
+ * Served: head_dim 64 or 128; n_q_heads a multiple of n_kv_heads with a ratio of 1 to 8; batch 1 to 64; anything else is
+ * SQLLM_E_SHAPE.  Rejected before the device is touched, in this order:
+ *   a NULL descriptor, q, out, k_cache, v_cache, block_table, seq_lens or workspace          SQLLM_E_NULL
+ *   a count < 1 (batch, heads, head_dim, n_slots, block_size, max_blocks, table_stride); slot_stride or head_stride
+ *   < head_dim; q_stride or out_stride < n_q_heads*head_dim; max_blocks > table_stride; a shape that is not served; a
+ *   stride at or above 2^32 that is ever multiplied, or an extent at or above 2^62 elements, as for sqllm_kv_cache
+ *                                                                                           SQLLM_E_SHAPE
+ *   a scale that is not finite                                                              SQLLM_E_OPTION
+ *   out or the workspace overlapping q, a cache, block_table, seq_lens or each other         SQLLM_E_SHAPE
+ *   q, out, k_cache or v_cache not aligned to 2 bytes, the workspace not to 4                SQLLM_E_ALIGN
+ * ------------------------------------------------------------------------------------------- */
+#define SQLLM_ATTN_PARTITION 256
+typedef struct sqllm_attn_decode {
+  const void* q;            /* 16-bit [batch, n_q_heads * head_dim], row stride q_stride elements: the front's out_q */
+  void* out;                /* 16-bit [batch, n_q_heads * head_dim], row stride out_stride; OVERWRITTEN; what o_proj reads */
+  const void* k_cache;      /* as sqllm_kv_cache: element (slot, kv head h, d) at slot*slot_stride + h*head_stride + d */
+  const void* v_cache;
+  const int32_t* block_table; /* int32 [batch, table_stride], DEVICE memory */
+  const int32_t* seq_lens;    /* int32 [batch], DEVICE memory: keys 0 .. seq_lens[b]-1 of row b are attended */
+  int32_t batch, n_q_heads, n_kv_heads, head_dim;
+  int32_t n_slots, block_size, max_blocks, table_stride;   /* max_blocks <= table_stride */
+  int64_t slot_stride, head_stride, q_stride, out_stride;
+  float scale;              /* the caller's, usually 1/sqrt(head_dim); finite */
+  void* workspace;          /* sqllm_attn_decode_workspace_bytes(); contents irrelevant */
+} sqllm_attn_decode;
+int64_t sqllm_attn_decode_workspace_bytes(int32_t batch, int32_t n_q_heads, int32_t head_dim, int32_t max_blocks, int32_t block_size);
+int sqllm_attn_decode_f16(const sqllm_attn_decode* a, sqllm_stream_t stream);
+int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

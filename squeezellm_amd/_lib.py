@@ -79,6 +79,20 @@ class SqllmKvCache(ctypes.Structure):
                 ("slot_stride", ctypes.c_int64), ("head_stride", ctypes.c_int64)]
 
 
+ATTN_PARTITION = 256  # SQLLM_ATTN_PARTITION: keys per partition of the decode attention
+
+
+class SqllmAttnDecode(ctypes.Structure):
+    """struct sqllm_attn_decode (include/sqllm_hip.h): one query per row over the KV cache of sqllm_kv_cache's layout -- key p
+    of row b in slot block_table[b, p / block_size] * block_size + p % block_size; strides in elements."""
+
+    _fields_ = [("q", c_void_p), ("out", c_void_p), ("k_cache", c_void_p), ("v_cache", c_void_p), ("block_table", c_void_p),
+                ("seq_lens", c_void_p), ("batch", c_int32), ("n_q_heads", c_int32), ("n_kv_heads", c_int32), ("head_dim", c_int32),
+                ("n_slots", c_int32), ("block_size", c_int32), ("max_blocks", c_int32), ("table_stride", c_int32),
+                ("slot_stride", ctypes.c_int64), ("head_stride", ctypes.c_int64), ("q_stride", ctypes.c_int64),
+                ("out_stride", ctypes.c_int64), ("scale", ctypes.c_float), ("workspace", c_void_p)]
+
+
 class SqllmQkvRope(ctypes.Structure):
     """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
 
@@ -179,6 +193,9 @@ SIGNATURES = {
     "sqllm_qkv_rope_cache_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmKvCache), P],
     "sqllm_qkv_rope_norm_cache_f16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), POINTER(SqllmKvCache), P],
     "sqllm_qkv_rope_norm_cache_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), POINTER(SqllmKvCache), P],
+    "sqllm_attn_decode_workspace_bytes": [c_int32, c_int32, c_int32, c_int32, c_int32],
+    "sqllm_attn_decode_f16": [POINTER(SqllmAttnDecode), P],
+    "sqllm_attn_decode_bf16": [POINTER(SqllmAttnDecode), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],
@@ -228,7 +245,7 @@ def load() -> ctypes.CDLL:
         fn.restype = (c_char_p if name == "sqllm_error_string" else
                       ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes",
                                                "sqllm_select_workspace_bytes", "sqllm_gated_workspace_bytes",
-                                               "sqllm_qkv_rope_workspace_bytes") else c_int)
+                                               "sqllm_qkv_rope_workspace_bytes", "sqllm_attn_decode_workspace_bytes") else c_int)
     if lib.sqllm_abi_version() != 1:
         raise RuntimeError(f"libsqllm_hip.so ABI {lib.sqllm_abi_version()} != 1 expected by this package")
     _lib = lib
@@ -282,6 +299,11 @@ def qkv_rope_workspace_bytes(n_q: int, n_k: int, n_v: int, batch: int = 0) -> in
     """Bytes of zero-filled device memory one q/k/v rotary launch of these widths needs (no GPU needed)."""
     ops = [SqllmOp(N=n, batch=batch) for n in (n_q, n_k, n_v)]
     return int(load().sqllm_qkv_rope_workspace_bytes(*[ctypes.byref(o) for o in ops]))
+
+
+def attn_decode_workspace_bytes(batch: int, n_q_heads: int, head_dim: int, max_blocks: int, block_size: int) -> int:
+    """Bytes of device memory (contents irrelevant) one decode attention of these shapes needs (no GPU needed)."""
+    return int(load().sqllm_attn_decode_workspace_bytes(batch, n_q_heads, head_dim, max_blocks, block_size))
 
 
 def workspace_bytes(bits: int, K: int, N: int, batch: int, nnz: int = 0, topX: int = 0, n_ops: int = 1) -> int:

@@ -23,6 +23,7 @@ hipError_t (*g_launch_linear_gated_norm)(int bits, const LaunchArgs& a, void* pa
 hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm.hip
 hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_cache.hip
 hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm_cache.hip
+hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
 }
 
 namespace sqllm_host {
@@ -1525,6 +1526,85 @@ int sqllm_qkv_rope_norm_cache_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm*
   const int rc = check_rmsnorm(nm);
   return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, true, nm, true, c);
 }
+
+// Decode attention (sqllm_attn_decode_*): the partitions of the launch, from HOST fields alone.  capacity is what the table
+// can address, clipped to what an int32 seq_lens can ask for.
+static int64_t attn_capacity(int32_t max_blocks, int32_t block_size) {
+  const int64_t cap = (int64_t)max_blocks * block_size;
+  return cap < INT32_MAX ? cap : INT32_MAX;
+}
+static int64_t attn_parts(int32_t max_blocks, int32_t block_size) {
+  return (attn_capacity(max_blocks, block_size) + SQLLM_ATTN_PARTITION - 1) / SQLLM_ATTN_PARTITION;
+}
+static_assert(SQLLM_ATTN_PARTITION == sqllm::kAttnPartition, "the header documents the kernel's partition");
+
+int64_t sqllm_attn_decode_workspace_bytes(int32_t batch, int32_t n_q_heads, int32_t head_dim, int32_t max_blocks, int32_t block_size) {
+  if (batch < 1 || n_q_heads < 1 || head_dim < 1 || max_blocks < 1 || block_size < 1) return 0;
+  // per (row, query head, partition): acc[head_dim], max, sum -- asked for with one partition too, where nothing is written
+  return (int64_t)batch * n_q_heads * attn_parts(max_blocks, block_size) * (head_dim + 2) * 4;
+}
+
+static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream, bool bf16) {
+  if (!a || !a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || !a->workspace) return SQLLM_E_NULL;
+  const int64_t D = a->head_dim;
+  if (a->batch < 1 || a->n_q_heads < 1 || a->n_kv_heads < 1 || D < 1 || a->n_slots < 1 || a->block_size < 1 || a->max_blocks < 1 ||
+      a->table_stride < 1)
+    return SQLLM_E_SHAPE;
+  const int64_t width = (int64_t)a->n_q_heads * D;
+  if (a->slot_stride < D || a->head_stride < D || a->q_stride < width || a->out_stride < width) return SQLLM_E_SHAPE;
+  if (a->max_blocks > a->table_stride) return SQLLM_E_SHAPE;
+  // what the kernel serves
+  if ((D != 64 && D != 128) || a->n_q_heads % a->n_kv_heads || a->n_q_heads / a->n_kv_heads > 8 || a->batch > 64 || a->n_q_heads > 65535)
+    return SQLLM_E_SHAPE;
+  // as for sqllm_kv_cache: 32 x 32 -> 64-bit products, and extents that do not wrap
+  const int64_t H = a->n_kv_heads;
+  if ((a->n_slots > 1 && a->slot_stride >= (1ll << 32)) || (H > 1 && a->head_stride >= (1ll << 32))) return SQLLM_E_SHAPE;
+  const unsigned __int128 extent = (unsigned __int128)(a->n_slots - 1) * (uint64_t)a->slot_stride + (unsigned __int128)(H - 1) * (uint64_t)a->head_stride + (uint64_t)D;
+  const unsigned __int128 q_extent = (unsigned __int128)(a->batch - 1) * (uint64_t)a->q_stride + (uint64_t)width;
+  const unsigned __int128 out_extent = (unsigned __int128)(a->batch - 1) * (uint64_t)a->out_stride + (uint64_t)width;
+  if (extent >= ((unsigned __int128)1 << 62) || q_extent >= ((unsigned __int128)1 << 62) || out_extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
+  if (!__builtin_isfinite(a->scale)) return SQLLM_E_OPTION;
+  const int64_t ws_bytes = sqllm_attn_decode_workspace_bytes(a->batch, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
+  const void* const in[5] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens};
+  const int64_t in_bytes[5] = {2 * (int64_t)q_extent, 2 * (int64_t)extent, 2 * (int64_t)extent,
+                               4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch};
+  for (int i = 0; i < 5; ++i)
+    if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i]))
+      return SQLLM_E_SHAPE;
+  if (ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
+  if (((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->out) | reinterpret_cast<uintptr_t>(a->k_cache) |
+        reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0 ||
+      (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0)
+    return SQLLM_E_ALIGN;
+  sqllm::AttnDecode d;
+  d.q = a->q;
+  d.out = a->out;
+  d.k_cache = a->k_cache;
+  d.v_cache = a->v_cache;
+  d.block_table = a->block_table;
+  d.seq_lens = a->seq_lens;
+  d.workspace = a->workspace;
+  d.batch = a->batch;
+  d.n_q_heads = a->n_q_heads;
+  d.n_kv_heads = a->n_kv_heads;
+  d.head_dim = a->head_dim;
+  d.n_slots = a->n_slots;
+  d.block_size = a->block_size;
+  d.table_stride = a->table_stride;
+  d.capacity = (int)attn_capacity(a->max_blocks, a->block_size);
+  d.n_parts = (int)attn_parts(a->max_blocks, a->block_size);
+  d.slot_stride = a->slot_stride;
+  d.head_stride = a->head_stride;
+  d.q_stride = a->q_stride;
+  d.out_stride = a->out_stride;
+  d.scale = a->scale;
+  d.bf16 = bf16;
+  const hipError_t e = sqllm::g_launch_attn_decode ? sqllm::g_launch_attn_decode(d, static_cast<hipStream_t>(stream)) : hipErrorNotSupported;
+  return static_cast<int>(e);
+}
+
+int sqllm_attn_decode_f16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, false); }
+int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, true); }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

@@ -181,6 +181,25 @@ struct KvCache {
 };
 extern hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream);
 extern hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream);
+// decode attention over that cache (sqllm_attn_decode_f16 / _bf16), on the kernels of sqllm_attn_decode.hip: the partials of
+// every (row, kv head, partition of kAttnPartition keys), then -- with more than one partition -- the combine.  A hook, as above.
+constexpr int kAttnPartition = 256;  // keys per partition (SQLLM_ATTN_PARTITION of include/sqllm_hip.h)
+struct AttnDecode {
+  const void* q;
+  void* out;
+  const void* k_cache;
+  const void* v_cache;
+  const int* block_table;  // int32 [batch, table_stride], device memory
+  const int* seq_lens;     // int32 [batch], device memory
+  void* workspace;         // n_parts x (head_dim + 2) floats per (row, query head); contents irrelevant
+  int batch, n_q_heads, n_kv_heads, head_dim, n_slots, block_size, table_stride;
+  int capacity;            // min(max_blocks * block_size, INT32_MAX) keys
+  int n_parts;             // ceil(capacity / kAttnPartition): HOST fields only, never device data
+  int64_t slot_stride, head_stride, q_stride, out_stride;  // in elements
+  float scale;
+  bool bf16;
+};
+extern hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

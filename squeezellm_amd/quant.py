@@ -972,6 +972,217 @@ def fuse_qkv_rope(module: nn.Module, q: str = "q_proj", k: str = "k_proj", v: st
     return n
 
 
+_ATTN_ENTRY = {torch.float16: "sqllm_attn_decode_f16", torch.bfloat16: "sqllm_attn_decode_bf16"}
+ATTN_PARTITION = _lib.ATTN_PARTITION  # keys per partition of the decode attention's kernel (SQLLM_ATTN_PARTITION)
+
+
+def static_cache_blocks(batch: int, n_kv_heads: int, device=None) -> torch.Tensor:
+    """The int32 block table [batch, 1] of a head-major static cache [B, H, S, D] seen through kv_cache_view(cache, "bhsd"),
+    for DecodeAttention with block_size = S: block_table[b, 0] = b * H, so that key p of row b lies in slot b * H * S + p --
+    the slot static_cache_slots gave the front for it."""
+    return (torch.arange(int(batch), dtype=torch.int32, device=device) * int(n_kv_heads)).reshape(-1, 1)
+
+
+def _torch_attn_decode(q, k_cache, v_cache, block_table, seq_lens, block_size, n_heads, n_kv_heads, head_dim, scale, dtype):
+    """The formulas of sqllm_attn_decode (include/sqllm_hip.h) in torch: fp32, rounded once to `dtype`; the +0 row, the NaN
+    rows; unaddressed slots never enter a result.  q: [rows, n_heads * head_dim]."""
+    rows, D, G = q.shape[0], head_dim, n_heads // n_kv_heads
+    n_slots, H = k_cache.shape[0], k_cache.shape[1]
+    ss, hs = k_cache.stride(0), (k_cache.stride(1) if H > 1 else D)
+    dev = q.device
+    lens = seq_lens.reshape(-1).long()
+    cap = block_table.shape[1] * int(block_size)
+    over = lens > cap
+    use = torch.where(over, torch.zeros_like(lens), lens.clamp(min=0))
+    S = max(int(use.max().item()), 1)
+    p = torch.arange(S, device=dev)
+    valid = p[None, :] < use[:, None]  # [rows, S]
+    entry = block_table.long()[:, (p // block_size).clamp(max=block_table.shape[1] - 1)]  # [rows, S]
+    slot = entry * int(block_size) + (p % block_size)[None, :]
+    bad = (valid & ((slot < 0) | (slot >= n_slots))).any(dim=1)
+    valid = valid & ~bad[:, None]
+    slot = torch.where(valid, slot, torch.zeros_like(slot))
+    at = slot[:, :, None, None] * ss + torch.arange(H, device=dev)[None, None, :, None] * hs + torch.arange(D, device=dev)[None, None, None, :]
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+
+    def gather(cache):
+        flat = cache.as_strided(((n_slots - 1) * ss + (H - 1) * hs + D,), (1,), cache.storage_offset())
+        return torch.where(valid[:, :, None, None], flat[at.reshape(-1)].reshape(at.shape).float(), zero)  # [rows, S, H, D]
+
+    k, v = gather(k_cache), gather(v_cache)
+    qf = q.float().reshape(rows, n_kv_heads, G, D)
+    s = torch.einsum("bhgd,bshd->bhgs", qf, k) * float(scale)
+    s = torch.where(valid[:, None, None, :], s, torch.full((), float("-inf"), dtype=torch.float32, device=dev))
+    m = s.max(dim=-1, keepdim=True).values
+    m = torch.where(torch.isinf(m) & (m < 0), torch.zeros_like(m), m)  # (a row without keys: w = 0 everywhere)
+    w = torch.where(valid[:, None, None, :], torch.exp(s - m), zero)
+    o = torch.einsum("bhgs,bshd->bhgd", w, v) / w.sum(dim=-1, keepdim=True)
+    o = o.reshape(rows, n_heads * D)
+    o = torch.where((lens <= 0)[:, None], zero, o)
+    o = torch.where((over | bad)[:, None], torch.full((), float("nan"), dtype=torch.float32, device=dev), o)
+    return o.to(dtype)
+
+
+class DecodeAttention(nn.Module):
+    """Decode attention -- ONE new query per sequence -- over the KV cache QuantQKVRopeFused writes, as HIP kernels
+    (sqllm_attn_decode_f16 / _bf16; include/sqllm_hip.h, sqllm_attn_decode: the formulas, the fixed partitions of
+    ATTN_PARTITION keys and their order, the +0 and NaN rows, non-finite values): the step between the front's q and o_proj.
+    It reads K and V once for all the query heads of a kv group, only the keys below each row's length, and follows lengths
+    and block tables in device memory -- no mask tensor, no expanded heads.
+
+    DecodeAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None); scale: 1 / sqrt(head_dim) where None.  No
+    parameters, no buffers, no state-dict keys.
+
+    forward(q, k_cache, v_cache, block_table, seq_lens, out=None, block_size=None) -> [..., n_heads * head_dim].
+    `q`: [..., n_heads * head_dim] with a contiguous last dimension, one row per sequence (the front's q).  `k_cache`,
+    `v_cache`: the 3-D views [n_slots, n_kv_heads, head_dim] of kv_cache_view, as QuantQKVRopeFused takes them (q's dtype and
+    device, equal shape and strides, stride(-1) == 1; overlapping as_strided views are allowed).  `block_table`: int32
+    [rows, max_blocks] on q's device; key p of row b lies in slot block_table[b, p // block_size] * block_size + p % block_size
+    (a paged cache's own table; static_cache_blocks for a "bhsd" cache, with block_size = S).  `seq_lens`: int32 [rows], the
+    number of keys each row attends to -- position + 1 when the front wrote the new token in the same step.  Both are used
+    WITHOUT a copy, so a captured graph follows them updated in place; int64 is converted, which costs a kernel each (as for
+    positions).  `block_size`: per call, or the constructor's.  `out`: a [rows, n_heads * head_dim] tensor of q's dtype with a
+    contiguous last dimension to be overwritten, or None for a new one.
+
+    A row with seq_lens <= 0 is +0; a row whose length exceeds max_blocks * block_size, or whose table leads outside the cache,
+    is NaN (nothing outside the cache is read).  Slots the table and the lengths do not address never influence a result.
+
+    fp16 / bf16 GPU tensors with head_dim 64 or 128, n_heads / n_kv_heads of 1 to 8 and at most 64 rows take the kernels
+    (`last_route` "attn_decode"): two launches, one when max_blocks * block_size <= ATTN_PARTITION; one workspace per
+    (device, stream) by the rules of QuantLinearLUTFused._workspace.  CPU tensors, other dtypes and other shapes compute the
+    same formulas in torch, in fp32 with one rounding (`last_route` "fallback").
+
+    Speed, graph-replayed on an MI355X against torch SDPA over the static cache with a length mask (tools/attn_decode_bench.py,
+    table in DESIGN.md 4.4, raw output profiles/attn_decode_bench.txt; 32/32 and 32/8 heads of 128, 1 / 4 / 16 rows, 128 / 1024 /
+    4096 keys in a cache of 4096, static and paged, fp16 / bf16): 9.7 - 207 us per call against 160 - 1761 us, faster on all 72
+    points; ABOVE the `3 us + bytes / 4.8 TB/s` per-launch fit on all but 32/32 at 4096 keys with 4 and 16 rows (5.3 TB/s there),
+    by up to 3.7x at 16 rows of 128 keys."""
+
+    GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
+
+    def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None):
+        super().__init__()
+        n_heads, n_kv_heads, head_dim = int(n_heads), int(n_kv_heads), int(head_dim)
+        if n_heads < 1 or n_kv_heads < 1 or head_dim < 1 or n_heads % n_kv_heads:
+            raise ValueError(f"n_heads must be a positive multiple of n_kv_heads and head_dim positive, got {n_heads}, {n_kv_heads}, {head_dim}")
+        scale = head_dim ** -0.5 if scale is None else float(scale)
+        if scale != scale or scale in (float("inf"), float("-inf")):
+            raise ValueError(f"scale must be finite, got {scale}")
+        if block_size is not None and int(block_size) < 1:
+            raise ValueError(f"block_size must be positive, got {block_size}")
+        self.n_heads, self.n_kv_heads, self.head_dim, self.scale = n_heads, n_kv_heads, head_dim, scale
+        self.block_size = None if block_size is None else int(block_size)
+
+    @property
+    def last_route(self):
+        """"attn_decode" or "fallback": the way the most recent forward went (None before the first)."""
+        return self.__dict__.get("_last_route")
+
+    def _check_cache(self, q: torch.Tensor, k_cache, v_cache) -> None:
+        """The cache views as QuantQKVRopeFused._check_cache wants them."""
+        D, H = self.head_dim, self.n_kv_heads
+        for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if not isinstance(t, torch.Tensor) or t.dtype != q.dtype or t.device != q.device:
+                raise ValueError(f"{name} must be a {q.dtype} tensor on {q.device}, got {getattr(t, 'dtype', type(t).__name__)} on "
+                                 f"{getattr(t, 'device', None)}")
+            if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] != H or t.shape[2] != D or t.stride(2) != 1:
+                raise ValueError(f"{name} must be a view [n_slots, {H}, {D}] with a contiguous last dimension, got {tuple(t.shape)} "
+                                 f"with strides {t.stride()}")
+        if k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride():
+            raise ValueError(f"k_cache and v_cache must have equal shape and strides, got {tuple(k_cache.shape)} / {k_cache.stride()} and "
+                             f"{tuple(v_cache.shape)} / {v_cache.stride()}")
+        if k_cache.stride(0) < D or (k_cache.stride(1) < D and H > 1):
+            raise ValueError(f"the strides of a cache view must be at least head_dim = {D}, got {k_cache.stride()}")
+
+    def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
+                out=None, block_size=None) -> torch.Tensor:
+        D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
+        W = HQ * D
+        if q.shape[-1] != W or q.stride(-1) != 1:
+            raise ValueError(f"q must be [..., {W}] with a contiguous last dimension, got {tuple(q.shape)} with strides {q.stride()}")
+        bs = self.block_size if block_size is None else int(block_size)
+        if bs is None or bs < 1:
+            raise ValueError("block_size must be given, at construction or per call, and be positive")
+        self._check_cache(q, k_cache, v_cache)
+        lead = q.shape[:-1]
+        q2 = q if q.dim() == 2 else q.reshape(-1, W)
+        rows = q2.shape[0]
+        if rows < 1:
+            raise ValueError("q has no rows")
+        if (not isinstance(block_table, torch.Tensor) or block_table.dtype not in (torch.int32, torch.int64) or block_table.dim() != 2
+                or block_table.shape[0] != rows or block_table.shape[1] < 1 or block_table.device != q.device):
+            raise ValueError(f"block_table must be int32 (or int64) [{rows}, max_blocks] on {q.device}")
+        if not isinstance(seq_lens, torch.Tensor) or seq_lens.dtype not in (torch.int32, torch.int64) or seq_lens.numel() != rows or seq_lens.device != q.device:
+            raise ValueError(f"seq_lens must be {rows} int32 (or int64) values on {q.device}")
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or out.shape != (rows, W)
+                    or out.stride(1) != 1 or (rows > 1 and out.stride(0) < W)):
+                raise ValueError(f"out must be a {q.dtype} [{rows}, {W}] tensor on {q.device} with a contiguous last dimension")
+        if rows > 1 and q2.stride(0) < W:
+            q2 = q2.contiguous()
+        kernel = q.dtype in _ATTN_ENTRY and q.is_cuda and D in (64, 128) and HQ // H <= 8 and rows <= 64
+        if not kernel:
+            self.__dict__["_last_route"] = "fallback"
+            o = _torch_attn_decode(q2, k_cache, v_cache, block_table, seq_lens, bs, HQ, H, D, self.scale, q.dtype)
+            if out is not None:
+                out.copy_(o)
+                return out
+            return o.reshape(*lead, W)
+        bt = block_table if block_table.dtype == torch.int32 else block_table.to(torch.int32)  # (a kernel)
+        if bt.stride(1) != 1 or (rows > 1 and bt.stride(0) < bt.shape[1]):
+            bt = bt.contiguous()
+        sl = seq_lens.reshape(-1)
+        if sl.dtype != torch.int32:
+            sl = sl.to(torch.int32)  # (a kernel)
+        if not sl.is_contiguous():
+            sl = sl.contiguous()
+        self.__dict__["_last_route"] = "attn_decode"
+        dev = q.get_device()
+        o = out if out is not None else torch.empty((rows, W), dtype=q.dtype, device=q.device)
+        stream = quant_cuda._raw_stream(dev)
+        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.attn_decode_workspace_bytes(rows, HQ, D, bt.shape[1], bs), q.device,
+                           self.GRAPH_WS_MAX_BYTES)
+        descs = self.__dict__.setdefault("_desc", {})
+        hit = descs.get((dev, stream))
+        if hit is None:
+            a = _lib.SqllmAttnDecode()
+            hit = descs[(dev, stream)] = (a, ctypes.byref(a))
+        a, ref = hit
+        a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+        a.block_table, a.seq_lens = bt.data_ptr(), sl.data_ptr()
+        a.batch, a.n_q_heads, a.n_kv_heads, a.head_dim = rows, HQ, H, D
+        a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, bt.shape[1]
+        a.table_stride = bt.stride(0) if rows > 1 else bt.shape[1]
+        a.slot_stride = k_cache.stride(0)
+        a.head_stride = k_cache.stride(1) if H > 1 else D  # (one head: its stride is anything, and never used)
+        a.q_stride = q2.stride(0) if rows > 1 else W
+        a.out_stride = o.stride(0) if rows > 1 else W
+        a.scale, a.workspace = self.scale, ws.data_ptr()
+        quant_cuda._launch(quant_cuda._fn(_ATTN_ENTRY[q.dtype]), dev, (ref,))
+        return o if out is not None else o.reshape(*lead, W)
+
+
+def fuse_decode_attention(module: nn.Module, n_heads=None, n_kv_heads=None) -> int:
+    """Give every submodule of `module` that carries a `qkv_rope` (fuse_qkv_rope) an attribute `attend_decode`, a
+    DecodeAttention for its heads: head_dim the front's, n_heads and n_kv_heads the widths of the front's q and k over it
+    (or the arguments).  Not a child, through `__dict__`: the module tree, the state dict and every `forward` stay as they
+    are; an attention forward calls `self.attend_decode(q, k_cache, v_cache, block_table, seq_lens)` between `self.qkv_rope`
+    and `o_proj`.  Returns the count."""
+    n = 0
+    for m in module.modules():
+        front = m.__dict__.get("qkv_rope")
+        if not isinstance(front, QuantQKVRopeFused):
+            continue
+        d = front.head_dim
+        hq = int(n_heads) if n_heads is not None else front.q.outfeatures // d
+        hk = int(n_kv_heads) if n_kv_heads is not None else front.k.outfeatures // d
+        if hq < 1 or hk < 1 or hq % hk:
+            continue
+        m.__dict__["attend_decode"] = DecodeAttention(hq, hk, d)
+        n += 1
+    return n
+
+
 def _norm_of(m):
     """(weight, eps) of an RMSNorm-like module: a `weight` and a `variance_epsilon` (or `eps`); None for anything else."""
     w = getattr(m, "weight", None)
