@@ -561,6 +561,69 @@ int sqllm_attn_decode_f16(const sqllm_attn_decode* a, sqllm_stream_t stream);
 int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * FP8 KV cache: the attention front writes 1-byte OCP e4m3fn elements (NOT the fnuz format), decode attention reads them.
+ * One fp32 scale per cache, k_scale and v_scale, chosen by the caller (calibration is the caller's; absmax / 448 is the usual
+ * choice).  Half the bytes of the 16-bit cache for the step of a decode layer that is bound by them.
+ *
+ *   - Encoding (sqllm_qkv_rope_cache_fp8_* / sqllm_qkv_rope_norm_cache_fp8_*).  With inv = 1.0f / scale, computed once on the host
+ *     in fp32:
+ *         byte = e4m3_rne(min(max(x * inv, -448), 448))
+ *     where x is the fp32 value that out_k[b, n] / out_v[b, n] would round to 16 bits: the rotated value for k, the plain sum
+ *     for v.  The fp32 value is rounded ONCE, straight to fp8; it does not go through the 16-bit output.  Rounding is to
+ *     nearest, ties to even; e4m3's subnormals are produced, not flushed; +-inf saturates to +-448; NaN stays NaN (exponent
+ *     and mantissa bits all ones, either sign).  The clamp is explicit in the kernel.
+ *   - Decoding (sqllm_attn_decode_fp8_*).  float(k) = k_scale * f32(byte) and float(v) = v_scale * f32(byte) stand in the
+ *     formulas of sqllm_attn_decode.  scale * k_scale is folded into the score's scale, rounded once on the host; v_scale
+ *     multiplies each partition's sum over its keys once per output element, in fp32, before the one rounding to the output
+ *     type.  A NaN byte among the attended elements behaves as a NaN element does there.
+ *   - Everything else holds word for word, for the front as for the attention: the paged and the head-major static layout
+ *     through the two strides, which now count BYTES; int32 slots, tables and lengths in device memory; out-of-range slots
+ *     write nothing; optional out_k / out_v, written as by the 16-bit entries when given; the +0 row and the NaN rows;
+ *     unaddressed slots never influence a result; fixed partitions of SQLLM_ATTN_PARTITION keys combined in ascending order;
+ *     the workspace of sqllm_attn_decode_workspace_bytes(); no allocation; one kernel node for the front, two for the
+ *     attention, one when max_blocks * block_size <= SQLLM_ATTN_PARTITION.  Cache elements are aligned to one byte only: any
+ *     base address and any strides >= head_dim, head_stride = head_dim + 3 included.
+ *   - Determinism.  Every sum's order depends on head_dim, n_q_heads / n_kv_heads and the key's index alone: bit-identical
+ *     run to run and row by row.  The order is not the 16-bit kernel's.
+ *
+ * Rejected before the device is touched: everything the 16-bit sibling rejects, with its codes and in its order (the cache
+ * extents in bytes, and no alignment rule for k_cache / v_cache); then
+ *   a k_scale or v_scale that is not finite, not positive, or whose fp32 reciprocal is not finite     SQLLM_E_OPTION
+ *   in the attention entries, a scale * k_scale that is not finite                                    SQLLM_E_OPTION
+ * Not covered: per-head or per-token scales, e5m2, int8 or 4-bit caches, computing the scales, prefill attention.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_kv_cache_fp8 {
+  void* k_cache;          /* 1-byte e4m3fn elements, device memory */
+  void* v_cache;
+  const int32_t* slots;   /* int32 [batch], DEVICE memory: a captured graph follows slots updated in place */
+  int32_t n_slots;        /* >= 1 */
+  int64_t slot_stride;    /* bytes between consecutive slots,            >= head_dim */
+  int64_t head_stride;    /* bytes between consecutive kv heads of a slot, >= head_dim */
+  float k_scale, v_scale; /* finite, positive, with finite fp32 reciprocals */
+} sqllm_kv_cache_fp8;
+int sqllm_qkv_rope_cache_fp8_f16(const sqllm_qkv_rope* r, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream);
+int sqllm_qkv_rope_cache_fp8_bf16(const sqllm_qkv_rope* r, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream);
+int sqllm_qkv_rope_norm_cache_fp8_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream);
+int sqllm_qkv_rope_norm_cache_fp8_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* norm, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream);
+typedef struct sqllm_attn_decode_fp8 {
+  const void* q;            /* 16-bit [batch, n_q_heads * head_dim], row stride q_stride elements */
+  void* out;                /* 16-bit [batch, n_q_heads * head_dim], row stride out_stride; OVERWRITTEN */
+  const void* k_cache;      /* as sqllm_kv_cache_fp8: byte (slot, kv head h, d) at slot*slot_stride + h*head_stride + d */
+  const void* v_cache;
+  const int32_t* block_table; /* int32 [batch, table_stride], DEVICE memory */
+  const int32_t* seq_lens;    /* int32 [batch], DEVICE memory */
+  int32_t batch, n_q_heads, n_kv_heads, head_dim;
+  int32_t n_slots, block_size, max_blocks, table_stride;   /* max_blocks <= table_stride */
+  int64_t slot_stride, head_stride, q_stride, out_stride;  /* the first two in bytes, the last two in 16-bit elements */
+  float scale;              /* the caller's, usually 1/sqrt(head_dim); finite */
+  void* workspace;          /* sqllm_attn_decode_workspace_bytes(); contents irrelevant */
+  float k_scale, v_scale;   /* the cache's, as the front was given them */
+} sqllm_attn_decode_fp8;
+/* the suffix names the type of q and out */
+int sqllm_attn_decode_fp8_f16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream);
+int sqllm_attn_decode_fp8_bf16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

@@ -93,6 +93,20 @@ class SqllmAttnDecode(ctypes.Structure):
                 ("out_stride", ctypes.c_int64), ("scale", ctypes.c_float), ("workspace", c_void_p)]
 
 
+class SqllmKvCacheFp8(ctypes.Structure):
+    """struct sqllm_kv_cache_fp8 (include/sqllm_hip.h): sqllm_kv_cache for caches of 1-byte e4m3fn elements -- strides in bytes,
+    one fp32 scale per cache."""
+
+    _fields_ = SqllmKvCache._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float)]
+
+
+class SqllmAttnDecodeFp8(ctypes.Structure):
+    """struct sqllm_attn_decode_fp8 (include/sqllm_hip.h): sqllm_attn_decode over caches of 1-byte e4m3fn elements -- the caches'
+    strides in bytes, the scales the front was given."""
+
+    _fields_ = SqllmAttnDecode._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float)]
+
+
 class SqllmQkvRope(ctypes.Structure):
     """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
 
@@ -196,6 +210,12 @@ SIGNATURES = {
     "sqllm_attn_decode_workspace_bytes": [c_int32, c_int32, c_int32, c_int32, c_int32],
     "sqllm_attn_decode_f16": [POINTER(SqllmAttnDecode), P],
     "sqllm_attn_decode_bf16": [POINTER(SqllmAttnDecode), P],
+    "sqllm_qkv_rope_cache_fp8_f16": [POINTER(SqllmQkvRope), POINTER(SqllmKvCacheFp8), P],
+    "sqllm_qkv_rope_cache_fp8_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmKvCacheFp8), P],
+    "sqllm_qkv_rope_norm_cache_fp8_f16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), POINTER(SqllmKvCacheFp8), P],
+    "sqllm_qkv_rope_norm_cache_fp8_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), POINTER(SqllmKvCacheFp8), P],
+    "sqllm_attn_decode_fp8_f16": [POINTER(SqllmAttnDecodeFp8), P],
+    "sqllm_attn_decode_fp8_bf16": [POINTER(SqllmAttnDecodeFp8), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],

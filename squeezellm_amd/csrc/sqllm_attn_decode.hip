@@ -38,22 +38,7 @@ constexpr int kAttnThreads = 256;
 constexpr int kAttnUnroll = 4;  // 16-byte loads in flight per lane before the first use
 static_assert(kAttnPartition == kAttnThreads, "phase 0 resolves one key per thread");
 
-struct AttnArgs {
-  const void* q;
-  void* out;
-  const void* k_cache;
-  const void* v_cache;
-  const int* block_table;
-  const int* seq_lens;
-  float* ws_acc;  // [batch, n_q_heads, n_parts, head_dim]
-  float* ws_ml;   // [batch, n_q_heads, n_parts, 2]
-  long long q_stride, out_stride;
-  unsigned slot_stride, head_stride;  // (below 2^32 wherever they are multiplied: checked by the host)
-  int n_q_heads, group, n_slots, block_size, table_stride;
-  int capacity;  // min(max_blocks * block_size, INT32_MAX)
-  int n_parts;
-  float scale;
-};
+// (AttnArgs, the kernels' argument: sqllm_kernels.h)
 
 // 16 bytes of 16-bit elements that are aligned to their elements only
 struct __attribute__((packed, aligned(2))) Packed8 {
@@ -334,32 +319,26 @@ static hipError_t launch_attn_decode(const AttnDecode& d, hipStream_t stream) {
   if ((d.head_dim != 64 && d.head_dim != 128) || d.n_kv_heads < 1 || d.n_q_heads % d.n_kv_heads || d.n_q_heads / d.n_kv_heads > 8 ||
       d.batch < 1 || d.n_parts < 1)
     return hipErrorInvalidValue;
-  AttnArgs k;
-  k.q = d.q;
-  k.out = d.out;
-  k.k_cache = d.k_cache;
-  k.v_cache = d.v_cache;
-  k.block_table = d.block_table;
-  k.seq_lens = d.seq_lens;
-  k.ws_acc = static_cast<float*>(d.workspace);
-  k.ws_ml = k.ws_acc + (long long)d.batch * d.n_q_heads * d.n_parts * d.head_dim;
-  k.q_stride = d.q_stride;
-  k.out_stride = d.out_stride;
-  k.slot_stride = (unsigned)d.slot_stride;
-  k.head_stride = (unsigned)d.head_stride;
-  k.n_q_heads = d.n_q_heads;
-  k.group = d.n_q_heads / d.n_kv_heads;
-  k.n_slots = d.n_slots;
-  k.block_size = d.block_size;
-  k.table_stride = d.table_stride;
-  k.capacity = d.capacity;
-  k.n_parts = d.n_parts;
-  k.scale = d.scale;
+  const AttnArgs k = make_attn_args(d);
   if (d.bf16) return d.head_dim == 64 ? launch_attn_group<64, __bf16>(k, d.n_kv_heads, d.batch, stream) : launch_attn_group<128, __bf16>(k, d.n_kv_heads, d.batch, stream);
   return d.head_dim == 64 ? launch_attn_group<64, _Float16>(k, d.n_kv_heads, d.batch, stream) : launch_attn_group<128, _Float16>(k, d.n_kv_heads, d.batch, stream);
 }
 
+// the combine alone, behind partials that another file's kernels left in the workspace (sqllm_attn_decode_fp8.hip)
+static hipError_t launch_attn_combine(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) {
+  if (head_dim != 64 && head_dim != 128) return hipErrorInvalidValue;
+  const dim3 grid(k.n_q_heads, batch);
+  if (head_dim == 64) {
+    if (bf16) hipLaunchKernelGGL((sqllm_attn_combine_kernel<64, __bf16>), grid, dim3(64), 0, stream, k);
+    else hipLaunchKernelGGL((sqllm_attn_combine_kernel<64, _Float16>), grid, dim3(64), 0, stream, k);
+  } else {
+    if (bf16) hipLaunchKernelGGL((sqllm_attn_combine_kernel<128, __bf16>), grid, dim3(128), 0, stream, k);
+    else hipLaunchKernelGGL((sqllm_attn_combine_kernel<128, _Float16>), grid, dim3(128), 0, stream, k);
+  }
+  return hipGetLastError();
+}
+
 // the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_attn_decode_registered = (g_launch_attn_decode = launch_attn_decode, true);
+static const bool g_attn_decode_registered = (g_launch_attn_decode = launch_attn_decode, g_launch_attn_combine = launch_attn_combine, true);
 
 }  // namespace sqllm

@@ -1,0 +1,332 @@
+// sqllm_attn_decode_fp8.hip -- decode attention over a KV cache of 1-byte OCP e4m3fn elements with one fp32 scale per cache
+// (include/sqllm_hip.h: sqllm_attn_decode_fp8_f16 / _bf16; the suffix names the type of q and out).  The partial kernel of
+// sqllm_attn_decode.hip for bytes: the same phases, the same partitions of kAttnPartition keys, the same workspace, and --
+// with more than one partition -- the SAME combine kernel behind it, reached through g_launch_attn_combine (it does not see the
+// cache).  float(k) = k_scale * f32(byte): k_scale is folded into the score's scale on the host, so phase 1 multiplies raw
+// bytes' values; float(v) = v_scale * f32(byte): v_scale multiplies each partition's sum over the keys once per (head, d), in
+// front of the division (one partition) or of the workspace (several), so the combine needs no scale.
+//
+// Lanes and loads.  A lane loads 16 ELEMENTS = 16 bytes per key (one 16-byte load, as in the 16-bit kernel: an 8-byte load per
+// lane would halve the bytes in flight of a kernel that lives on them), so head_dim / 16 lanes cover a key: 8 lanes at head_dim
+// 128, 4 at head_dim 64, and a wave instruction covers 8 resp. 16 keys -- twice the 16-bit kernel's.  kAttnUnroll loads are in
+// flight per lane before the first use (4 waves x 4 KiB per workgroup, as there).  The bytes widen with the packed conversion
+// (v_cvt_pk_f32_fp8, two elements per instruction).
+//
+// The cross-lane reduction this implies.  Phase 1: the dot product meets across the key's lanes in DPP -- quad_perm [1,0,3,2]
+// and [2,3,0,1] for 4 lanes, row_half_mirror on top for 8; all lanes of a key end with the same bits.  With 4 lanes per key and
+// a group class of 8, lane `sub` of a key stores the scores of heads sub and sub + 4.  Phase 4: the workgroup has 32 (head_dim
+// 128) or 64 (head_dim 64) key-lanes, each with acc[head][16]; they meet through LDS in ascending key-lane order, TWO heads per
+// round (32 KiB of exchange, as the 16-bit kernel's four heads of 8 elements).
+//
+// The order of every sum depends on head_dim, the group class and the key's index alone: bit-identical run to run, and row by
+// row.  It is NOT the 16-bit kernel's order (16 elements per lane, other key-lanes).
+//
+// Registers: q (group x 16 fp32) lives in phase 1 only, acc (group x 16 fp32) in phase 3 only; no scratch, no spills, two
+// workgroups per CU at least (tests/test_codegen_kv_fp8_cpu.py).  LDS: scores 8 KiB at most, slots 1 KiB, the exchange 32 KiB.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sqllm_decode.h"
+#include "sqllm_kernels.h"
+
+namespace sqllm {
+
+constexpr int kAttnFp8Threads = 256;
+constexpr int kAttnFp8Unroll = 4;  // 16-byte loads in flight per lane before the first use
+static_assert(kAttnPartition == kAttnFp8Threads, "phase 0 resolves one key per thread");
+
+// 16 bytes that are aligned to one byte only
+struct __attribute__((packed, aligned(1))) Bytes16 {
+  uint32_t w[4];
+};
+// 16 bytes of 16-bit elements that are aligned to their elements only (q)
+struct __attribute__((packed, aligned(2))) Halves8 {
+  uint32_t w[4];
+};
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// 16 e4m3fn bytes as fp32 (a NaN byte is a NaN)
+__device__ __forceinline__ void widen_e4m3(const Bytes16& p, float (&f)[16]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)p.w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)p.w[i], true);
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
+}
+
+template <typename OT>
+__device__ __forceinline__ void widen_q8(const Halves8& p, float* f) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if constexpr (std::is_same<OT, __bf16>::value) {
+      f[2 * i] = __builtin_bit_cast(float, p.w[i] << 16);
+      f[2 * i + 1] = __builtin_bit_cast(float, p.w[i] & 0xffff0000u);
+    } else {
+      f[2 * i] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] & 0xffffu));
+      f[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] >> 16));
+    }
+  }
+}
+
+// the sum over the LPK lanes of a key, in every one of them (a + b and b + a: the same bits on both sides of each exchange)
+template <int LPK>
+__device__ __forceinline__ float key_sum_fp8(float v) {
+  static_assert(LPK == 4 || LPK == 8, "head_dim 64 or 128");
+  v += dpp_f32<0xB1, 0xf>(v);  // quad_perm [1,0,3,2]
+  v += dpp_f32<0x4E, 0xf>(v);  // quad_perm [2,3,0,1]
+  if constexpr (LPK == 8) v += dpp_f32<0x141, 0xf>(v);  // row_half_mirror: the other quad of the 8 lanes
+  return v;
+}
+
+__device__ __forceinline__ float wave_max_fp8(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+template <int D, int GC, typename OT>
+__global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(const AttnArgs a, const float v_scale) {
+  constexpr int P = kAttnPartition;
+  constexpr int E = 16;              // elements (bytes) per lane and key
+  constexpr int LPK = D / E;         // lanes per key
+  constexpr int KPW = 64 / LPK;      // keys per wave instruction
+  constexpr int KPS = KPW * 4;       // keys per step of the workgroup
+  constexpr int STEPS = P / KPS;
+  constexpr int U = kAttnFp8Unroll;
+  constexpr int HC = GC < 2 ? GC : 2;          // heads per round of the key-lane exchange
+  constexpr int R = (GC + LPK - 1) / LPK;      // heads whose score one lane of a key stores
+  static_assert(STEPS % U == 0, "whole unrolled rounds");
+  static_assert(KPS * HC * D * 4 <= 32 * 1024, "the exchange");
+  __shared__ float sc[GC][P];
+  __shared__ int slots[P];
+  __shared__ float ml[GC][2];
+  __shared__ __attribute__((aligned(16))) float red[KPS][HC][D];
+
+  const int part = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sub = lane % LPK, grp = lane / LPK;
+  const int g = a.group;
+  const bool single = a.n_parts == 1;
+  OT* const out = reinterpret_cast<OT*>(a.out) + (long long)b * a.out_stride + (long long)hk * g * D;
+
+  const int len = a.seq_lens[b];
+  if (len <= 0 || len > a.capacity) {
+    if (single) {  // (otherwise the combine writes these rows)
+      const OT c = len <= 0 ? (OT)0.0f : (OT)__builtin_nanf("");
+      for (int i = tid; i < g * D; i += kAttnFp8Threads) out[i] = c;
+    }
+    return;
+  }
+  const int p0 = part * P;
+  if (p0 >= len) return;
+  const int n_valid = len - p0 < P ? len - p0 : P;
+
+  // 0. the slots of this partition's keys
+  {
+    const unsigned p = tid < n_valid ? p0 + tid : p0;
+    const unsigned blk = p / (unsigned)a.block_size, off = p - blk * (unsigned)a.block_size;
+    const long long s = (long long)a.block_table[(long long)b * a.table_stride + blk] * a.block_size + off;
+    const bool bad = s < 0 || s >= a.n_slots;
+    slots[tid] = (int)s;
+    if (__syncthreads_or(bad)) {  // NaN, and nothing of the caches is read
+      const float nan = __builtin_nanf("");
+      if (single) {
+        for (int i = tid; i < g * D; i += kAttnFp8Threads) out[i] = (OT)nan;
+      } else {
+        for (int i = tid; i < g * D; i += kAttnFp8Threads) {
+          const long long at = ((long long)b * a.n_q_heads + hk * g + i / D) * a.n_parts + part;
+          a.ws_acc[at * D + i % D] = nan;
+          if (i % D == 0) {
+            a.ws_ml[at * 2] = 0.0f;
+            a.ws_ml[at * 2 + 1] = nan;
+          }
+        }
+      }
+      return;
+    }
+  }
+  const int nsteps = (n_valid + KPS - 1) / KPS;
+  const unsigned long long head_off = (unsigned long long)(unsigned)hk * a.head_stride + (unsigned)(sub * E);
+
+  // 1. scores
+  {
+    float qf[GC][E];
+    const OT* q = reinterpret_cast<const OT*>(a.q) + (long long)b * a.q_stride + (long long)hk * g * D + sub * E;
+#pragma unroll
+    for (int h = 0; h < GC; ++h) {
+      if (h < g) {
+        widen_q8<OT>(*reinterpret_cast<const Halves8*>(q + h * D), qf[h]);
+        widen_q8<OT>(*reinterpret_cast<const Halves8*>(q + h * D + 8), qf[h] + 8);
+      } else {
+#pragma unroll
+        for (int j = 0; j < E; ++j) qf[h][j] = 0.0f;
+      }
+    }
+    const uint8_t* kc = reinterpret_cast<const uint8_t*>(a.k_cache);
+    for (int s0 = 0; s0 < nsteps; s0 += U) {
+      Bytes16 kr[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int kl = (s0 + u) * KPS + wave * KPW + grp;
+        kr[u] = *reinterpret_cast<const Bytes16*>(kc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int kl = (s0 + u) * KPS + wave * KPW + grp;
+        float kf[E];
+        widen_e4m3(kr[u], kf);
+        float mine[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) mine[r] = 0.0f;
+#pragma unroll
+        for (int h = 0; h < GC; ++h) {
+          float dot = qf[h][0] * kf[0];
+#pragma unroll
+          for (int j = 1; j < E; ++j) dot = fmaf(qf[h][j], kf[j], dot);
+          dot = key_sum_fp8<LPK>(dot);
+          if (sub == h % LPK) mine[h / LPK] = dot;
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int h = sub + r * LPK;
+          if (h < GC) sc[h][kl] = kl < n_valid ? a.scale * mine[r] : -__builtin_inff();
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // 2. the partition's softmax, one wave per head; every entry of sc[h] is written, whatever phase 1 left there
+  for (int h = wave; h < g; h += 4) {
+    float s[P / 64], m = -__builtin_inff();
+#pragma unroll
+    for (int i = 0; i < P / 64; ++i) {
+      const int kl = lane + 64 * i;
+      s[i] = kl < n_valid ? sc[h][kl] : -__builtin_inff();
+      m = fmaxf(m, s[i]);
+    }
+    m = wave_max_fp8(m);
+    float l = 0.0f;
+#pragma unroll
+    for (int i = 0; i < P / 64; ++i) {
+      const int kl = lane + 64 * i;
+      const float w = kl < n_valid ? expf(s[i] - m) : 0.0f;
+      sc[h][kl] = w;
+      l += w;
+    }
+    l = wave_sum(l);
+    if (lane == 0) {
+      ml[h][0] = m;
+      ml[h][1] = l;
+    }
+  }
+  __syncthreads();
+
+  // 3. PV
+  float acc[GC][E];
+#pragma unroll
+  for (int h = 0; h < GC; ++h)
+#pragma unroll
+    for (int j = 0; j < E; ++j) acc[h][j] = 0.0f;
+  {
+    const uint8_t* vc = reinterpret_cast<const uint8_t*>(a.v_cache);
+    for (int s0 = 0; s0 < nsteps; s0 += U) {
+      Bytes16 vr[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int kl = (s0 + u) * KPS + wave * KPW + grp;
+        vr[u] = *reinterpret_cast<const Bytes16*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int kl = (s0 + u) * KPS + wave * KPW + grp;
+        const bool valid = kl < n_valid;
+        if (!valid) {  // (the stand-in slot's values: 0 x NaN would be NaN; a zero byte is +0)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) vr[u].w[i] = 0u;
+        }
+        float vf[E];
+        widen_e4m3(vr[u], vf);
+#pragma unroll
+        for (int h = 0; h < GC; ++h) {
+          const float w = h < g && valid ? sc[h][kl] : 0.0f;
+#pragma unroll
+          for (int j = 0; j < E; ++j) acc[h][j] = fmaf(w, vf[j], acc[h][j]);
+        }
+      }
+    }
+  }
+
+  // 4. the key-lanes meet, HC heads per round, in ascending key-lane order; v_scale once per element of the sum
+#pragma unroll
+  for (int h0 = 0; h0 < GC; h0 += HC) {
+    if (h0 >= g) break;  // (uniform)
+    if (h0) __syncthreads();
+#pragma unroll
+    for (int hh = 0; hh < HC; ++hh) {
+      f32x4* at = reinterpret_cast<f32x4*>(&red[wave * KPW + grp][hh][sub * E]);
+#pragma unroll
+      for (int i = 0; i < E / 4; ++i)
+        at[i] = f32x4{acc[h0 + hh][4 * i], acc[h0 + hh][4 * i + 1], acc[h0 + hh][4 * i + 2], acc[h0 + hh][4 * i + 3]};
+    }
+    __syncthreads();
+    for (int i = tid; i < HC * D; i += kAttnFp8Threads) {
+      const int hh = i / D, d = i % D, h = h0 + hh;
+      if (h >= g) break;
+      float t = red[0][hh][d];
+#pragma unroll
+      for (int k = 1; k < KPS; ++k) t += red[k][hh][d];
+      t *= v_scale;
+      if (single) {
+        out[h * D + d] = (OT)(t / ml[h][1]);
+      } else {
+        const long long pa = ((long long)b * a.n_q_heads + hk * g + h) * a.n_parts + part;
+        a.ws_acc[pa * D + d] = t;
+        if (d == 0) {
+          a.ws_ml[pa * 2] = ml[h][0];
+          a.ws_ml[pa * 2 + 1] = ml[h][1];
+        }
+      }
+    }
+  }
+}
+
+template <int D, int GC, typename OT>
+static hipError_t launch_attn_fp8_inst(const AttnArgs& k, float v_scale, int n_kv_heads, int batch, bool bf16, hipStream_t stream) {
+  if (k.n_parts > 1 && !g_launch_attn_combine) return hipErrorNotSupported;  // (a missing kernel is an error, before anything is launched)
+  hipLaunchKernelGGL((sqllm_attn_decode_fp8_kernel<D, GC, OT>), dim3(k.n_parts, n_kv_heads, batch), dim3(kAttnFp8Threads), 0, stream, k, v_scale);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || k.n_parts == 1) return e;
+  return g_launch_attn_combine(k, D, bf16, batch, stream);
+}
+
+template <int D, typename OT>
+static hipError_t launch_attn_fp8_group(const AttnArgs& k, float v_scale, int n_kv_heads, int batch, bool bf16, hipStream_t stream) {
+  switch (k.group) {
+    case 1: return launch_attn_fp8_inst<D, 1, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
+    case 2: return launch_attn_fp8_inst<D, 2, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
+    case 3: case 4: return launch_attn_fp8_inst<D, 4, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
+    default: return launch_attn_fp8_inst<D, 8, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
+  }
+}
+
+static hipError_t launch_attn_decode_fp8(const AttnDecode& d, hipStream_t stream) {
+  if ((d.head_dim != 64 && d.head_dim != 128) || d.n_kv_heads < 1 || d.n_q_heads % d.n_kv_heads || d.n_q_heads / d.n_kv_heads > 8 ||
+      d.batch < 1 || d.n_parts < 1)
+    return hipErrorInvalidValue;
+  const AttnArgs k = make_attn_args(d);
+  if (d.bf16)
+    return d.head_dim == 64 ? launch_attn_fp8_group<64, __bf16>(k, d.v_scale, d.n_kv_heads, d.batch, true, stream)
+                            : launch_attn_fp8_group<128, __bf16>(k, d.v_scale, d.n_kv_heads, d.batch, true, stream);
+  return d.head_dim == 64 ? launch_attn_fp8_group<64, _Float16>(k, d.v_scale, d.n_kv_heads, d.batch, false, stream)
+                          : launch_attn_fp8_group<128, _Float16>(k, d.v_scale, d.n_kv_heads, d.batch, false, stream);
+}
+
+// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
+static const bool g_attn_decode_fp8_registered = (g_launch_attn_decode_fp8 = launch_attn_decode_fp8, true);
+
+}  // namespace sqllm

@@ -24,6 +24,10 @@ hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvR
 hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_cache.hip
 hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm_cache.hip
 hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
+hipError_t (*g_launch_linear_qkv_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_cache_fp8.hip
+hipError_t (*g_launch_linear_qkv_norm_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm_cache_fp8.hip
+hipError_t (*g_launch_attn_decode_fp8)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode_fp8.hip
+hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
 }
 
 namespace sqllm_host {
@@ -1174,6 +1178,7 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
   GroupPlan plan;
   plan_group(ops, n, route, facts, &plan);
   if (plan.rc != SQLLM_OK) return plan.rc;
+  if (kc && kc->fp8 && !kc->scales_ok) return SQLLM_E_OPTION;  // (the fp8 cache entries: behind everything their 16-bit siblings reject)
   if (small.xT && !(g_experimental.skip_prepare_small && g_experimental.skip_prepare_small())) {  // (measurement library only: what the kernel in front costs)
     const hipError_t e = small.planes ? sqllm::prepare_small(ops[0].vec, small.xT, small.planes, ops[0].batch, ops[0].K, s, e0)
                                       : sqllm::transpose_small(ops[0].vec, small.xT, ops[0].batch, ops[0].K, s, e0);
@@ -1203,6 +1208,12 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
           break;
         }
         if (qkv) {  // (sqllm_linear_qkv.hip; a missing kernel is an error here too, and the launch is not decorated either)
+          if (kc && kc->fp8) {  // (sqllm_linear_qkv_cache_fp8.hip / sqllm_linear_qkv_norm_cache_fp8.hip)
+            if (vn) e = sqllm::g_launch_linear_qkv_norm_cache_fp8 ? sqllm::g_launch_linear_qkv_norm_cache_fp8(op->bits, a, *qkv, *kc, *vn, s) : hipErrorNotSupported;
+            else
+            e = sqllm::g_launch_linear_qkv_cache_fp8 ? sqllm::g_launch_linear_qkv_cache_fp8(op->bits, a, *qkv, *kc, s) : hipErrorNotSupported;
+            break;
+          }
           if (kc) {  // (sqllm_linear_qkv_cache.hip / sqllm_linear_qkv_norm_cache.hip)
             if (vn) e = sqllm::g_launch_linear_qkv_norm_cache ? sqllm::g_launch_linear_qkv_norm_cache(op->bits, a, *qkv, *kc, *vn, s) : hipErrorNotSupported;
             else
@@ -1390,7 +1401,8 @@ static bool ranges_overlap(const void* p, int64_t p_bytes, const void* q, int64_
 // The cache entries' own checks (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*): the descriptor `c` against the call `r` it
 // comes with, which has passed launch_qkv_rope's own checks -- behind those and in front of the linear's validation, to which
 // widths it is about to reject are left (`widths_ok`).
-static int check_kv_cache(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, const sqllm_rmsnorm* nm, bool widths_ok) {
+// `elem`: bytes per cache element (2, or 1 in the fp8 entries, whose strides and extent then count bytes)
+static int check_kv_cache(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, const sqllm_rmsnorm* nm, bool widths_ok, int elem = 2) {
   if (!c || !c->k_cache || !c->v_cache || !c->slots) return SQLLM_E_NULL;
   const int64_t D = r->head_dim;
   if (c->n_slots < 1 || c->slot_stride < D || c->head_stride < D) return SQLLM_E_SHAPE;
@@ -1402,7 +1414,7 @@ static int check_kv_cache(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, cons
   // (in 128 bits: strides up to 2^63 are still to be rejected by the overlap rule, not to wrap)
   const unsigned __int128 extent = (unsigned __int128)(c->n_slots - 1) * (uint64_t)c->slot_stride + (unsigned __int128)(H - 1) * (uint64_t)c->head_stride + (uint64_t)D;
   if (extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
-  const int64_t bytes = 2 * (int64_t)extent;
+  const int64_t bytes = elem * (int64_t)extent;
   const int64_t rows = r->q.batch <= 0 ? 1 : r->q.batch;
   if (ranges_overlap(c->k_cache, bytes, c->v_cache, bytes)) return SQLLM_E_SHAPE;
   void* const cache[2] = {c->k_cache, c->v_cache};
@@ -1421,8 +1433,10 @@ static int check_kv_cache(const sqllm_qkv_rope* r, const sqllm_kv_cache* c, cons
 // q, k and v as the three-op group of the fused linear (same route, plan and validation), finished by the qkv kernel
 // `nm` (sqllm_qkv_rope_norm_*): vec is the un-normalised hidden state and the kernel is the norm front's
 // `cache_entry` (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*): k and v go to the KV cache `c`, and out_k / out_v may be NULL
+// `fp8` (sqllm_qkv_rope_cache_fp8_* / sqllm_qkv_rope_norm_cache_fp8_*, with `cache_entry`): the cache is `c8`, of 1-byte e4m3fn elements
+static bool fp8_scale_ok(float s) { return __builtin_isfinite(s) && s > 0.0f && __builtin_isfinite(1.0f / s); }
 static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool bf16, const sqllm_rmsnorm* nm = nullptr, bool cache_entry = false,
-                           const sqllm_kv_cache* c = nullptr) {
+                           const sqllm_kv_cache* c = nullptr, bool fp8 = false, const sqllm_kv_cache_fp8* c8 = nullptr) {
   if (!r) return SQLLM_E_NULL;
   const sqllm_op* m[3] = {&r->q, &r->k, &r->v};
   void* const out[3] = {r->out_q, r->out_k, r->out_v};
@@ -1459,8 +1473,22 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
     if (nm && m[0]->K > 0 && norm_weight_overlaps(nm, m[0]->K, r->workspace, ws_bytes)) return SQLLM_E_SHAPE;
   }
   sqllm::KvCache kc = {};
+  sqllm_kv_cache c16;
+  if (fp8 && c8) {  // (the fields the two descriptors share; the scales are judged behind the linear's validation)
+    c16.k_cache = c8->k_cache;
+    c16.v_cache = c8->v_cache;
+    c16.slots = c8->slots;
+    c16.n_slots = c8->n_slots;
+    c16.slot_stride = c8->slot_stride;
+    c16.head_stride = c8->head_stride;
+    c = &c16;
+    kc.fp8 = true;
+    kc.scales_ok = fp8_scale_ok(c8->k_scale) && fp8_scale_ok(c8->v_scale);
+    kc.inv_k_scale = 1.0f / c8->k_scale;
+    kc.inv_v_scale = 1.0f / c8->v_scale;
+  }
   if (cache_entry) {
-    const int rc = check_kv_cache(r, c, nm, r->q.N > 0 && r->k.N > 0 && r->v.N > 0);
+    const int rc = check_kv_cache(r, c, nm, r->q.N > 0 && r->k.N > 0 && r->v.N > 0, fp8 ? 1 : 2);
     if (rc != SQLLM_OK) return rc;
     kc.k_cache = c->k_cache;
     kc.v_cache = c->v_cache;
@@ -1527,6 +1555,21 @@ int sqllm_qkv_rope_norm_cache_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm*
   return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, true, nm, true, c);
 }
 
+int sqllm_qkv_rope_cache_fp8_f16(const sqllm_qkv_rope* r, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream) {
+  return launch_qkv_rope(r, stream, false, nullptr, true, nullptr, true, c);
+}
+int sqllm_qkv_rope_cache_fp8_bf16(const sqllm_qkv_rope* r, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream) {
+  return launch_qkv_rope(r, stream, true, nullptr, true, nullptr, true, c);
+}
+int sqllm_qkv_rope_norm_cache_fp8_f16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, false, nm, true, nullptr, true, c);
+}
+int sqllm_qkv_rope_norm_cache_fp8_bf16(const sqllm_qkv_rope* r, const sqllm_rmsnorm* nm, const sqllm_kv_cache_fp8* c, sqllm_stream_t stream) {
+  const int rc = check_rmsnorm(nm);
+  return rc != SQLLM_OK ? rc : launch_qkv_rope(r, stream, true, nm, true, nullptr, true, c);
+}
+
 // Decode attention (sqllm_attn_decode_*): the partitions of the launch, from HOST fields alone.  capacity is what the table
 // can address, clipped to what an int32 seq_lens can ask for.
 static int64_t attn_capacity(int32_t max_blocks, int32_t block_size) {
@@ -1544,7 +1587,10 @@ int64_t sqllm_attn_decode_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
   return (int64_t)batch * n_q_heads * attn_parts(max_blocks, block_size) * (head_dim + 2) * 4;
 }
 
-static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream, bool bf16) {
+// `a8` (sqllm_attn_decode_fp8_*): the descriptor the fields of `a` were taken from -- the caches hold 1-byte e4m3fn elements,
+// their strides and extents count bytes and they need no alignment; its scales are judged last
+static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream, bool bf16, const sqllm_attn_decode_fp8* a8 = nullptr) {
+  const int celem = a8 ? 1 : 2;  // bytes per cache element
   if (!a || !a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || !a->workspace) return SQLLM_E_NULL;
   const int64_t D = a->head_dim;
   if (a->batch < 1 || a->n_q_heads < 1 || a->n_kv_heads < 1 || D < 1 || a->n_slots < 1 || a->block_size < 1 || a->max_blocks < 1 ||
@@ -1566,16 +1612,22 @@ static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream,
   if (!__builtin_isfinite(a->scale)) return SQLLM_E_OPTION;
   const int64_t ws_bytes = sqllm_attn_decode_workspace_bytes(a->batch, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
   const void* const in[5] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens};
-  const int64_t in_bytes[5] = {2 * (int64_t)q_extent, 2 * (int64_t)extent, 2 * (int64_t)extent,
+  const int64_t in_bytes[5] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
                                4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch};
   for (int i = 0; i < 5; ++i)
     if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i]))
       return SQLLM_E_SHAPE;
   if (ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
-  if (((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->out) | reinterpret_cast<uintptr_t>(a->k_cache) |
-        reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0 ||
+  if (((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->out)) & 1u) != 0 ||
+      (!a8 && ((reinterpret_cast<uintptr_t>(a->k_cache) | reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0) ||
       (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0)
     return SQLLM_E_ALIGN;
+  float scale = a->scale;
+  if (a8) {
+    if (!fp8_scale_ok(a8->k_scale) || !fp8_scale_ok(a8->v_scale)) return SQLLM_E_OPTION;
+    scale = a->scale * a8->k_scale;  // (rounded once, here)
+    if (!__builtin_isfinite(scale)) return SQLLM_E_OPTION;
+  }
   sqllm::AttnDecode d;
   d.q = a->q;
   d.out = a->out;
@@ -1597,11 +1649,42 @@ static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream,
   d.head_stride = a->head_stride;
   d.q_stride = a->q_stride;
   d.out_stride = a->out_stride;
-  d.scale = a->scale;
+  d.scale = scale;
   d.bf16 = bf16;
-  const hipError_t e = sqllm::g_launch_attn_decode ? sqllm::g_launch_attn_decode(d, static_cast<hipStream_t>(stream)) : hipErrorNotSupported;
+  d.v_scale = a8 ? a8->v_scale : 1.0f;
+  const auto launch = a8 ? sqllm::g_launch_attn_decode_fp8 : sqllm::g_launch_attn_decode;
+  const hipError_t e = launch ? launch(d, static_cast<hipStream_t>(stream)) : hipErrorNotSupported;
   return static_cast<int>(e);
 }
+
+// the fp8 entries: the fields the two descriptors share, then the checks and the launch above
+static int launch_attn_decode_fp8(const sqllm_attn_decode_fp8* a8, sqllm_stream_t stream, bool bf16) {
+  if (!a8) return SQLLM_E_NULL;
+  sqllm_attn_decode a;
+  a.q = a8->q;
+  a.out = a8->out;
+  a.k_cache = a8->k_cache;
+  a.v_cache = a8->v_cache;
+  a.block_table = a8->block_table;
+  a.seq_lens = a8->seq_lens;
+  a.batch = a8->batch;
+  a.n_q_heads = a8->n_q_heads;
+  a.n_kv_heads = a8->n_kv_heads;
+  a.head_dim = a8->head_dim;
+  a.n_slots = a8->n_slots;
+  a.block_size = a8->block_size;
+  a.max_blocks = a8->max_blocks;
+  a.table_stride = a8->table_stride;
+  a.slot_stride = a8->slot_stride;
+  a.head_stride = a8->head_stride;
+  a.q_stride = a8->q_stride;
+  a.out_stride = a8->out_stride;
+  a.scale = a8->scale;
+  a.workspace = a8->workspace;
+  return launch_attn_decode(&a, stream, bf16, a8);
+}
+int sqllm_attn_decode_fp8_f16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream) { return launch_attn_decode_fp8(a, stream, false); }
+int sqllm_attn_decode_fp8_bf16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream) { return launch_attn_decode_fp8(a, stream, true); }
 
 int sqllm_attn_decode_f16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, false); }
 int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, true); }

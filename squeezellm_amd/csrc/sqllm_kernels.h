@@ -178,9 +178,16 @@ struct KvCache {
   int n_slots;
   int64_t slot_stride, head_stride;  // in elements
   bool write_out_k, write_out_v;     // false: the caller gave no such output, and the segment's out16 is a stand-in to be ignored
+  // the fp8 entries (sqllm_qkv_rope_cache_fp8_* / sqllm_qkv_rope_norm_cache_fp8_*): the caches hold 1-byte e4m3fn elements, the
+  // strides count bytes, and the launch goes to the kernels of sqllm_linear_qkv_cache_fp8.hip / sqllm_linear_qkv_norm_cache_fp8.hip
+  bool fp8;
+  bool scales_ok;                    // both scales finite and positive with finite reciprocals (rejected behind the linear's validation)
+  float inv_k_scale, inv_v_scale;    // 1 / k_scale, 1 / v_scale, fp32
 };
 extern hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream);
 extern hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream);
+extern hipError_t (*g_launch_linear_qkv_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream);
+extern hipError_t (*g_launch_linear_qkv_norm_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream);
 // decode attention over that cache (sqllm_attn_decode_f16 / _bf16), on the kernels of sqllm_attn_decode.hip: the partials of
 // every (row, kv head, partition of kAttnPartition keys), then -- with more than one partition -- the combine.  A hook, as above.
 constexpr int kAttnPartition = 256;  // keys per partition (SQLLM_ATTN_PARTITION of include/sqllm_hip.h)
@@ -198,8 +205,56 @@ struct AttnDecode {
   int64_t slot_stride, head_stride, q_stride, out_stride;  // in elements
   float scale;
   bool bf16;
+  float v_scale;           // the fp8 entries only (scale then holds scale * k_scale, rounded once)
 };
 extern hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream);
+// ... over a cache of 1-byte e4m3fn elements (sqllm_attn_decode_fp8_f16 / _bf16), on the partial kernels of sqllm_attn_decode_fp8.hip;
+// strides in bytes.  A hook, as above.
+extern hipError_t (*g_launch_attn_decode_fp8)(const AttnDecode& d, hipStream_t stream);
+// The kernels' argument (sqllm_attn_decode.hip: the partials and the combine; sqllm_attn_decode_fp8.hip: the partials over bytes).
+struct AttnArgs {
+  const void* q;
+  void* out;
+  const void* k_cache;
+  const void* v_cache;
+  const int* block_table;
+  const int* seq_lens;
+  float* ws_acc;  // [batch, n_q_heads, n_parts, head_dim]
+  float* ws_ml;   // [batch, n_q_heads, n_parts, 2]
+  long long q_stride, out_stride;
+  unsigned slot_stride, head_stride;  // (below 2^32 wherever they are multiplied: checked by the host)
+  int n_q_heads, group, n_slots, block_size, table_stride;
+  int capacity;  // min(max_blocks * block_size, INT32_MAX)
+  int n_parts;
+  float scale;
+};
+inline AttnArgs make_attn_args(const AttnDecode& d) {
+  AttnArgs k;
+  k.q = d.q;
+  k.out = d.out;
+  k.k_cache = d.k_cache;
+  k.v_cache = d.v_cache;
+  k.block_table = d.block_table;
+  k.seq_lens = d.seq_lens;
+  k.ws_acc = static_cast<float*>(d.workspace);
+  k.ws_ml = k.ws_acc + (long long)d.batch * d.n_q_heads * d.n_parts * d.head_dim;
+  k.q_stride = d.q_stride;
+  k.out_stride = d.out_stride;
+  k.slot_stride = (unsigned)d.slot_stride;
+  k.head_stride = (unsigned)d.head_stride;
+  k.n_q_heads = d.n_q_heads;
+  k.group = d.n_q_heads / d.n_kv_heads;
+  k.n_slots = d.n_slots;
+  k.block_size = d.block_size;
+  k.table_stride = d.table_stride;
+  k.capacity = d.capacity;
+  k.n_parts = d.n_parts;
+  k.scale = d.scale;
+  return k;
+}
+// the combine of sqllm_attn_decode.hip (it does not see the cache): one workgroup of head_dim threads per (query head, row) over
+// the partials in the workspace.  A hook that file sets, so that the byte caches' partials are followed by the same kernel.
+extern hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

@@ -1,0 +1,113 @@
+// sqllm_linear_qkv_cache_fp8.hip -- the attention front that writes k and v straight into a KV cache of 1-byte OCP e4m3fn
+// elements, as ONE kernel (include/sqllm_hip.h: sqllm_qkv_rope_cache_fp8_f16 / _bf16): sqllm_linear_qkv_cache.hip's kernel,
+// statement for statement, with the finishing policy RopeCacheFp8Finish (sqllm_cache_fp8_finish.h) in the place of
+// RopeCacheFinish.  For row b, s = slots[b], column n = h * D + d of member k (resp. v), x the fp32 value that out_k[b, n]
+// would round to 16 bits:
+//
+//     k_cache[s * slot_stride + h * head_stride + d] = e4m3_rne(clamp(x / k_scale, +-448))        0 <= s < n_slots
+//
+// in bytes, and nothing of row b when s is outside that range.  A finisher of v stores one byte; the one finisher of a pair
+// of k that completes it converts both elements in one packed conversion and stores two bytes, `dist` apart.  out_k / out_v
+// are written as in the parent when given.  The cache's arguments, the two reciprocals among them, lie behind the rotary
+// ones in the kernel-argument segment and are read there by the finisher that needs them (cache_fp8_args).
+#include <stddef.h>
+
+#include "sqllm_cache_fp8_finish.h"
+#include "sqllm_fused.h"
+
+namespace sqllm {
+
+// the kernel's explicit arguments as the ABI lays them out (natural alignment, in order)
+struct QkvCacheFp8KernArgs {
+  const void* x;
+  GroupArgs ga;
+  RopeArgs ra;
+  KvCacheFp8Args fa;
+};
+constexpr unsigned kKvCacheFp8ArgsOffset = offsetof(QkvCacheFp8KernArgs, fa);
+static_assert(offsetof(QkvCacheFp8KernArgs, ra) == kRopeArgsAt, "rope_args() reads the third argument");
+static_assert(kKvCacheFp8ArgsOffset == kKvCacheFp8ArgsAt, "cache_fp8_args() reads the fourth argument");
+
+template <int BITS, int BT, typename OT>
+__global__ void __launch_bounds__(kWaves * 64, fused_min_waves(BITS, BT, 0))
+sqllm_linear_qkv_cache_fp8_kernel(const void* xv, const GroupArgs ga, const RopeArgs ra /* read through rope_args() */,
+                                  const KvCacheFp8Args fa /* read through cache_fp8_args() */) {
+  constexpr int WAVES = kWaves;
+  constexpr bool HALF = fused_half_stages(BITS, BT);
+  constexpr int T = WAVES * 64;
+  constexpr int kLds = lds_floats(Fmt<BITS>::kLut, WAVES, BT, BITS == 3 && BT == 1 && SQLLM_HALF_STAGES && SQLLM_PAIR3);
+  __shared__ __attribute__((aligned(16))) float lds[kLds];
+  using XT = OT;
+  using AT = u64;
+  using FIN = RopeCacheFp8Finish<OT>;
+  const XT* x = reinterpret_cast<const XT*>(xv);
+
+  // one round of scalar loads for vec's address, the block table and segment 0 (see sqllm_fused_matvec)
+  Segment sg;
+  const int bid = pick_segment(ga, x, sg);
+  const KernelGeom& gm = sg.gm;
+  const int b0 = blockIdx.y * BT;
+  int nb = gm.batch - b0;
+  if (nb > BT) nb = BT;
+  // (three segments: the host launches nothing else here)
+  const FIN fin{(int)blockIdx.x >= ga.block0[2] ? 2 : (int)blockIdx.x >= ga.block0[1] ? 1 : 0};
+
+  // role by block id within the segment: [sparse | pad | dense] or, with sparse_last, [dense | sparse]
+  int d, sp;
+  if (gm.sparse_last & 1) {
+    d = bid;
+    sp = bid - gm.dense_blocks;
+  } else {
+    d = bid - gm.dense_block0;
+    sp = bid < gm.dense_block0 ? bid : -1;
+  }
+  if (d >= 0 && d < gm.dense_blocks) {
+    dense_role<BITS, BT, WAVES, 0, XT, HALF, false, FIN>(x, reinterpret_cast<const u32x4*>(sg.q), sg.y, sg.lut, gm.K, gm.N, b0, nb, d,
+                                                         gm.col_tiles, gm.units_total, gm.units_per_wg, lds, sg, &sg, fin);
+  } else if (sp >= 0 && sp < gm.csr_blocks) {
+    if (gm.dense_prio == 2) __builtin_amdgcn_s_setprio(1);
+    csr_role<T, BT, XT, AT, false, false, NoGate, kCsrChunk, FIN>(x, reinterpret_cast<AT*>(sg.y), sg.rows, sg.cols, sg.vals, gm.nnz, gm.K, gm.N,
+                                                                  b0, nb, sp, lds, &sg, gm.sparse_last >> 1, nullptr, 0, nullptr, NoGate(), fin);
+  } else if (sp >= gm.csr_blocks && sp < gm.csr_blocks + gm.topx_blocks) {
+    // (never taken when the plan folds the top-X rows into the dense tiles)
+    if (gm.dense_prio == 2) __builtin_amdgcn_s_setprio(1);
+    topx_role<T, XT, AT, false, NoGate, BT, FIN>(x, reinterpret_cast<AT*>(sg.y), sg.full_rows, sg.full_idx, gm.topX, gm.K, gm.N, b0, nb,
+                                                 sp - gm.csr_blocks, lds);
+  }
+}
+
+template <int BITS, int BT, typename OT>
+static hipError_t launch_qkv_fp8_cache_inst(const LaunchArgs& a, const RopeArgs& ra, const KvCacheFp8Args& fa, hipStream_t stream) {
+  const int batch = a.ga.seg[0].gm.batch;
+  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
+  auto kern = sqllm_linear_qkv_cache_fp8_kernel<BITS, BT, OT>;
+  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, ra, fa);
+}
+
+template <int BITS, typename OT>
+static hipError_t launch_qkv_fp8_cache_bits(const LaunchArgs& a, const RopeArgs& ra, const KvCacheFp8Args& fa, hipStream_t stream) {
+  switch (batch_tile(a.ga.seg[0].gm.batch)) {
+    case 1: return launch_qkv_fp8_cache_inst<BITS, 1, OT>(a, ra, fa, stream);
+    case 2: return launch_qkv_fp8_cache_inst<BITS, 2, OT>(a, ra, fa, stream);
+    case 4: return launch_qkv_fp8_cache_inst<BITS, 4, OT>(a, ra, fa, stream);
+    default: return launch_qkv_fp8_cache_inst<BITS, 8, OT>(a, ra, fa, stream);
+  }
+}
+
+// q, k and v (segments 0, 1, 2) over one 16-bit vec (a0.ga; a0.bf16: its type); r: the rotation; kc: the byte cache and its scales
+static hipError_t launch_linear_qkv_cache_fp8(int bits, const LaunchArgs& a0, const QkvRope& r, const KvCache& kc, hipStream_t stream) {
+  if (a0.ga.n_seg != 3 || !r.pair_q || !r.pair_k || !r.cos || !r.sin || !r.positions || r.head_dim < 2 || (r.head_dim & 1) || !kc.k_cache ||
+      !kc.v_cache || !kc.slots || kc.n_slots < 1 || !kc.fp8 || !kc.scales_ok || a0.ga.seg[1].gm.N != a0.ga.seg[2].gm.N ||
+      a0.ga.seg[2].gm.N % r.head_dim)
+    return hipErrorInvalidValue;
+  const LaunchArgs a = without_left_out(a0, kc);
+  const RopeArgs ra = make_rope_args(a, r);
+  const KvCacheFp8Args fa = make_kv_cache_fp8_args(a, r, kc);
+  if (a.bf16) return bits == 4 ? launch_qkv_fp8_cache_bits<4, __bf16>(a, ra, fa, stream) : launch_qkv_fp8_cache_bits<3, __bf16>(a, ra, fa, stream);
+  return bits == 4 ? launch_qkv_fp8_cache_bits<4, _Float16>(a, ra, fa, stream) : launch_qkv_fp8_cache_bits<3, _Float16>(a, ra, fa, stream);
+}
+
+// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
+static const bool g_qkv_cache_fp8_registered = (g_launch_linear_qkv_cache_fp8 = launch_linear_qkv_cache_fp8, true);
+
+}  // namespace sqllm

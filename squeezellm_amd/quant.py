@@ -690,6 +690,38 @@ def _torch_rope(s: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin
 
 _QKV_CACHE_ENTRY = {torch.float16: "sqllm_qkv_rope_cache_f16", torch.bfloat16: "sqllm_qkv_rope_cache_bf16"}
 _QKV_NORM_CACHE_ENTRY = {torch.float16: "sqllm_qkv_rope_norm_cache_f16", torch.bfloat16: "sqllm_qkv_rope_norm_cache_bf16"}
+_QKV_CACHE_FP8_ENTRY = {torch.float16: "sqllm_qkv_rope_cache_fp8_f16", torch.bfloat16: "sqllm_qkv_rope_cache_fp8_bf16"}
+_QKV_NORM_CACHE_FP8_ENTRY = {torch.float16: "sqllm_qkv_rope_norm_cache_fp8_f16", torch.bfloat16: "sqllm_qkv_rope_norm_cache_fp8_bf16"}
+FP8_KV_DTYPES = (torch.float8_e4m3fn, torch.uint8)  # what an fp8 KV cache may be held as: OCP e4m3fn elements, or their bytes
+FP8_KV_MAX = 448.0  # the largest finite e4m3fn value
+
+
+def fp8_kv_scale(absmax):
+    """The scale of an fp8 KV cache whose largest magnitude is to be `absmax` (a float or a tensor; calibration is the caller's)."""
+    return absmax / FP8_KV_MAX
+
+
+def _check_fp8_scales(fp8: bool, k_scale, v_scale):
+    """The scales of forward(): both with an fp8 cache -- finite, positive, with finite fp32 reciprocals --, none without."""
+    if not fp8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError("k_scale and v_scale belong to a float8_e4m3fn (or uint8) KV cache: this call has none")
+        return None, None
+    if k_scale is None or v_scale is None:
+        raise ValueError("an fp8 KV cache needs both k_scale and v_scale")
+    out = []
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        f = torch.tensor(float(t), dtype=torch.float32)
+        if not bool(torch.isfinite(f)) or float(f) <= 0.0 or not bool(torch.isfinite(1.0 / f)):
+            raise ValueError(f"{name} must be finite and positive with a finite fp32 reciprocal, got {t}")
+        out.append(float(f))
+    return out[0], out[1]
+
+
+def _fp8_bytes(x32: torch.Tensor, scale: float) -> torch.Tensor:
+    """The bytes of include/sqllm_hip.h's encoding of fp32 values: e4m3_rne(clamp(x * (1 / scale), +-448)), NaN staying NaN."""
+    inv = (1.0 / torch.tensor(scale, dtype=torch.float32)).to(x32.device)
+    return (x32.float() * inv).clamp(-FP8_KV_MAX, FP8_KV_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
 
 
 def kv_cache_view(cache: torch.Tensor, layout: str = "nhd") -> torch.Tensor:
@@ -735,6 +767,11 @@ def _torch_cache_write(cache: torch.Tensor, slots: torch.Tensor, rows_: torch.Te
     flat = cache.as_strided(((n_slots - 1) * ss + (H - 1) * hs + D,), (1,), cache.storage_offset())
     at = (s[ok][:, None, None] * ss + torch.arange(H, device=s.device)[None, :, None] * hs + torch.arange(D, device=s.device)[None, None, :])
     flat.index_put_((at.reshape(-1),), rows_.reshape(-1, H, D)[ok].reshape(-1))
+
+
+def _torch_cache_write_fp8(cache: torch.Tensor, slots: torch.Tensor, rows32: torch.Tensor, scale: float) -> None:
+    """_torch_cache_write for an fp8 cache: the fp32 values `rows32`, encoded once, as bytes (torch has no indexing for float8)."""
+    _torch_cache_write(cache.view(torch.uint8), slots, _fp8_bytes(rows32, scale))
 
 
 class QuantQKVRopeFused(nn.Module):
@@ -786,7 +823,15 @@ class QuantQKVRopeFused(nn.Module):
     saves, graph-replayed (tools/kv_cache_bench.py, table in DESIGN.md 4.4, raw output profiles/kv_cache_bench.txt; the shapes of
     qkv_rope_bench.py, a slot-major cache): two index_copy_ behind the parent cost 5.6 - 7.2 us per layer at any row count, the
     scattered stores 0.1 - 0.4 us at 1 row and 1.4 - 4.4 us at 16 -- 5.4 - 6.1 us less per layer at 1 row, 2.7 - 5.3 us less at 16,
-    faster than the copies on all 48 points."""
+    faster than the copies on all 48 points.
+
+    module(..., k_scale=None, v_scale=None) -- keyword arguments of the module call, `self.qkv_rope(x, ..., k_scale=, v_scale=)`,
+    not of `forward`, whose parameter list stays what it was.  Caches of torch.float8_e4m3fn (or uint8: the same bytes) select the fp8 entries
+    (sqllm_qkv_rope_cache_fp8_* / sqllm_qkv_rope_norm_cache_fp8_*; include/sqllm_hip.h, sqllm_kv_cache_fp8): each element is
+    e4m3_rne(clamp(x / scale, +-448)) of the fp32 value x BEFORE its rounding to 16 bits, one scale per cache (fp8_kv_scale; finite
+    and positive floats, calibrated by the caller).  Both scales are required then; scales with a 16-bit cache, or an fp8 cache
+    without them, are a ValueError.  The returned k and v are the 16-bit ones, as ever.  The dense and fallback routes make the
+    same writes by the same formula in torch."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
 
@@ -811,6 +856,17 @@ class QuantQKVRopeFused(nn.Module):
     def last_route(self):
         """"qkv_rope", "qkv_rope_norm", "dense" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
+
+    def __call__(self, *args, k_scale=None, v_scale=None, **kwargs):
+        """forward(*args, **kwargs) with the two scales of an fp8 KV cache.  They are keyword arguments of the module CALL:
+        forward's own parameter list is pinned (tests/test_qkv_cache_cpu.py) and stays what it was."""
+        if k_scale is None and v_scale is None:
+            return super().__call__(*args, **kwargs)
+        self.__dict__["_fp8_scales"] = (k_scale, v_scale)
+        try:
+            return super().__call__(*args, **kwargs)
+        finally:
+            del self.__dict__["_fp8_scales"]
 
     def _descriptor(self, dev: int, stream: int):
         """The sqllm_qkv_rope of (device, stream): the members' own pre-marshalled descriptors (QuantLinearLUTFused._descriptor)
@@ -841,12 +897,14 @@ class QuantQKVRopeFused(nn.Module):
         if self.v.outfeatures != N:
             raise ValueError(f"a KV cache needs k and v of one width, got {N} and {self.v.outfeatures}")
         for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-            if not isinstance(t, torch.Tensor) or t.dtype != x.dtype or t.device != x.device:
-                raise ValueError(f"{name} must be a {x.dtype} tensor on {x.device}, got {getattr(t, 'dtype', type(t).__name__)} on "
-                                 f"{getattr(t, 'device', None)}")
+            if not isinstance(t, torch.Tensor) or (t.dtype != x.dtype and t.dtype not in FP8_KV_DTYPES) or t.device != x.device:
+                raise ValueError(f"{name} must be a {x.dtype} (or float8_e4m3fn / uint8) tensor on {x.device}, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', None)}")
             if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] * t.shape[2] != N or t.shape[2] != D or t.stride(2) != 1:
                 raise ValueError(f"{name} must be a view [n_slots, {N // D}, {D}] with a contiguous last dimension, got {tuple(t.shape)} "
                                  f"with strides {t.stride()}")
+        if k_cache.dtype != v_cache.dtype:
+            raise ValueError(f"k_cache and v_cache must have one dtype, got {k_cache.dtype} and {v_cache.dtype}")
         if k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride():
             raise ValueError(f"k_cache and v_cache must have equal shape and strides, got {tuple(k_cache.shape)} / {k_cache.stride()} and "
                              f"{tuple(v_cache.shape)} / {v_cache.stride()}")
@@ -858,6 +916,7 @@ class QuantQKVRopeFused(nn.Module):
 
     def forward(self, x: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, norm_weight=None,
                 norm_eps: float = 1e-6, k_cache=None, v_cache=None, slots=None, return_kv: bool = True):
+        k_scale, v_scale = self.__dict__.get("_fp8_scales", (None, None))  # (the module call's keyword arguments: __call__)
         q, k, v = self.q, self.k, self.v
         K, D, half = q.infeatures, self.head_dim, self.head_dim // 2
         if x.shape[-1] != K:
@@ -867,6 +926,8 @@ class QuantQKVRopeFused(nn.Module):
         x2 = x if x.dim() == 2 else x.reshape(-1, K)
         rows = x2.shape[0]
         cached = self._check_cache(x, rows, k_cache, v_cache, slots, return_kv)
+        fp8 = cached and k_cache.dtype in FP8_KV_DTYPES and k_cache.dtype != x.dtype
+        k_scale, v_scale = _check_fp8_scales(fp8, k_scale, v_scale)
         for name, t in (("cos", cos), ("sin", sin)):
             if t.dim() != 2 or t.shape[1] != half or t.shape[0] < 1 or t.shape != cos.shape or t.device != x.device:
                 raise ValueError(f"{name} must be [n_pos, {half}] on {x.device}, got {tuple(t.shape)} on {t.device}")
@@ -892,11 +953,16 @@ class QuantQKVRopeFused(nn.Module):
                 xin = x2 if norm_weight is None else _torch_rmsnorm(x2, norm_weight, norm_eps)  # (fp32 sums from fp32 xn)
                 sums = [QuantLinearLUT.forward(m, xin) for m in (q, k, v)]
             oq = _torch_rope(sums[0], pos, cos, sin, D, self.layout, x.dtype)
-            ok = _torch_rope(sums[1], pos, cos, sin, D, self.layout, x.dtype)
+            ok32 = _torch_rope(sums[1], pos, cos, sin, D, self.layout, torch.float32)  # (the value before its one rounding)
+            ok = ok32.to(x.dtype)
             ov = sums[2].to(x.dtype)
             if cached:
-                _torch_cache_write(k_cache, slots, ok)
-                _torch_cache_write(v_cache, slots, ov)
+                if fp8:  # (the same fp32 values, rounded once, straight to fp8)
+                    _torch_cache_write_fp8(k_cache, slots, ok32, k_scale)
+                    _torch_cache_write_fp8(v_cache, slots, sums[2].float(), v_scale)
+                else:
+                    _torch_cache_write(k_cache, slots, ok)
+                    _torch_cache_write(v_cache, slots, ov)
                 if not return_kv:
                     return oq.reshape(*lead, -1), None, None
             return oq.reshape(*lead, -1), ok.reshape(*lead, -1), ov.reshape(*lead, -1)
@@ -931,16 +997,22 @@ class QuantQKVRopeFused(nn.Module):
                 sl = sl.to(torch.int32)  # (a kernel)
             if not sl.is_contiguous():
                 sl = sl.contiguous()
-            kcs = self.__dict__.setdefault("_kv", {})
+            kcs = self.__dict__.setdefault("_kv8" if fp8 else "_kv", {})
             hit = kcs.get((dev, stream))
             if hit is None:
-                c = _lib.SqllmKvCache()
+                c = _lib.SqllmKvCacheFp8() if fp8 else _lib.SqllmKvCache()
                 hit = kcs[(dev, stream)] = (c, ctypes.byref(c))
             c, cref = hit
             c.k_cache, c.v_cache, c.slots = k_cache.data_ptr(), v_cache.data_ptr(), sl.data_ptr()
             c.n_slots, c.slot_stride = k_cache.shape[0], k_cache.stride(0)
             c.head_stride = k_cache.stride(1) if k_cache.shape[1] > 1 else D  # (one head: its stride is anything, and never used)
-            if nref is not None:
+            if fp8:
+                c.k_scale, c.v_scale = k_scale, v_scale
+                if nref is not None:
+                    quant_cuda._launch(quant_cuda._fn(_QKV_NORM_CACHE_FP8_ENTRY[x.dtype]), dev, (ref, nref, cref))
+                else:
+                    quant_cuda._launch(quant_cuda._fn(_QKV_CACHE_FP8_ENTRY[x.dtype]), dev, (ref, cref))
+            elif nref is not None:
                 quant_cuda._launch(quant_cuda._fn(_QKV_NORM_CACHE_ENTRY[x.dtype]), dev, (ref, nref, cref))
             else:
                 quant_cuda._launch(quant_cuda._fn(_QKV_CACHE_ENTRY[x.dtype]), dev, (ref, cref))
@@ -973,6 +1045,7 @@ def fuse_qkv_rope(module: nn.Module, q: str = "q_proj", k: str = "k_proj", v: st
 
 
 _ATTN_ENTRY = {torch.float16: "sqllm_attn_decode_f16", torch.bfloat16: "sqllm_attn_decode_bf16"}
+_ATTN_FP8_ENTRY = {torch.float16: "sqllm_attn_decode_fp8_f16", torch.bfloat16: "sqllm_attn_decode_fp8_bf16"}
 ATTN_PARTITION = _lib.ATTN_PARTITION  # keys per partition of the decode attention's kernel (SQLLM_ATTN_PARTITION)
 
 
@@ -983,9 +1056,12 @@ def static_cache_blocks(batch: int, n_kv_heads: int, device=None) -> torch.Tenso
     return (torch.arange(int(batch), dtype=torch.int32, device=device) * int(n_kv_heads)).reshape(-1, 1)
 
 
-def _torch_attn_decode(q, k_cache, v_cache, block_table, seq_lens, block_size, n_heads, n_kv_heads, head_dim, scale, dtype):
+def _torch_attn_decode(q, k_cache, v_cache, block_table, seq_lens, block_size, n_heads, n_kv_heads, head_dim, scale, dtype,
+                       k_scale=None, v_scale=None):
     """The formulas of sqllm_attn_decode (include/sqllm_hip.h) in torch: fp32, rounded once to `dtype`; the +0 row, the NaN
-    rows; unaddressed slots never enter a result.  q: [rows, n_heads * head_dim]."""
+    rows; unaddressed slots never enter a result.  q: [rows, n_heads * head_dim].  With `k_scale` and `v_scale` the caches
+    hold e4m3fn bytes (sqllm_attn_decode_fp8): scale * k_scale is the score's scale, rounded once to fp32, and v_scale
+    multiplies the sum over the keys."""
     rows, D, G = q.shape[0], head_dim, n_heads // n_kv_heads
     n_slots, H = k_cache.shape[0], k_cache.shape[1]
     ss, hs = k_cache.stride(0), (k_cache.stride(1) if H > 1 else D)
@@ -1005,18 +1081,29 @@ def _torch_attn_decode(q, k_cache, v_cache, block_table, seq_lens, block_size, n
     at = slot[:, :, None, None] * ss + torch.arange(H, device=dev)[None, None, :, None] * hs + torch.arange(D, device=dev)[None, None, None, :]
     zero = torch.zeros((), dtype=torch.float32, device=dev)
 
+    fp8 = k_scale is not None
+
     def gather(cache):
+        if fp8:  # (through the bytes: torch has no indexing for float8)
+            cache = cache.view(torch.uint8)
         flat = cache.as_strided(((n_slots - 1) * ss + (H - 1) * hs + D,), (1,), cache.storage_offset())
-        return torch.where(valid[:, :, None, None], flat[at.reshape(-1)].reshape(at.shape).float(), zero)  # [rows, S, H, D]
+        got = flat[at.reshape(-1)]
+        got = got.view(torch.float8_e4m3fn).float() if fp8 else got.float()
+        return torch.where(valid[:, :, None, None], got.reshape(at.shape), zero)  # [rows, S, H, D]
 
     k, v = gather(k_cache), gather(v_cache)
     qf = q.float().reshape(rows, n_kv_heads, G, D)
+    if fp8:
+        scale = float(torch.tensor(float(scale), dtype=torch.float32) * torch.tensor(float(k_scale), dtype=torch.float32))
     s = torch.einsum("bhgd,bshd->bhgs", qf, k) * float(scale)
     s = torch.where(valid[:, None, None, :], s, torch.full((), float("-inf"), dtype=torch.float32, device=dev))
     m = s.max(dim=-1, keepdim=True).values
     m = torch.where(torch.isinf(m) & (m < 0), torch.zeros_like(m), m)  # (a row without keys: w = 0 everywhere)
     w = torch.where(valid[:, None, None, :], torch.exp(s - m), zero)
-    o = torch.einsum("bhgs,bshd->bhgd", w, v) / w.sum(dim=-1, keepdim=True)
+    o = torch.einsum("bhgs,bshd->bhgd", w, v)
+    if fp8:
+        o = o * torch.tensor(float(v_scale), dtype=torch.float32, device=dev)
+    o = o / w.sum(dim=-1, keepdim=True)
     o = o.reshape(rows, n_heads * D)
     o = torch.where((lens <= 0)[:, None], zero, o)
     o = torch.where((over | bad)[:, None], torch.full((), float("nan"), dtype=torch.float32, device=dev), o)
@@ -1056,7 +1143,13 @@ class DecodeAttention(nn.Module):
     table in DESIGN.md 4.4, raw output profiles/attn_decode_bench.txt; 32/32 and 32/8 heads of 128, 1 / 4 / 16 rows, 128 / 1024 /
     4096 keys in a cache of 4096, static and paged, fp16 / bf16): 9.7 - 207 us per call against 160 - 1761 us, faster on all 72
     points; ABOVE the `3 us + bytes / 4.8 TB/s` per-launch fit on all but 32/32 at 4096 keys with 4 and 16 rows (5.3 TB/s there),
-    by up to 3.7x at 16 rows of 128 keys."""
+    by up to 3.7x at 16 rows of 128 keys.
+
+    forward(..., k_scale=None, v_scale=None).  Caches of torch.float8_e4m3fn (or uint8: the same bytes), as QuantQKVRopeFused
+    writes them with the same two scales, take the kernels for byte caches (sqllm_attn_decode_fp8_f16 / _bf16; include/sqllm_hip.h,
+    sqllm_attn_decode_fp8): float(k) = k_scale * f32(byte), float(v) = v_scale * f32(byte) in the formulas above, half the bytes
+    read.  Both scales are required then; scales with a 16-bit cache, or an fp8 cache without them, are a ValueError.  The torch
+    fallback dequantises.  Speed against the 16-bit kernel: tools/attn_decode_bench.py --cache fp8, DESIGN.md 4.4."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
 
@@ -1082,12 +1175,14 @@ class DecodeAttention(nn.Module):
         """The cache views as QuantQKVRopeFused._check_cache wants them."""
         D, H = self.head_dim, self.n_kv_heads
         for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-            if not isinstance(t, torch.Tensor) or t.dtype != q.dtype or t.device != q.device:
-                raise ValueError(f"{name} must be a {q.dtype} tensor on {q.device}, got {getattr(t, 'dtype', type(t).__name__)} on "
-                                 f"{getattr(t, 'device', None)}")
+            if not isinstance(t, torch.Tensor) or (t.dtype != q.dtype and t.dtype not in FP8_KV_DTYPES) or t.device != q.device:
+                raise ValueError(f"{name} must be a {q.dtype} (or float8_e4m3fn / uint8) tensor on {q.device}, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', None)}")
             if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] != H or t.shape[2] != D or t.stride(2) != 1:
                 raise ValueError(f"{name} must be a view [n_slots, {H}, {D}] with a contiguous last dimension, got {tuple(t.shape)} "
                                  f"with strides {t.stride()}")
+        if k_cache.dtype != v_cache.dtype:
+            raise ValueError(f"k_cache and v_cache must have one dtype, got {k_cache.dtype} and {v_cache.dtype}")
         if k_cache.shape != v_cache.shape or k_cache.stride() != v_cache.stride():
             raise ValueError(f"k_cache and v_cache must have equal shape and strides, got {tuple(k_cache.shape)} / {k_cache.stride()} and "
                              f"{tuple(v_cache.shape)} / {v_cache.stride()}")
@@ -1095,7 +1190,7 @@ class DecodeAttention(nn.Module):
             raise ValueError(f"the strides of a cache view must be at least head_dim = {D}, got {k_cache.stride()}")
 
     def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
-                out=None, block_size=None) -> torch.Tensor:
+                out=None, block_size=None, k_scale=None, v_scale=None) -> torch.Tensor:
         D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
         W = HQ * D
         if q.shape[-1] != W or q.stride(-1) != 1:
@@ -1104,6 +1199,10 @@ class DecodeAttention(nn.Module):
         if bs is None or bs < 1:
             raise ValueError("block_size must be given, at construction or per call, and be positive")
         self._check_cache(q, k_cache, v_cache)
+        fp8 = k_cache.dtype in FP8_KV_DTYPES and k_cache.dtype != q.dtype
+        k_scale, v_scale = _check_fp8_scales(fp8, k_scale, v_scale)
+        if fp8 and not math.isfinite(float(torch.tensor(self.scale, dtype=torch.float32) * torch.tensor(k_scale, dtype=torch.float32))):
+            raise ValueError(f"scale * k_scale must be finite in fp32, got {self.scale} * {k_scale}")
         lead = q.shape[:-1]
         q2 = q if q.dim() == 2 else q.reshape(-1, W)
         rows = q2.shape[0]
@@ -1123,7 +1222,7 @@ class DecodeAttention(nn.Module):
         kernel = q.dtype in _ATTN_ENTRY and q.is_cuda and D in (64, 128) and HQ // H <= 8 and rows <= 64
         if not kernel:
             self.__dict__["_last_route"] = "fallback"
-            o = _torch_attn_decode(q2, k_cache, v_cache, block_table, seq_lens, bs, HQ, H, D, self.scale, q.dtype)
+            o = _torch_attn_decode(q2, k_cache, v_cache, block_table, seq_lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
             if out is not None:
                 out.copy_(o)
                 return out
@@ -1142,10 +1241,10 @@ class DecodeAttention(nn.Module):
         stream = quant_cuda._raw_stream(dev)
         ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.attn_decode_workspace_bytes(rows, HQ, D, bt.shape[1], bs), q.device,
                            self.GRAPH_WS_MAX_BYTES)
-        descs = self.__dict__.setdefault("_desc", {})
+        descs = self.__dict__.setdefault("_desc8" if fp8 else "_desc", {})
         hit = descs.get((dev, stream))
         if hit is None:
-            a = _lib.SqllmAttnDecode()
+            a = _lib.SqllmAttnDecodeFp8() if fp8 else _lib.SqllmAttnDecode()
             hit = descs[(dev, stream)] = (a, ctypes.byref(a))
         a, ref = hit
         a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
@@ -1158,7 +1257,9 @@ class DecodeAttention(nn.Module):
         a.q_stride = q2.stride(0) if rows > 1 else W
         a.out_stride = o.stride(0) if rows > 1 else W
         a.scale, a.workspace = self.scale, ws.data_ptr()
-        quant_cuda._launch(quant_cuda._fn(_ATTN_ENTRY[q.dtype]), dev, (ref,))
+        if fp8:
+            a.k_scale, a.v_scale = k_scale, v_scale
+        quant_cuda._launch(quant_cuda._fn((_ATTN_FP8_ENTRY if fp8 else _ATTN_ENTRY)[q.dtype]), dev, (ref,))
         return o if out is not None else o.reshape(*lead, W)
 
 

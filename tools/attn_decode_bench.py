@@ -2,6 +2,7 @@
 in ONE process (built like kv_cache_bench.py).
 
     python tools/attn_decode_bench.py [--heads 32/32,32/8] [--rows 1,4,16] [--lens 128,1024,4096] [--dtypes fp16,bf16] [--layers 4] [--reps 3]
+    python tools/attn_decode_bench.py --cache fp8 [...]       # the fp8 KV cache against the 16-bit kernels, the same points
 
 Workload: --layers attention layers with distinct caches and queries, head_dim 128, every row at the same sequence length, in
   * a head-major static cache [rows, H_kv, S = 4096, D] per layer (kv_cache_view "bhsd", static_cache_blocks), and
@@ -17,6 +18,10 @@ One JSON line per point: median us per call (per layer) and spread per way; the 
 TB/s of the two kernels' ways; the per-launch fit of DESIGN.md 5, launches x 3 us + bytes / 4.8 TB/s; whether the kernel is
 faster than sdpa; and the largest |static - sdpa| as a sanity check.  K + V of all layers at short lengths fit the 256 MiB
 Infinity Cache: those points measure on-die reads, and say so (`l3_resident`).
+
+--cache fp8: the ways are static, paged (the 16-bit kernels, as above) and static_fp8, paged_fp8 -- DecodeAttention over the same
+keys quantised to float8_e4m3fn caches of the same two layouts (one scale per cache, fp8_kv_scale of the largest magnitude),
+no sdpa.  Per point: us per call of the four ways, fp8 / 16-bit per layout, and `fp8_slower` naming the layouts where fp8 lost.
 """
 import argparse, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,6 +37,7 @@ ap.add_argument("--lens", default="128,1024,4096")
 ap.add_argument("--dtypes", default="fp16,bf16")
 ap.add_argument("--layers", type=int, default=4)
 ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--cache", default="16", choices=["16", "fp8"])
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 sdpa = torch.nn.functional.scaled_dot_product_attention
@@ -83,6 +89,11 @@ for heads in args.heads.split(","):
             views = [tuple(quant.kv_cache_view(t, "bhsd") for t in pair) for pair in statics]
             sblocks = quant.static_cache_blocks(rows, H, dev)
             qs = [torch.randn((rows, HQ * D), device=dev).to(dt) for _ in range(args.layers)]
+            if args.cache == "fp8":  # the same keys as bytes, in both layouts; one scale per cache
+                scales = [tuple(float(quant.fp8_kv_scale(t.float().abs().max())) for t in pair) for pair in statics]
+                to8 = lambda t, s: (t.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)  # noqa: E731
+                views8 = [tuple(quant.kv_cache_view(to8(t, s), "bhsd") for t, s in zip(pair, sc)) for pair, sc in zip(statics, scales)]
+                pageds8 = [tuple(quant.kv_cache_view(to8(t, s), "nhd") for t, s in zip(pair, sc)) for pair, sc in zip(pageds, scales)]
             ar = torch.arange(S, device=dev)
             for n in map(int, args.lens.split(",")):
                 lens = torch.full((rows,), n, dtype=torch.int32, device=dev)
@@ -112,6 +123,42 @@ for heads in args.heads.split(","):
                     with torch.no_grad():
                         for q, (k, v) in zip(qs, pageds): keep.append(att(q, k, v, table, lens, block_size=BLOCK))
 
+                def run_static8():
+                    keep.clear()
+                    with torch.no_grad():
+                        for q, (k, v), (ks, vs) in zip(qs, views8, scales): keep.append(att(q, k, v, sblocks, lens, block_size=S, k_scale=ks, v_scale=vs))
+
+                def run_paged8():
+                    keep.clear()
+                    with torch.no_grad():
+                        for q, (k, v), (ks, vs) in zip(qs, pageds8, scales): keep.append(att(q, k, v, table, lens, block_size=BLOCK, k_scale=ks, v_scale=vs))
+
+                if args.cache == "fp8":
+                    run_static(); st = keep[0].float(); assert att.last_route == "attn_decode"
+                    run_static8(); s8 = keep[0].float(); assert att.last_route == "attn_decode"
+                    run_paged8(); p8 = keep[0].float()
+                    torch.cuda.synchronize()
+                    diff8, same8 = float((s8 - st).abs().max()), bool(torch.equal(s8, p8))
+                    runs = {"static": run_static, "paged": run_paged, "static_fp8": run_static8, "paged_fp8": run_paged8}
+                    gs = {k: capture(f) for k, f in runs.items()}
+                    for g in gs.values(): timed(g.replay, 3, 2)
+                    ms = {k: [] for k in gs}
+                    order = list(runs)
+                    for r in range(args.reps):
+                        for k in order[r % 4:] + order[:r % 4]: ms[k].append(timed(gs[k].replay))
+                    us = {k: statistics.median(v) * 1e3 / args.layers for k, v in ms.items()}
+                    nbytes = rows * H * n * D * 2 * 2
+                    rec = dict(heads=heads, rows=rows, dtype=dname, seq_len=n, kv_bytes_16=nbytes, kv_bytes_fp8=nbytes // 2,
+                               l3_resident=nbytes * args.layers <= 256 << 20)
+                    for k in order:
+                        rec[f"{k}_us"] = round(us[k], 2)
+                        rec[f"{k}_spread_us"] = round((max(ms[k]) - min(ms[k])) * 1e3 / args.layers, 2)
+                    rec.update(static_fp8_over_16=round(us["static_fp8"] / us["static"], 3), paged_fp8_over_16=round(us["paged_fp8"] / us["paged"], 3),
+                               fp8_slower=[k for k in ("static", "paged") if us[k + "_fp8"] > us[k]],
+                               max_abs_diff_fp8_vs_16=round(diff8, 5), static_fp8_equals_paged_fp8=same8)
+                    print(json.dumps(rec), flush=True)
+                    del gs; keep.clear()
+                    continue
                 run_sdpa(); ref = keep[0].reshape(rows, HQ * D).float()
                 run_static(); st = keep[0].float(); assert att.last_route == "attn_decode"
                 run_paged(); pg = keep[0].float()
@@ -137,5 +184,6 @@ for heads in args.heads.split(","):
                            max_abs_diff_vs_sdpa=round(diff, 5), static_equals_paged=same)
                 print(json.dumps(rec), flush=True)
                 del gs; keep.clear()
+            if args.cache == "fp8": del views8, pageds8
             del statics, pageds, views, qs
             torch.cuda.empty_cache()

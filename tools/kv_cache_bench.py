@@ -1,6 +1,7 @@
 """What writing k and v into the KV cache costs, three ways, graph-replayed alternately in ONE process (built like qkv_rope_bench.py).
 
     python tools/kv_cache_bench.py [--shapes mha,gqa] [--bits 3,4] [--rows 1,4,16] [--dtypes fp16,bf16] [--layers 32] [--reps 5]
+    python tools/kv_cache_bench.py --fp8 [...]      # a fourth way, d: the fp8 cache entry, against c
 
 Workload: qkv_rope_bench.py's -- the q / k / v projections of --layers decoder layers with distinct weights, each over its own
 activations, K = 4096, head_dim 128, positions drawn per row; shapes mha and gqa; s0 and s45 + top-10 -- and per layer a
@@ -12,6 +13,8 @@ Each way is captured once after an eager warm-up; the three graphs are then repl
 replays each.  One JSON line per point: the median per way and its spread (max - min) in ms per pass over all layers, and in us
 per layer c - a (what the scattered stores cost) and b - c (what the fused write saves; negative: it does not pay), with a
 sanity check that b's and c's caches hold the same bits.
+  d  (--fp8) QuantQKVRopeFused with float8_e4m3fn caches of the same shape, k_scale and v_scale, return_kv=False: the fp8 writer.
+     Reported as d - c in us per layer (negative: the fp8 writer is the faster one) and `fp8_slower`.
 """
 import argparse, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,6 +32,7 @@ ap.add_argument("--dtypes", default="fp16,bf16")
 ap.add_argument("--layers", type=int, default=32)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--slots", type=int, default=256)
+ap.add_argument("--fp8", action="store_true")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 cos32, sin32 = quant.rope_tables(D, N_POS, device=dev)
@@ -88,15 +92,26 @@ for shape in args.shapes.split(","):
                             for m, x, (kc, vc) in zip(fused, xs, caches["c"]):
                                 keep.append(m(x, pos, cos32, sin32, k_cache=kc, v_cache=vc, slots=slots, return_kv=False)[0])
 
+                    caches8 = [tuple(torch.zeros((args.slots, H, D), device=dev, dtype=torch.float8_e4m3fn) for _ in "kv") for _ in trios] if args.fp8 else []
+
+                    def run_d():
+                        keep.clear()
+                        with torch.no_grad():
+                            for m, x, (kc, vc) in zip(fused, xs, caches8):
+                                keep.append(m(x, pos, cos32, sin32, k_cache=kc, v_cache=vc, slots=slots, return_kv=False, k_scale=0.0625, v_scale=0.03125)[0])
+
                     runs = {"a": run_a, "b": run_b, "c": run_c}
+                    if args.fp8:
+                        runs["d"] = run_d
+                        run_d()
                     run_b(); run_c(); torch.cuda.synchronize()
                     same = all(torch.equal(b.view(torch.int16), c.view(torch.int16)) for lb, lc in zip(caches["b"], caches["c"]) for b, c in zip(lb, lc))
                     gs = {k: capture(f) for k, f in runs.items()}
                     for g in gs.values(): timed(g.replay, 5, 3)
                     ms = {k: [] for k in gs}
-                    order = ["a", "b", "c"]
+                    order = list(runs)
                     for r in range(args.reps):
-                        for k in order[r % 3:] + order[:r % 3]: ms[k].append(timed(gs[k].replay))
+                        for k in order[r % len(order):] + order[:r % len(order)]: ms[k].append(timed(gs[k].replay))
                     med = {k: statistics.median(v) for k, v in ms.items()}
                     rec = dict(shape=shape, bits=bits, sparse=tag, rows=rows, dtype=dname, layers=len(trios), reps=args.reps)
                     for k in order:
@@ -105,7 +120,9 @@ for shape in args.shapes.split(","):
                                b_minus_c_us_per_layer=round((med["b"] - med["c"]) * 1e3 / len(trios), 2),
                                b_minus_a_us_per_layer=round((med["b"] - med["a"]) * 1e3 / len(trios), 2),
                                caches_equal=same)
+                    if args.fp8:
+                        rec.update(d_minus_c_us_per_layer=round((med["d"] - med["c"]) * 1e3 / len(trios), 2), fp8_slower=med["d"] > med["c"])
                     print(json.dumps(rec), flush=True)
-                    del gs, xs, caches; keep.clear()
+                    del gs, xs, caches, caches8; keep.clear()
             del trios, fused
             torch.cuda.empty_cache()
