@@ -16,16 +16,8 @@
 #include "sqllm_kernels.h"
 
 namespace sqllm {
-hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated.hip
-hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream) = nullptr;  // set by sqllm_linear_ep.hip
-hipError_t (*g_launch_linear_qkv)(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv.hip
-hipError_t (*g_launch_linear_gated_norm)(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_gated_norm.hip
-hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm.hip
-hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_cache.hip
-hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm_cache.hip
+FrontLauncher g_launch_front[kFrontKinds] = {};  // each slot set by its kernel file (sqllm_linear_gated.hip ... sqllm_linear_qkv_norm_cache_fp8.hip)
 hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
-hipError_t (*g_launch_linear_qkv_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_cache_fp8.hip
-hipError_t (*g_launch_linear_qkv_norm_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream) = nullptr;  // set by sqllm_linear_qkv_norm_cache_fp8.hip
 hipError_t (*g_launch_attn_decode_fp8)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode_fp8.hip
 hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
 }
@@ -1130,19 +1122,11 @@ static void fill_args(sqllm::LaunchArgs* a, const sqllm_op* ops, const sqllm_lin
 // `ws_entry`: the call came through a `_ws` entry point -- up to 16 rows nothing is allocated then, workspace or not.
 // `bf16` (fused linears only): vec and mul are bf16 -- same route, plan and workspace; the flag travels in LaunchArgs and
 // launch_fused hands such a launch to launch_linear_bf16 (sqllm_linear_bf16.hip), so the host layer calls the launchers it always did.
-// `pair` (sqllm_gated_*: two fused linears, gate and up): the plane of pair words; the launch then goes to the gated kernel.
-// `ep` (sqllm_linear_ep_*: one fused linear): activation code and residual; the launch then goes to the epilogue kernel.
-// `qkv` (sqllm_qkv_rope_*: three fused linears, q, k and v): the rotation's operands; the launch then goes to the qkv kernel.
-// `vn` (sqllm_gated_norm_* / sqllm_qkv_rope_norm_*, with `pair` / `qkv`): vec is un-normalised, the launch goes to the norm front's kernel.
-// `kc` (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*, with `qkv`): the KV cache, checked by the caller; the launch goes to the cache-writing kernel.
-struct EpilogueArgs {
-  const void* residual;  // 16-bit [batch, N] of the output's type, or null
-  int act;               // SQLLM_ACT_*, validated by the caller
-};
+// `front` (the gated pair, the epilogue linear, the attention front and their norm / cache variants): what the front's kernel takes
+// beyond the fused linear's arguments (sqllm_kernels.h: FrontCall), checked by the caller; the launch then goes to the kernel of its kind.
 static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t stream, hipEvent_t e0,
                                     hipEvent_t e1, const sqllm_linear* lin = nullptr, void* ws = nullptr, int64_t ws_bytes = 0,
-                                    bool ws_entry = false, bool bf16 = false, void* pair = nullptr, const EpilogueArgs* ep = nullptr,
-                                    const sqllm::QkvRope* qkv = nullptr, const sqllm::VecNorm* vn = nullptr, const sqllm::KvCache* kc = nullptr) {
+                                    bool ws_entry = false, bool bf16 = false, const sqllm::FrontCall* front = nullptr) {
   if (n < 1 || n > sqllm::kMaxSegments) return SQLLM_E_GROUP;
   if (!ops && !lin) return SQLLM_E_NULL;
   sqllm_op tmp[sqllm::kMaxSegments];
@@ -1178,7 +1162,7 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
   GroupPlan plan;
   plan_group(ops, n, route, facts, &plan);
   if (plan.rc != SQLLM_OK) return plan.rc;
-  if (kc && kc->fp8 && !kc->scales_ok) return SQLLM_E_OPTION;  // (the fp8 cache entries: behind everything their 16-bit siblings reject)
+  if (front && front->kc && front->kc->fp8 && !front->kc->scales_ok) return SQLLM_E_OPTION;  // (the fp8 cache entries: behind everything their 16-bit siblings reject)
   if (small.xT && !(g_experimental.skip_prepare_small && g_experimental.skip_prepare_small())) {  // (measurement library only: what the kernel in front costs)
     const hipError_t e = small.planes ? sqllm::prepare_small(ops[0].vec, small.xT, small.planes, ops[0].batch, ops[0].K, s, e0)
                                       : sqllm::transpose_small(ops[0].vec, small.xT, ops[0].batch, ops[0].K, s, e0);
@@ -1196,33 +1180,10 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
     switch (route) {
       case kFusedTiles:
       case kFusedLinear:
-        if (pair) {  // (sqllm_linear_gated.hip; without that file in the link there is no such kernel.  Not decorated: the measurement
-                     // library's ablation bits, LDS pad and timeline buffer belong to the kernels it instantiates itself)
-          if (vn) e = sqllm::g_launch_linear_gated_norm ? sqllm::g_launch_linear_gated_norm(op->bits, a, pair, *vn, s) : hipErrorNotSupported;
-          else
-          e = sqllm::g_launch_linear_gated ? sqllm::g_launch_linear_gated(op->bits, a, pair, s) : hipErrorNotSupported;
-          break;
-        }
-        if (ep) {  // (sqllm_linear_ep.hip; a missing kernel is an error here too, and the launch is not decorated either)
-          e = sqllm::g_launch_linear_ep ? sqllm::g_launch_linear_ep(op->bits, a, ep->residual, ep->act, s) : hipErrorNotSupported;
-          break;
-        }
-        if (qkv) {  // (sqllm_linear_qkv.hip; a missing kernel is an error here too, and the launch is not decorated either)
-          if (kc && kc->fp8) {  // (sqllm_linear_qkv_cache_fp8.hip / sqllm_linear_qkv_norm_cache_fp8.hip)
-            if (vn) e = sqllm::g_launch_linear_qkv_norm_cache_fp8 ? sqllm::g_launch_linear_qkv_norm_cache_fp8(op->bits, a, *qkv, *kc, *vn, s) : hipErrorNotSupported;
-            else
-            e = sqllm::g_launch_linear_qkv_cache_fp8 ? sqllm::g_launch_linear_qkv_cache_fp8(op->bits, a, *qkv, *kc, s) : hipErrorNotSupported;
-            break;
-          }
-          if (kc) {  // (sqllm_linear_qkv_cache.hip / sqllm_linear_qkv_norm_cache.hip)
-            if (vn) e = sqllm::g_launch_linear_qkv_norm_cache ? sqllm::g_launch_linear_qkv_norm_cache(op->bits, a, *qkv, *kc, *vn, s) : hipErrorNotSupported;
-            else
-            e = sqllm::g_launch_linear_qkv_cache ? sqllm::g_launch_linear_qkv_cache(op->bits, a, *qkv, *kc, s) : hipErrorNotSupported;
-            break;
-          }
-          if (vn) e = sqllm::g_launch_linear_qkv_norm ? sqllm::g_launch_linear_qkv_norm(op->bits, a, *qkv, *vn, s) : hipErrorNotSupported;
-          else
-          e = sqllm::g_launch_linear_qkv ? sqllm::g_launch_linear_qkv(op->bits, a, *qkv, s) : hipErrorNotSupported;
+        if (front) {  // (the kernel file of the front's kind; without it in the link there is no such kernel, and that is an error.  Not
+                      // decorated: the measurement library's ablation bits, LDS pad and timeline buffer belong to the kernels it instantiates itself)
+          const sqllm::FrontLauncher launch = sqllm::g_launch_front[sqllm::front_kind(*front)];
+          e = launch ? launch(op->bits, a, *front, s) : hipErrorNotSupported;
           break;
         }
         if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: ablation bits, LDS pad, timeline buffer)
@@ -1346,11 +1307,12 @@ static int launch_gated(const sqllm_gated* g, sqllm_stream_t stream, bool bf16, 
       if (norm_weight_overlaps(nm, a.K, g->out, 2 * rows * a.N) || norm_weight_overlaps(nm, a.K, g->workspace, sqllm_gated_workspace_bytes(&a)))
         return SQLLM_E_SHAPE;
     }
-    const sqllm::VecNorm vn = {nm->weight, nm->eps};
-    return launch_group_with_events(nullptr, 2, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, static_cast<char*>(g->workspace) + 2 * plane,
-                                    nullptr, nullptr, &vn);
   }
-  return launch_group_with_events(nullptr, 2, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, static_cast<char*>(g->workspace) + 2 * plane);
+  const sqllm::VecNorm vn = {nm ? nm->weight : nullptr, nm ? nm->eps : 0.f};
+  sqllm::FrontCall front;
+  front.pair = static_cast<char*>(g->workspace) + 2 * plane;
+  front.vn = nm ? &vn : nullptr;
+  return launch_group_with_events(nullptr, 2, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, &front);
 }
 
 int sqllm_gated_f16(const sqllm_gated* g, sqllm_stream_t stream) { return launch_gated(g, stream, false); }
@@ -1377,8 +1339,10 @@ static int launch_linear_ep(const sqllm_linear_ep* e, sqllm_stream_t stream, boo
     const uintptr_t bytes = 2u * (uintptr_t)(op.batch <= 0 ? 1 : op.batch) * (uintptr_t)op.N;
     if (r < o + bytes && o < r + bytes) return SQLLM_E_SHAPE;
   }
-  const EpilogueArgs ep = {e->residual, e->act};
-  return launch_group_with_events(nullptr, 1, stream, nullptr, nullptr, &e->lin, nullptr, 0, false, bf16, nullptr, &ep);
+  sqllm::FrontCall front;
+  front.residual = e->residual;
+  front.act = e->act;
+  return launch_group_with_events(nullptr, 1, stream, nullptr, nullptr, &e->lin, nullptr, 0, false, bf16, &front);
 }
 
 int sqllm_linear_ep_f16(const sqllm_linear_ep* e, sqllm_stream_t stream) { return launch_linear_ep(e, stream, false); }
@@ -1520,12 +1484,12 @@ static int launch_qkv_rope(const sqllm_qkv_rope* r, sqllm_stream_t stream, bool 
   qr.n_pos = r->n_pos;
   qr.head_dim = D;
   qr.interleaved = r->layout == SQLLM_ROPE_INTERLEAVED;
-  const sqllm::KvCache* kcp = cache_entry ? &kc : nullptr;
-  if (nm) {
-    const sqllm::VecNorm vn = {nm->weight, nm->eps};
-    return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr, &vn, kcp);
-  }
-  return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, nullptr, nullptr, &qr, nullptr, kcp);
+  const sqllm::VecNorm vn = {nm ? nm->weight : nullptr, nm ? nm->eps : 0.f};
+  sqllm::FrontCall front;
+  front.qkv = &qr;
+  front.vn = nm ? &vn : nullptr;
+  front.kc = cache_entry ? &kc : nullptr;
+  return launch_group_with_events(nullptr, 3, stream, nullptr, nullptr, lin, nullptr, 0, false, bf16, &front);
 }
 
 int sqllm_qkv_rope_f16(const sqllm_qkv_rope* r, sqllm_stream_t stream) { return launch_qkv_rope(r, stream, false); }

@@ -559,4 +559,44 @@ inline hipError_t launch_inst(const LaunchArgs& a, hipStream_t stream) {
   return launch_kernel(kern, grid, dim3(WAVES * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The launch ladder of the front kernels (sqllm_linear_*.hip), written once: bits 3 / 4 x batch tile 1 / 2 / 4 / 8 x
+// {_Float16, __bf16} (a.bf16) -> one instantiation of the kernel template that TAG names, on the fused linear's grid.
+// A kernel file says
+//   struct MyFront : FrontTag {
+//     template <int BITS, int BT, typename OT> static auto kernel() { return my_kernel<BITS, BT, OT>; }
+//   };
+// and calls launch_front<MyFront>(bits, a, stream, tail...), `tail` being the kernel's arguments behind (x, ga).  A tag whose
+// kernel takes one of them as another type (a pointer to OT, a cast) says `using FrontTag::arg;` and adds the one converting
+// overload, arg<OT>(const ThatType&): the more specialised template wins, every other argument passes through.
+// ------------------------------------------------------------------------------------------------
+struct FrontTag {
+  template <typename OT, typename T>
+  static const T& arg(const T& v) { return v; }
+};
+
+template <typename TAG, int BITS, int BT, typename OT, typename... TAIL>
+inline hipError_t launch_front_inst(const LaunchArgs& a, hipStream_t stream, const TAIL&... tail) {
+  const int batch = a.ga.seg[0].gm.batch;
+  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
+  auto kern = TAG::template kernel<BITS, BT, OT>();
+  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, TAG::template arg<OT>(tail)...);
+}
+
+template <typename TAG, int BITS, typename OT, typename... TAIL>
+inline hipError_t launch_front_bits(const LaunchArgs& a, hipStream_t stream, const TAIL&... tail) {
+  switch (batch_tile(a.ga.seg[0].gm.batch)) {
+    case 1: return launch_front_inst<TAG, BITS, 1, OT>(a, stream, tail...);
+    case 2: return launch_front_inst<TAG, BITS, 2, OT>(a, stream, tail...);
+    case 4: return launch_front_inst<TAG, BITS, 4, OT>(a, stream, tail...);
+    default: return launch_front_inst<TAG, BITS, 8, OT>(a, stream, tail...);
+  }
+}
+
+template <typename TAG, typename... TAIL>
+inline hipError_t launch_front(int bits, const LaunchArgs& a, hipStream_t stream, const TAIL&... tail) {
+  if (a.bf16) return bits == 4 ? launch_front_bits<TAG, 4, __bf16>(a, stream, tail...) : launch_front_bits<TAG, 3, __bf16>(a, stream, tail...);
+  return bits == 4 ? launch_front_bits<TAG, 4, _Float16>(a, stream, tail...) : launch_front_bits<TAG, 3, _Float16>(a, stream, tail...);
+}
+
 }  // namespace sqllm

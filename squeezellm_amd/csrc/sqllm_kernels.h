@@ -140,15 +140,15 @@ inline int mfma_row_blocks(int batch) { return batch <= 16 ? 1 : batch <= 32 ? 2
 hipError_t launch_fused(int bits, const LaunchArgs& a, hipStream_t stream);
 hipError_t launch_linear_bf16(int bits, const LaunchArgs& a, hipStream_t stream);  // the fused linear, bf16 in / bf16 out (a.linear && a.bf16): launch_fused hands such launches on
 extern bool (*g_fused_variant)(int bits, const LaunchArgs& a, hipStream_t stream, hipError_t* err);  // measurement library hook (null in the product)
-// the gated pair (sqllm_gated_f16 / _bf16): a fused-linear launch of exactly two segments, gate and up, on the kernel of
-// sqllm_linear_gated.hip; `pair`: the plane of pair words [batch, N].  A hook that file sets when it is linked in (defined
-// null in sqllm_capi.hip: the host layer links without the kernels, and a missing kernel is an error, not a fallback).
-extern hipError_t (*g_launch_linear_gated)(int bits, const LaunchArgs& a, void* pair, hipStream_t stream);
-// the fused linear with an epilogue (sqllm_linear_ep_f16 / _bf16): a fused-linear launch of exactly one segment on the kernel of
-// sqllm_linear_ep.hip; `residual`: 16-bit [batch, N] of the output's type or null, `act`: SQLLM_ACT_*.  A hook, as above.
-extern hipError_t (*g_launch_linear_ep)(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream);
-// the attention front (sqllm_qkv_rope_f16 / _bf16): a fused-linear launch of exactly three segments, q, k and v, on the kernel of
-// sqllm_linear_qkv.hip, which rotates q and k by the rotary position embedding as their columns finish.  A hook, as above.
+// The fronts: fused-linear launches whose columns are finished by a kernel of their own.  Each kind is one kernel file, which
+// registers its launcher in g_launch_front when it is linked in (the table is defined all null in sqllm_capi.hip: the host layer
+// links without the kernels, and a missing kernel is an error -- hipErrorNotSupported --, never a fallback).
+//   gated (sqllm_gated_f16 / _bf16): exactly two segments, gate and up, on the kernel of sqllm_linear_gated.hip; FrontCall::pair is
+//     the plane of pair words [batch, N].
+//   ep (sqllm_linear_ep_f16 / _bf16): exactly one segment on the kernel of sqllm_linear_ep.hip; `residual`: 16-bit [batch, N] of the
+//     output's type or null, `act`: SQLLM_ACT_*.
+//   qkv (sqllm_qkv_rope_f16 / _bf16): exactly three segments, q, k and v, on the kernel of sqllm_linear_qkv.hip, which rotates q
+//     and k by the rotary position embedding as their columns finish.
 struct QkvRope {
   void* pair_q;          // plane of pair words [batch, N_q / 2], all zero between launches
   void* pair_k;          // ... [batch, N_k / 2]
@@ -158,19 +158,16 @@ struct QkvRope {
   int n_pos, head_dim;
   bool interleaved;      // SQLLM_ROPE_INTERLEAVED (partner next door) instead of SQLLM_ROPE_HALF (partner head_dim / 2 away)
 };
-extern hipError_t (*g_launch_linear_qkv)(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream);
-// the norm fronts (sqllm_gated_norm_* / sqllm_qkv_rope_norm_*): the two launches above with RMSNorm as a prologue, on the kernels of
-// sqllm_linear_gated_norm.hip / sqllm_linear_qkv_norm.hip -- every element of vec is read as float(x) * float(weight[k]) * r[row].
-// Hooks, as above.
+//   gated_norm, qkv_norm (sqllm_gated_norm_* / sqllm_qkv_rope_norm_*): the two launches above with RMSNorm as a prologue, on the
+//     kernels of sqllm_linear_gated_norm.hip / sqllm_linear_qkv_norm.hip -- every element of vec is read as
+//     float(x) * float(weight[k]) * r[row].
 struct VecNorm {
   const void* weight;  // 16-bit [K] of vec's type, device memory
   float eps;
 };
-extern hipError_t (*g_launch_linear_gated_norm)(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream);
-extern hipError_t (*g_launch_linear_qkv_norm)(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream);
-// the attention front writing k and v into a KV cache (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*): the two q/k/v launches
-// above on the kernels of sqllm_linear_qkv_cache.hip / sqllm_linear_qkv_norm_cache.hip, whose finishers store the elements of
-// k and v at cache + slots[b] * slot_stride + head * head_stride + d as well as, or instead of, in the outputs.  Hooks, as above.
+//   qkv_cache, qkv_norm_cache (sqllm_qkv_rope_cache_* / sqllm_qkv_rope_norm_cache_*): the two q/k/v launches above on the kernels of
+//     sqllm_linear_qkv_cache.hip / sqllm_linear_qkv_norm_cache.hip, whose finishers store the elements of k and v at
+//     cache + slots[b] * slot_stride + head * head_stride + d as well as, or instead of, in the outputs.
 struct KvCache {
   void* k_cache;         // 16-bit elements of the outputs' type, device memory
   void* v_cache;
@@ -178,16 +175,36 @@ struct KvCache {
   int n_slots;
   int64_t slot_stride, head_stride;  // in elements
   bool write_out_k, write_out_v;     // false: the caller gave no such output, and the segment's out16 is a stand-in to be ignored
-  // the fp8 entries (sqllm_qkv_rope_cache_fp8_* / sqllm_qkv_rope_norm_cache_fp8_*): the caches hold 1-byte e4m3fn elements, the
-  // strides count bytes, and the launch goes to the kernels of sqllm_linear_qkv_cache_fp8.hip / sqllm_linear_qkv_norm_cache_fp8.hip
+  //   qkv_cache_fp8, qkv_norm_cache_fp8 (sqllm_qkv_rope_cache_fp8_* / sqllm_qkv_rope_norm_cache_fp8_*): the caches hold 1-byte e4m3fn
+  //     elements, the strides count bytes, and the launch goes to the kernels of sqllm_linear_qkv_cache_fp8.hip /
+  //     sqllm_linear_qkv_norm_cache_fp8.hip
   bool fp8;
   bool scales_ok;                    // both scales finite and positive with finite reciprocals (rejected behind the linear's validation)
   float inv_k_scale, inv_v_scale;    // 1 / k_scale, 1 / v_scale, fp32
 };
-extern hipError_t (*g_launch_linear_qkv_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream);
-extern hipError_t (*g_launch_linear_qkv_norm_cache)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream);
-extern hipError_t (*g_launch_linear_qkv_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, hipStream_t stream);
-extern hipError_t (*g_launch_linear_qkv_norm_cache_fp8)(int bits, const LaunchArgs& a, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream);
+enum FrontKind {
+  kFrontGated, kFrontGatedNorm, kFrontEp, kFrontQkv, kFrontQkvNorm, kFrontQkvCache, kFrontQkvNormCache, kFrontQkvCacheFp8,
+  kFrontQkvNormCacheFp8, kFrontKinds
+};
+// what a front's launch takes beyond the fused linear's LaunchArgs; a kind reads its own fields and rejects a call without them
+struct FrontCall {
+  void* pair = nullptr;            // the gated kinds
+  const void* residual = nullptr;  // ep
+  int act = 0;                     // ep
+  const QkvRope* qkv = nullptr;    // the qkv kinds
+  const VecNorm* vn = nullptr;     // the norm kinds
+  const KvCache* kc = nullptr;     // the cache kinds
+};
+// the kind a call names: the pair plane makes it gated, the rotation qkv, neither ep; the norm and the cache choose the variant
+inline FrontKind front_kind(const FrontCall& f) {
+  if (f.pair) return f.vn ? kFrontGatedNorm : kFrontGated;
+  if (!f.qkv) return kFrontEp;
+  if (f.kc && f.kc->fp8) return f.vn ? kFrontQkvNormCacheFp8 : kFrontQkvCacheFp8;
+  if (f.kc) return f.vn ? kFrontQkvNormCache : kFrontQkvCache;
+  return f.vn ? kFrontQkvNorm : kFrontQkv;
+}
+typedef hipError_t (*FrontLauncher)(int bits, const LaunchArgs& a, const FrontCall& f, hipStream_t stream);
+extern FrontLauncher g_launch_front[kFrontKinds];
 // decode attention over that cache (sqllm_attn_decode_f16 / _bf16), on the kernels of sqllm_attn_decode.hip: the partials of
 // every (row, kv head, partition of kAttnPartition keys), then -- with more than one partition -- the combine.  A hook, as above.
 constexpr int kAttnPartition = 256;  // keys per partition (SQLLM_ATTN_PARTITION of include/sqllm_hip.h)

@@ -60,27 +60,16 @@ sqllm_linear_bf16_kernel(const void* xv, const GroupArgs ga) {
   }
 }
 
-template <int BITS, int BT>
-static hipError_t launch_linear_bf16_inst(const LaunchArgs& a, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_bf16_kernel<BITS, BT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga);
-}
-
-template <int BITS>
-static hipError_t launch_linear_bf16_bits(const LaunchArgs& a, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_linear_bf16_inst<BITS, 1>(a, stream);
-    case 2: return launch_linear_bf16_inst<BITS, 2>(a, stream);
-    case 4: return launch_linear_bf16_inst<BITS, 4>(a, stream);
-    default: return launch_linear_bf16_inst<BITS, 8>(a, stream);
-  }
-}
+// (the kernel has no fp16 form: OT is __bf16 whatever the ladder names, and launch_fused hands over launches with a.bf16 only)
+struct LinearBf16Front : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_bf16_kernel<BITS, BT>; }
+};
 
 // 1..kMaxSegments fused linears over one bf16 vec (a.ga): the batch tiles of launch_fused's linear form
 hipError_t launch_linear_bf16(int bits, const LaunchArgs& a, hipStream_t stream) {
-  return bits == 4 ? launch_linear_bf16_bits<4>(a, stream) : launch_linear_bf16_bits<3>(a, stream);
+  if (!a.bf16) return hipErrorInvalidValue;
+  return launch_front<LinearBf16Front>(bits, a, stream);
 }
 
 }  // namespace sqllm

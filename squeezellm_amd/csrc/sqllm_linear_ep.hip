@@ -94,32 +94,20 @@ sqllm_linear_ep_kernel(const void* xv, const GroupArgs ga, const OT* residual, i
   }
 }
 
-template <int BITS, int BT, typename OT>
-static hipError_t launch_ep_inst(const LaunchArgs& a, const void* residual, int act, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_ep_kernel<BITS, BT, OT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, static_cast<const OT*>(residual), act);
-}
-
-template <int BITS, typename OT>
-static hipError_t launch_ep_bits(const LaunchArgs& a, const void* residual, int act, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_ep_inst<BITS, 1, OT>(a, residual, act, stream);
-    case 2: return launch_ep_inst<BITS, 2, OT>(a, residual, act, stream);
-    case 4: return launch_ep_inst<BITS, 4, OT>(a, residual, act, stream);
-    default: return launch_ep_inst<BITS, 8, OT>(a, residual, act, stream);
-  }
-}
+struct EpFront : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_ep_kernel<BITS, BT, OT>; }
+  using FrontTag::arg;
+  template <typename OT> static const OT* arg(const void* const& residual) { return static_cast<const OT*>(residual); }
+};
 
 // one fused linear over a 16-bit vec (a.ga; a.bf16: its type), finished by act and the optional residual
-static hipError_t launch_linear_ep(int bits, const LaunchArgs& a, const void* residual, int act, hipStream_t stream) {
-  if (a.ga.n_seg != 1 || act < kActSilu || act > kActGeluTanh) return hipErrorInvalidValue;
-  if (a.bf16) return bits == 4 ? launch_ep_bits<4, __bf16>(a, residual, act, stream) : launch_ep_bits<3, __bf16>(a, residual, act, stream);
-  return bits == 4 ? launch_ep_bits<4, _Float16>(a, residual, act, stream) : launch_ep_bits<3, _Float16>(a, residual, act, stream);
+static hipError_t launch_linear_ep(int bits, const LaunchArgs& a, const FrontCall& f, hipStream_t stream) {
+  if (a.ga.n_seg != 1 || f.act < kActSilu || f.act > kActGeluTanh) return hipErrorInvalidValue;
+  return launch_front<EpFront>(bits, a, stream, f.residual, f.act);
 }
 
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_ep_registered = (g_launch_linear_ep = launch_linear_ep, true);
+// the host layer reaches the launcher through its slot of g_launch_front (sqllm_kernels.h), so that it links without this file too
+static const bool g_ep_registered = (g_launch_front[kFrontEp] = launch_linear_ep, true);
 
 }  // namespace sqllm

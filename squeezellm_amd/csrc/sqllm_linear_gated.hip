@@ -72,32 +72,20 @@ sqllm_linear_gated_kernel(const void* xv, const GroupArgs ga, u64* pair) {
   }
 }
 
-template <int BITS, int BT, typename OT>
-static hipError_t launch_gated_inst(const LaunchArgs& a, void* pair, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_gated_kernel<BITS, BT, OT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, static_cast<u64*>(pair));
+struct GatedFront : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_gated_kernel<BITS, BT, OT>; }
+  using FrontTag::arg;
+  template <typename OT> static u64* arg(void* const& pair) { return static_cast<u64*>(pair); }
+};
+
+// gate (segment 0) and up (segment 1) over one 16-bit vec (a.ga; a.bf16: its type), f.pair: the pair plane
+static hipError_t launch_linear_gated(int bits, const LaunchArgs& a, const FrontCall& f, hipStream_t stream) {
+  if (a.ga.n_seg != 2 || !f.pair) return hipErrorInvalidValue;
+  return launch_front<GatedFront>(bits, a, stream, f.pair);
 }
 
-template <int BITS, typename OT>
-static hipError_t launch_gated_bits(const LaunchArgs& a, void* pair, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_gated_inst<BITS, 1, OT>(a, pair, stream);
-    case 2: return launch_gated_inst<BITS, 2, OT>(a, pair, stream);
-    case 4: return launch_gated_inst<BITS, 4, OT>(a, pair, stream);
-    default: return launch_gated_inst<BITS, 8, OT>(a, pair, stream);
-  }
-}
-
-// gate (segment 0) and up (segment 1) over one 16-bit vec (a.ga; a.bf16: its type), `pair`: the pair plane
-static hipError_t launch_linear_gated(int bits, const LaunchArgs& a, void* pair, hipStream_t stream) {
-  if (a.ga.n_seg != 2 || !pair) return hipErrorInvalidValue;
-  if (a.bf16) return bits == 4 ? launch_gated_bits<4, __bf16>(a, pair, stream) : launch_gated_bits<3, __bf16>(a, pair, stream);
-  return bits == 4 ? launch_gated_bits<4, _Float16>(a, pair, stream) : launch_gated_bits<3, _Float16>(a, pair, stream);
-}
-
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_gated_registered = (g_launch_linear_gated = launch_linear_gated, true);
+// the host layer reaches the launcher through its slot of g_launch_front (sqllm_kernels.h), so that it links without this file too
+static const bool g_gated_registered = (g_launch_front[kFrontGated] = launch_linear_gated, true);
 
 }  // namespace sqllm

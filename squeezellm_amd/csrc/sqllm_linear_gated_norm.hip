@@ -64,33 +64,21 @@ sqllm_linear_gated_norm_kernel(const void* xv, const GroupArgs ga, u64* pair, co
   }
 }
 
-template <int BITS, int BT, typename OT>
-static hipError_t launch_gated_norm_inst(const LaunchArgs& a, void* pair, const NormArgs& na, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_gated_norm_kernel<BITS, BT, OT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, static_cast<u64*>(pair), na);
+struct GatedNormFront : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_gated_norm_kernel<BITS, BT, OT>; }
+  using FrontTag::arg;
+  template <typename OT> static u64* arg(void* const& pair) { return static_cast<u64*>(pair); }
+};
+
+// gate (segment 0) and up (segment 1) over one un-normalised 16-bit vec (a.ga; a.bf16: its type); f.vn: the norm's weight and eps
+static hipError_t launch_linear_gated_norm(int bits, const LaunchArgs& a, const FrontCall& f, hipStream_t stream) {
+  if (a.ga.n_seg != 2 || !f.pair || !f.vn || !f.vn->weight) return hipErrorInvalidValue;
+  const NormArgs na = {f.vn->weight, f.vn->eps};
+  return launch_front<GatedNormFront>(bits, a, stream, f.pair, na);
 }
 
-template <int BITS, typename OT>
-static hipError_t launch_gated_norm_bits(const LaunchArgs& a, void* pair, const NormArgs& na, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_gated_norm_inst<BITS, 1, OT>(a, pair, na, stream);
-    case 2: return launch_gated_norm_inst<BITS, 2, OT>(a, pair, na, stream);
-    case 4: return launch_gated_norm_inst<BITS, 4, OT>(a, pair, na, stream);
-    default: return launch_gated_norm_inst<BITS, 8, OT>(a, pair, na, stream);
-  }
-}
-
-// gate (segment 0) and up (segment 1) over one un-normalised 16-bit vec (a.ga; a.bf16: its type); vn: the norm's weight and eps
-static hipError_t launch_linear_gated_norm(int bits, const LaunchArgs& a, void* pair, const VecNorm& vn, hipStream_t stream) {
-  if (a.ga.n_seg != 2 || !pair || !vn.weight) return hipErrorInvalidValue;
-  const NormArgs na = {vn.weight, vn.eps};
-  if (a.bf16) return bits == 4 ? launch_gated_norm_bits<4, __bf16>(a, pair, na, stream) : launch_gated_norm_bits<3, __bf16>(a, pair, na, stream);
-  return bits == 4 ? launch_gated_norm_bits<4, _Float16>(a, pair, na, stream) : launch_gated_norm_bits<3, _Float16>(a, pair, na, stream);
-}
-
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_gated_norm_registered = (g_launch_linear_gated_norm = launch_linear_gated_norm, true);
+// the host layer reaches the launcher through its slot of g_launch_front (sqllm_kernels.h), so that it links without this file too
+static const bool g_gated_norm_registered = (g_launch_front[kFrontGatedNorm] = launch_linear_gated_norm, true);
 
 }  // namespace sqllm

@@ -92,34 +92,21 @@ sqllm_linear_qkv_kernel(const void* xv, const GroupArgs ga, const RopeArgs ra /*
   }
 }
 
-template <int BITS, int BT, typename OT>
-static hipError_t launch_qkv_inst(const LaunchArgs& a, const RopeArgs& ra, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_qkv_kernel<BITS, BT, OT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, ra);
-}
+struct QkvFront : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_qkv_kernel<BITS, BT, OT>; }
+};
 
-template <int BITS, typename OT>
-static hipError_t launch_qkv_bits(const LaunchArgs& a, const RopeArgs& ra, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_qkv_inst<BITS, 1, OT>(a, ra, stream);
-    case 2: return launch_qkv_inst<BITS, 2, OT>(a, ra, stream);
-    case 4: return launch_qkv_inst<BITS, 4, OT>(a, ra, stream);
-    default: return launch_qkv_inst<BITS, 8, OT>(a, ra, stream);
-  }
-}
-
-// q, k and v (segments 0, 1, 2) over one 16-bit vec (a.ga; a.bf16: its type); r: the host's description of the rotation
-static hipError_t launch_linear_qkv(int bits, const LaunchArgs& a, const QkvRope& r, hipStream_t stream) {
+// q, k and v (segments 0, 1, 2) over one 16-bit vec (a.ga; a.bf16: its type); f.qkv: the host's description of the rotation
+static hipError_t launch_linear_qkv(int bits, const LaunchArgs& a, const FrontCall& f, hipStream_t stream) {
+  if (!f.qkv) return hipErrorInvalidValue;
+  const QkvRope& r = *f.qkv;
   if (a.ga.n_seg != 3 || !r.pair_q || !r.pair_k || !r.cos || !r.sin || !r.positions || r.head_dim < 2 || (r.head_dim & 1))
     return hipErrorInvalidValue;
-  const RopeArgs ra = make_rope_args(a, r);
-  if (a.bf16) return bits == 4 ? launch_qkv_bits<4, __bf16>(a, ra, stream) : launch_qkv_bits<3, __bf16>(a, ra, stream);
-  return bits == 4 ? launch_qkv_bits<4, _Float16>(a, ra, stream) : launch_qkv_bits<3, _Float16>(a, ra, stream);
+  return launch_front<QkvFront>(bits, a, stream, make_rope_args(a, r));
 }
 
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_qkv_registered = (g_launch_linear_qkv = launch_linear_qkv, true);
+// the host layer reaches the launcher through its slot of g_launch_front (sqllm_kernels.h), so that it links without this file too
+static const bool g_qkv_registered = (g_launch_front[kFrontQkv] = launch_linear_qkv, true);
 
 }  // namespace sqllm

@@ -79,37 +79,24 @@ sqllm_linear_qkv_cache_kernel(const void* xv, const GroupArgs ga, const RopeArgs
   }
 }
 
-template <int BITS, int BT, typename OT>
-static hipError_t launch_qkv_cache_inst(const LaunchArgs& a, const RopeArgs& ra, const KvCacheArgs& ca, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_qkv_cache_kernel<BITS, BT, OT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, ra, ca);
-}
+struct QkvCacheFront : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_qkv_cache_kernel<BITS, BT, OT>; }
+};
 
-template <int BITS, typename OT>
-static hipError_t launch_qkv_cache_bits(const LaunchArgs& a, const RopeArgs& ra, const KvCacheArgs& ca, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_qkv_cache_inst<BITS, 1, OT>(a, ra, ca, stream);
-    case 2: return launch_qkv_cache_inst<BITS, 2, OT>(a, ra, ca, stream);
-    case 4: return launch_qkv_cache_inst<BITS, 4, OT>(a, ra, ca, stream);
-    default: return launch_qkv_cache_inst<BITS, 8, OT>(a, ra, ca, stream);
-  }
-}
-
-// q, k and v (segments 0, 1, 2) over one 16-bit vec (a0.ga; a0.bf16: its type); r: the rotation; kc: the cache
-static hipError_t launch_linear_qkv_cache(int bits, const LaunchArgs& a0, const QkvRope& r, const KvCache& kc, hipStream_t stream) {
+// q, k and v (segments 0, 1, 2) over one 16-bit vec (a0.ga; a0.bf16: its type); f.qkv: the rotation; f.kc: the cache
+static hipError_t launch_linear_qkv_cache(int bits, const LaunchArgs& a0, const FrontCall& f, hipStream_t stream) {
+  if (!f.qkv || !f.kc) return hipErrorInvalidValue;
+  const QkvRope& r = *f.qkv;
+  const KvCache& kc = *f.kc;
   if (a0.ga.n_seg != 3 || !r.pair_q || !r.pair_k || !r.cos || !r.sin || !r.positions || r.head_dim < 2 || (r.head_dim & 1) || !kc.k_cache ||
       !kc.v_cache || !kc.slots || kc.n_slots < 1 || a0.ga.seg[1].gm.N != a0.ga.seg[2].gm.N || a0.ga.seg[2].gm.N % r.head_dim)
     return hipErrorInvalidValue;
   const LaunchArgs a = without_left_out(a0, kc);
-  const RopeArgs ra = make_rope_args(a, r);
-  const KvCacheArgs ca = make_kv_cache_args(a, r, kc);
-  if (a.bf16) return bits == 4 ? launch_qkv_cache_bits<4, __bf16>(a, ra, ca, stream) : launch_qkv_cache_bits<3, __bf16>(a, ra, ca, stream);
-  return bits == 4 ? launch_qkv_cache_bits<4, _Float16>(a, ra, ca, stream) : launch_qkv_cache_bits<3, _Float16>(a, ra, ca, stream);
+  return launch_front<QkvCacheFront>(bits, a, stream, make_rope_args(a, r), make_kv_cache_args(a, r, kc));
 }
 
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_qkv_cache_registered = (g_launch_linear_qkv_cache = launch_linear_qkv_cache, true);
+// the host layer reaches the launcher through its slot of g_launch_front (sqllm_kernels.h), so that it links without this file too
+static const bool g_qkv_cache_registered = (g_launch_front[kFrontQkvCache] = launch_linear_qkv_cache, true);
 
 }  // namespace sqllm

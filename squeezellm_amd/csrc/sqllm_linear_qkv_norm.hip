@@ -77,35 +77,23 @@ sqllm_linear_qkv_norm_kernel(const void* xv, const GroupArgs ga, const RopeArgs 
   }
 }
 
-template <int BITS, int BT, typename OT>
-static hipError_t launch_qkv_norm_inst(const LaunchArgs& a, const RopeArgs& ra, const NormArgs& na, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_qkv_norm_kernel<BITS, BT, OT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, ra, na);
-}
+struct QkvNormFront : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_qkv_norm_kernel<BITS, BT, OT>; }
+};
 
-template <int BITS, typename OT>
-static hipError_t launch_qkv_norm_bits(const LaunchArgs& a, const RopeArgs& ra, const NormArgs& na, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_qkv_norm_inst<BITS, 1, OT>(a, ra, na, stream);
-    case 2: return launch_qkv_norm_inst<BITS, 2, OT>(a, ra, na, stream);
-    case 4: return launch_qkv_norm_inst<BITS, 4, OT>(a, ra, na, stream);
-    default: return launch_qkv_norm_inst<BITS, 8, OT>(a, ra, na, stream);
-  }
-}
-
-// q, k and v (segments 0, 1, 2) over one un-normalised 16-bit vec; r: the rotation; vn: the norm's weight and eps
-static hipError_t launch_linear_qkv_norm(int bits, const LaunchArgs& a, const QkvRope& r, const VecNorm& vn, hipStream_t stream) {
+// q, k and v (segments 0, 1, 2) over one un-normalised 16-bit vec; f.qkv: the rotation; f.vn: the norm's weight and eps
+static hipError_t launch_linear_qkv_norm(int bits, const LaunchArgs& a, const FrontCall& f, hipStream_t stream) {
+  if (!f.qkv || !f.vn) return hipErrorInvalidValue;
+  const QkvRope& r = *f.qkv;
+  const VecNorm& vn = *f.vn;
   if (a.ga.n_seg != 3 || !r.pair_q || !r.pair_k || !r.cos || !r.sin || !r.positions || r.head_dim < 2 || (r.head_dim & 1) || !vn.weight)
     return hipErrorInvalidValue;
-  const RopeArgs ra = make_rope_args(a, r);
   const NormArgs na = {vn.weight, vn.eps};
-  if (a.bf16) return bits == 4 ? launch_qkv_norm_bits<4, __bf16>(a, ra, na, stream) : launch_qkv_norm_bits<3, __bf16>(a, ra, na, stream);
-  return bits == 4 ? launch_qkv_norm_bits<4, _Float16>(a, ra, na, stream) : launch_qkv_norm_bits<3, _Float16>(a, ra, na, stream);
+  return launch_front<QkvNormFront>(bits, a, stream, make_rope_args(a, r), na);
 }
 
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_qkv_norm_registered = (g_launch_linear_qkv_norm = launch_linear_qkv_norm, true);
+// the host layer reaches the launcher through its slot of g_launch_front (sqllm_kernels.h), so that it links without this file too
+static const bool g_qkv_norm_registered = (g_launch_front[kFrontQkvNorm] = launch_linear_qkv_norm, true);
 
 }  // namespace sqllm

@@ -76,38 +76,26 @@ sqllm_linear_qkv_norm_cache_kernel(const void* xv, const GroupArgs ga, const Rop
   }
 }
 
-template <int BITS, int BT, typename OT>
-static hipError_t launch_qkv_norm_cache_inst(const LaunchArgs& a, const RopeArgs& ra, const KvCacheArgs& ca, const NormArgs& na, hipStream_t stream) {
-  const int batch = a.ga.seg[0].gm.batch;
-  dim3 grid(a.ga.block0[a.ga.n_seg], (batch + BT - 1) / BT);
-  auto kern = sqllm_linear_qkv_norm_cache_kernel<BITS, BT, OT>;
-  return launch_kernel(kern, grid, dim3(kWaves * 64), a.lds_pad, stream, a.ev_start, a.ev_stop, a.x, a.ga, ra, ca, na);
-}
+struct QkvNormCacheFront : FrontTag {
+  template <int BITS, int BT, typename OT>
+  static auto kernel() { return sqllm_linear_qkv_norm_cache_kernel<BITS, BT, OT>; }
+};
 
-template <int BITS, typename OT>
-static hipError_t launch_qkv_norm_cache_bits(const LaunchArgs& a, const RopeArgs& ra, const KvCacheArgs& ca, const NormArgs& na, hipStream_t stream) {
-  switch (batch_tile(a.ga.seg[0].gm.batch)) {
-    case 1: return launch_qkv_norm_cache_inst<BITS, 1, OT>(a, ra, ca, na, stream);
-    case 2: return launch_qkv_norm_cache_inst<BITS, 2, OT>(a, ra, ca, na, stream);
-    case 4: return launch_qkv_norm_cache_inst<BITS, 4, OT>(a, ra, ca, na, stream);
-    default: return launch_qkv_norm_cache_inst<BITS, 8, OT>(a, ra, ca, na, stream);
-  }
-}
-
-// q, k and v (segments 0, 1, 2) over one un-normalised 16-bit vec; r: the rotation; kc: the cache; vn: the norm's weight and eps
-static hipError_t launch_linear_qkv_norm_cache(int bits, const LaunchArgs& a0, const QkvRope& r, const KvCache& kc, const VecNorm& vn, hipStream_t stream) {
+// q, k and v (segments 0, 1, 2) over one un-normalised 16-bit vec; f.qkv: the rotation; f.kc: the cache; f.vn: the norm's weight and eps
+static hipError_t launch_linear_qkv_norm_cache(int bits, const LaunchArgs& a0, const FrontCall& f, hipStream_t stream) {
+  if (!f.qkv || !f.kc || !f.vn) return hipErrorInvalidValue;
+  const QkvRope& r = *f.qkv;
+  const KvCache& kc = *f.kc;
+  const VecNorm& vn = *f.vn;
   if (a0.ga.n_seg != 3 || !r.pair_q || !r.pair_k || !r.cos || !r.sin || !r.positions || r.head_dim < 2 || (r.head_dim & 1) || !vn.weight ||
       !kc.k_cache || !kc.v_cache || !kc.slots || kc.n_slots < 1 || a0.ga.seg[1].gm.N != a0.ga.seg[2].gm.N || a0.ga.seg[2].gm.N % r.head_dim)
     return hipErrorInvalidValue;
   const LaunchArgs a = without_left_out(a0, kc);
-  const RopeArgs ra = make_rope_args(a, r);
-  const KvCacheArgs ca = make_kv_cache_args(a, r, kc);
   const NormArgs na = {vn.weight, vn.eps};
-  if (a.bf16) return bits == 4 ? launch_qkv_norm_cache_bits<4, __bf16>(a, ra, ca, na, stream) : launch_qkv_norm_cache_bits<3, __bf16>(a, ra, ca, na, stream);
-  return bits == 4 ? launch_qkv_norm_cache_bits<4, _Float16>(a, ra, ca, na, stream) : launch_qkv_norm_cache_bits<3, _Float16>(a, ra, ca, na, stream);
+  return launch_front<QkvNormCacheFront>(bits, a, stream, make_rope_args(a, r), make_kv_cache_args(a, r, kc), na);
 }
 
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_qkv_norm_cache_registered = (g_launch_linear_qkv_norm_cache = launch_linear_qkv_norm_cache, true);
+// the host layer reaches the launcher through its slot of g_launch_front (sqllm_kernels.h), so that it links without this file too
+static const bool g_qkv_norm_cache_registered = (g_launch_front[kFrontQkvNormCache] = launch_linear_qkv_norm_cache, true);
 
 }  // namespace sqllm

@@ -62,7 +62,11 @@ def test_the_sixteen_writers_exist_and_nothing_else_and_the_siblings_are_unchang
     assert sorted(new) == sorted(_name(f[1], f[2], b, t, ot) for b, t in CASES for ot in OTS)
     assert sorted(sib) == sorted(_name(f[4], f[5], b, t, ot) for b, t in CASES for ot in OTS)  # (the pinned source: today's instances)
     src = open(os.path.join(B.CSRC, f[0])).read()
-    assert [int(t) for t in re.findall(r"_fp8_cache_inst<BITS, (\d), OT>", src)] == [1, 2, 4, 8]
+    # (the batch-tile ladder the fronts share, and this source's kernel on it)
+    ladder = open(os.path.join(B.CSRC, "sqllm_fused.h")).read()
+    assert [int(t) for t in re.findall(r"launch_front_inst<TAG, BITS, (\d), OT>", ladder)] == [1, 2, 4, 8]
+    kernel = f[1].lstrip("0123456789")
+    assert f"return {kernel}<BITS, BT, OT>;" in src and re.search(r"launch_front<Qkv(Norm)?CacheFp8Front>\(bits, a, stream, ", src)
     assert "RopeCacheFp8Finish<OT>" in src and '#include "sqllm_cache_fp8_finish.h"' in src
 
 

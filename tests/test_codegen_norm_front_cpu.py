@@ -68,7 +68,10 @@ def test_the_thirty_two_kernels_exist_and_nothing_else(kernels):
     for fam in ("gated_norm", "qkv_norm"):
         assert sorted(kernels[fam]) == sorted(NAMES[fam].format(bits=b, bt=t, ot=ot) for b, t in CASES for ot in OTS)
         src = open(os.path.join(B.CSRC, FILES[fam])).read()
-        assert [int(t) for t in re.findall(r"launch_\w+_norm_inst<BITS, (\d), OT>", src)] == [1, 2, 4, 8]
+        # (the batch-tile ladder the fronts share, and this source's kernel on it)
+        ladder = open(os.path.join(B.CSRC, "sqllm_fused.h")).read()
+        assert [int(t) for t in re.findall(r"launch_front_inst<TAG, BITS, (\d), OT>", ladder)] == [1, 2, 4, 8]
+        assert f"return sqllm_linear_{fam}_kernel<BITS, BT, OT>;" in src and re.search(r"launch_front<\w+NormFront>\(bits, a, stream, ", src)
 
 
 @pytest.mark.parametrize("ot", OTS)

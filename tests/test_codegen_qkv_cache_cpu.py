@@ -49,7 +49,11 @@ def test_the_sixteen_kernels_exist_and_nothing_else(kernels, fam):
     assert sorted(new) == sorted(_name(f[1], f[2], b, t, ot) for b, t in CASES for ot in OTS)
     assert sorted(parent) == sorted(_name(f[4], f[5], b, t, ot) for b, t in CASES for ot in OTS)
     src = open(os.path.join(B.CSRC, f[0])).read()
-    assert [int(t) for t in re.findall(r"_cache_inst<BITS, (\d), OT>", src)] == [1, 2, 4, 8]
+    # (the batch-tile ladder the fronts share, and this source's kernel on it)
+    ladder = open(os.path.join(B.CSRC, "sqllm_fused.h")).read()
+    assert [int(t) for t in re.findall(r"launch_front_inst<TAG, BITS, (\d), OT>", ladder)] == [1, 2, 4, 8]
+    kernel = f[1].lstrip("0123456789")
+    assert f"return {kernel}<BITS, BT, OT>;" in src and re.search(r"launch_front<Qkv(Norm)?CacheFront>\(bits, a, stream, ", src)
 
 
 @pytest.mark.parametrize("ot", OTS)

@@ -59,12 +59,15 @@ def test_the_source_is_part_of_the_product_build():
 
 
 def test_the_sixteen_kernels_exist_and_nothing_else(kernels):
-    """launch_qkv_bits switches over batch_tile() = 1, 2, 4, 8 for both bit widths and both types: exactly those"""
+    """the fronts' launch ladder (sqllm_fused.h: launch_front_bits) switches over batch_tile() = 1, 2, 4, 8 for both bit widths and
+    both types, and the source launches its kernel through it: exactly those"""
     qkv, bf16 = kernels
     assert sorted(qkv) == sorted(_qkv_name(b, t, ot) for b, t in CASES for ot in ("DF16_", "DF16b"))
     assert sorted(bf16) == sorted(_bf16_name(b, t) for b, t in CASES)
+    ladder = open(os.path.join(B.CSRC, "sqllm_fused.h")).read()
+    assert [int(t) for t in re.findall(r"launch_front_inst<TAG, BITS, (\d), OT>", ladder)] == [1, 2, 4, 8]
     src = open(os.path.join(B.CSRC, "sqllm_linear_qkv.hip")).read()
-    assert [int(t) for t in re.findall(r"launch_qkv_inst<BITS, (\d), OT>", src)] == [1, 2, 4, 8]
+    assert "return sqllm_linear_qkv_kernel<BITS, BT, OT>;" in src and "launch_front<QkvFront>(bits, a, stream, " in src
 
 
 @pytest.mark.parametrize("ot", ["DF16_", "DF16b"])

@@ -179,3 +179,34 @@ def test_launch_hooks_on_the_recording_host_layer(tmp_path):
         assert (f["rc"], f["calls"], f["n_seg"]) == ("0", calls, n_seg)
         assert int(f["weight"], 16) == 0x300000 and float(f["eps"]) == pytest.approx(1e-5, rel=1e-6)
         assert int(f["x"], 16) == 0x1000 and f["same_pair"] == "1"  # the parent's launch arguments, the parent's workspace layout
+    # the table of nine kinds.  Nothing registered: every one of the 18 front entries is an error
+    assert len(lines["nohook_all"]) == 18 and all(v == ns for v in lines["nohook_all"].values())
+    # recording launchers in all nine slots: each entry reaches the slot of its own kind and no other, with its descriptors' fields
+    KINDS = ("gated", "gated_norm", "ep", "qkv", "qkv_norm", "qkv_cache", "qkv_norm_cache", "qkv_cache_fp8", "qkv_norm_cache_fp8")
+    entry_of = {"gated": "sqllm_gated", "gated_norm": "sqllm_gated_norm", "ep": "sqllm_linear_ep", "qkv": "sqllm_qkv_rope",
+                "qkv_norm": "sqllm_qkv_rope_norm", "qkv_cache": "sqllm_qkv_rope_cache", "qkv_norm_cache": "sqllm_qkv_rope_norm_cache",
+                "qkv_cache_fp8": "sqllm_qkv_rope_cache_fp8", "qkv_norm_cache_fp8": "sqllm_qkv_rope_norm_cache_fp8"}
+    reached = {k: v for k, v in lines.items() if k.startswith("reach:")}
+    assert sorted(reached) == sorted(f"reach:{entry_of[kind]}_{t}" for kind in KINDS for t in ("f16", "bf16"))
+    assert set(lines["nohook_all"]) == {k[len("reach:"):] for k in reached}
+    for i, kind in enumerate(KINDS):
+        for t in ("f16", "bf16"):
+            f = reached[f"reach:{entry_of[kind]}_{t}"]
+            assert f["rc"] == "0" and int(f["kind"]) == i, (kind, t, f)
+            assert f["calls"] == ",".join("1" if j == i else "0" for j in range(9)), (kind, t, f["calls"])
+            gated, qkv, norm, cache, fp8 = kind.startswith("gated"), kind.startswith("qkv"), "norm" in kind, "cache" in kind, "fp8" in kind
+            assert f["n_seg"] == ("2" if gated else "3" if qkv else "1") and int(f["x"], 16) == 0x1000
+            assert (f["pair"], f["has_qkv"], f["has_vn"], f["has_kc"]) == tuple(str(int(b)) for b in (gated, qkv, norm, cache))
+            # the epilogue's residual and activation code (SQLLM_ACT_GELU = 3), nowhere else
+            assert (int(f["residual"], 16), f["act"]) == ((0x500000, "3") if kind == "ep" else (0, "0"))
+            if norm:  # VecNorm
+                assert int(f["weight"], 16) == 0x300000 and float(f["eps"]) == pytest.approx(1e-5, rel=1e-6)
+            if qkv:  # QkvRope
+                assert (f["pair_q"], f["pair_k"], f["n_pos"], f["head_dim"], f["interleaved"]) == ("1", "1", "16", "64", "0")
+                assert [int(f[k], 16) for k in ("cos", "sin", "positions")] == [0x200000, 0x210000, 0x220000]
+            if cache:  # KvCache
+                assert [int(f[k], 16) for k in ("k_cache", "v_cache", "slots")] == [0x800000, 0x900000, 0x230000]
+                assert (f["n_slots"], f["slot_stride"], f["head_stride"], f["write_out"]) == ("8", "128", "64", "11")
+                assert (f["fp8"], f["scales_ok"]) == (("1", "1") if fp8 else ("0", "0"))
+            if fp8:  # k_scale 0.5, v_scale 4: the reciprocals
+                assert (float(f["inv_k"]), float(f["inv_v"])) == (2.0, 0.25)

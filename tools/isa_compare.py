@@ -21,7 +21,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from squeezellm_amd import build as B  # noqa: E402
 
 PRODUCT = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "sqllm_dequant.hip", "sqllm_linear_bf16.hip", "sqllm_linear_gated.hip",
-           "sqllm_linear_ep.hip", "sqllm_linear_qkv.hip", "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip"]
+           "sqllm_linear_ep.hip", "sqllm_linear_qkv.hip", "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip", "sqllm_linear_qkv_cache.hip",
+           "sqllm_linear_qkv_norm_cache.hip", "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode.hip",
+           "sqllm_attn_decode_fp8.hip"]
 META = (".vgpr_count", ".sgpr_count", ".agpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size",
         ".vgpr_spill_count", ".sgpr_spill_count")
 CLASSES = ("v_mfma", "ds_read", "global_load", "buffer_load", "s_load", "s_barrier", "s_waitcnt")
