@@ -590,7 +590,8 @@ int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream);
  * extents in bytes, and no alignment rule for k_cache / v_cache); then
  *   a k_scale or v_scale that is not finite, not positive, or whose fp32 reciprocal is not finite     SQLLM_E_OPTION
  *   in the attention entries, a scale * k_scale that is not finite                                    SQLLM_E_OPTION
- * Not covered: per-head or per-token scales, e5m2, int8 or 4-bit caches, computing the scales, prefill attention.
+ * Not covered: per-head or per-token scales, e5m2, int8 or 4-bit caches, computing the scales, prefill attention beyond the
+ * up to 16 query rows per sequence of sqllm_attn_append_fp8 (below): prompt-length prefill stays out.
  * ------------------------------------------------------------------------------------------- */
 typedef struct sqllm_kv_cache_fp8 {
   void* k_cache;          /* 1-byte e4m3fn elements, device memory */
@@ -622,6 +623,72 @@ typedef struct sqllm_attn_decode_fp8 {
 /* the suffix names the type of q and out */
 int sqllm_attn_decode_fp8_f16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream);
 int sqllm_attn_decode_fp8_bf16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Decode attention for SEVERAL new tokens per sequence in one read of K and V: the verification step of speculative decoding
+ * (2 to 8 drafted tokens) or a chunk of a prompt (16 tokens per step), behind a front that wrote all of the step's tokens.
+ * sqllm_attn_append is the fields of sqllm_attn_decode, in the same order, followed by q_lens and q_len;
+ * sqllm_attn_append_fp8 is the fields of sqllm_attn_decode_fp8 followed by the same two.
+ *
+ *   - Rows.  batch counts SEQUENCES, q_len = T is a host field.  Row r = b*T + t of q and out is new token t of sequence b;
+ *     strides as before.  block_table is [batch, table_stride]: ONE table row per sequence.  seq_lens[b] is the number of
+ *     keys of sequence b INCLUDING all its new tokens, which the front wrote in the same step.
+ *   - q_lens: int32 [batch] in DEVICE memory, or NULL.  n_b = q_lens ? q_lens[b] : T is the number of real new tokens of
+ *     sequence b; a captured graph follows it updated in place.
+ *   - Token t < n_b attends the keys p < L(b,t) = seq_lens[b] - (n_b - 1 - t): causal, bottom-right aligned.
+ *   - Values, by reduction to the one-query entry.  Row (b, t) with t < n_b holds EXACTLY THE BITS that sqllm_attn_decode_*
+ *     (sqllm_attn_decode_fp8_* for the byte caches) writes for a row with table row b and length L(b,t), all other
+ *     descriptor fields equal: the +0 row (L <= 0); the NaN rows (L > max_blocks * block_size, or a table entry outside
+ *     [0, n_slots) used by a key below L -- a bad entry at key p makes NaN only the tokens with L > p); NaN propagation and
+ *     infinities.  Verifying T tokens at once yields what T decode steps would; isolation, determinism and row independence
+ *     carry over.  A key at or beyond L(b,t) that a later token attends never influences row (b, t), whatever bits it holds.
+ *   - Rows t >= n_b are padding and are +0.  n_b < 0 is treated as 0.  n_b > T makes all T rows of the sequence NaN.
+ *   - As the sibling: unaddressed slots never influence a result; nothing outside the cache extent is read; nothing but the
+ *     batch*T rows of out and the workspace is written; the workspace is sqllm_attn_decode_workspace_bytes(batch*q_len, ...),
+ *     CONTENTS IRRELEVANT; a call allocates nothing and is capturable: TWO kernel nodes, ONE when
+ *     max_blocks * block_size <= SQLLM_ATTN_PARTITION; launch geometry comes from host fields only.
+ *
+ * Served: head_dim 64 or 128; a head ratio of 1 to 8; q_len 1 to 16; batch*q_len <= 64.  Rejections are the sibling's, with
+ * its codes and in its order: q_len < 1 counts among the counts; q_len > 16 or batch*q_len > 64 among the shapes that are not
+ * served; q_lens, when given, among the tensors out and the workspace must not overlap; the fp8 scale checks come last.
+ * Not covered: more than 16 rows per sequence -- prompt-length prefill stays the integrator's.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_attn_append {
+  const void* q;            /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride q_stride elements */
+  void* out;                /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride out_stride; OVERWRITTEN */
+  const void* k_cache;      /* as sqllm_kv_cache */
+  const void* v_cache;
+  const int32_t* block_table; /* int32 [batch, table_stride], DEVICE memory: one row per sequence */
+  const int32_t* seq_lens;    /* int32 [batch], DEVICE memory: the keys of sequence b, its new tokens included */
+  int32_t batch, n_q_heads, n_kv_heads, head_dim;   /* batch: sequences */
+  int32_t n_slots, block_size, max_blocks, table_stride;   /* max_blocks <= table_stride */
+  int64_t slot_stride, head_stride, q_stride, out_stride;
+  float scale;              /* the caller's, usually 1/sqrt(head_dim); finite */
+  void* workspace;          /* sqllm_attn_decode_workspace_bytes(batch * q_len, ...); contents irrelevant */
+  const int32_t* q_lens;    /* int32 [batch], DEVICE memory, or NULL: q_len real tokens in every sequence */
+  int32_t q_len;            /* rows per sequence, 1 to 16 */
+} sqllm_attn_append;
+int sqllm_attn_append_f16(const sqllm_attn_append* a, sqllm_stream_t stream);
+int sqllm_attn_append_bf16(const sqllm_attn_append* a, sqllm_stream_t stream);
+typedef struct sqllm_attn_append_fp8 {
+  const void* q;            /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride q_stride elements */
+  void* out;                /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride out_stride; OVERWRITTEN */
+  const void* k_cache;      /* as sqllm_kv_cache_fp8 */
+  const void* v_cache;
+  const int32_t* block_table; /* int32 [batch, table_stride], DEVICE memory: one row per sequence */
+  const int32_t* seq_lens;    /* int32 [batch], DEVICE memory: the keys of sequence b, its new tokens included */
+  int32_t batch, n_q_heads, n_kv_heads, head_dim;   /* batch: sequences */
+  int32_t n_slots, block_size, max_blocks, table_stride;   /* max_blocks <= table_stride */
+  int64_t slot_stride, head_stride, q_stride, out_stride;  /* the first two in bytes, the last two in 16-bit elements */
+  float scale;              /* the caller's, usually 1/sqrt(head_dim); finite */
+  void* workspace;          /* sqllm_attn_decode_workspace_bytes(batch * q_len, ...); contents irrelevant */
+  float k_scale, v_scale;   /* the cache's, as the front was given them */
+  const int32_t* q_lens;    /* int32 [batch], DEVICE memory, or NULL */
+  int32_t q_len;            /* rows per sequence, 1 to 16 */
+} sqllm_attn_append_fp8;
+/* the suffix names the type of q and out */
+int sqllm_attn_append_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream);
+int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The reference operator names.

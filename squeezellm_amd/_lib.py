@@ -107,6 +107,19 @@ class SqllmAttnDecodeFp8(ctypes.Structure):
     _fields_ = SqllmAttnDecode._fields_ + [("k_scale", ctypes.c_float), ("v_scale", ctypes.c_float)]
 
 
+class SqllmAttnAppend(ctypes.Structure):
+    """struct sqllm_attn_append (include/sqllm_hip.h): sqllm_attn_decode for q_len new tokens per sequence -- batch counts
+    sequences, q and out have batch * q_len rows, q_lens (or NULL) the real tokens of each sequence."""
+
+    _fields_ = SqllmAttnDecode._fields_ + [("q_lens", c_void_p), ("q_len", c_int32)]
+
+
+class SqllmAttnAppendFp8(ctypes.Structure):
+    """struct sqllm_attn_append_fp8 (include/sqllm_hip.h): sqllm_attn_decode_fp8 followed by the same two fields."""
+
+    _fields_ = SqllmAttnDecodeFp8._fields_ + [("q_lens", c_void_p), ("q_len", c_int32)]
+
+
 class SqllmQkvRope(ctypes.Structure):
     """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
 
@@ -216,6 +229,10 @@ SIGNATURES = {
     "sqllm_qkv_rope_norm_cache_fp8_bf16": [POINTER(SqllmQkvRope), POINTER(SqllmRmsNorm), POINTER(SqllmKvCacheFp8), P],
     "sqllm_attn_decode_fp8_f16": [POINTER(SqllmAttnDecodeFp8), P],
     "sqllm_attn_decode_fp8_bf16": [POINTER(SqllmAttnDecodeFp8), P],
+    "sqllm_attn_append_f16": [POINTER(SqllmAttnAppend), P],
+    "sqllm_attn_append_bf16": [POINTER(SqllmAttnAppend), P],
+    "sqllm_attn_append_fp8_f16": [POINTER(SqllmAttnAppendFp8), P],
+    "sqllm_attn_append_fp8_bf16": [POINTER(SqllmAttnAppendFp8), P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],

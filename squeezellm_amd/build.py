@@ -22,7 +22,8 @@ LIB_NAME = "libsqllm_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "sqllm_nuq.hip", "sqllm_dequant.hip", "sqllm_encode.hip", "sqllm_select.hip", "sqllm_linear_bf16.hip", "sqllm_linear_gated.hip", "sqllm_linear_ep.hip", "sqllm_linear_qkv.hip",
            "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip", "sqllm_linear_qkv_cache.hip", "sqllm_linear_qkv_norm_cache.hip", "sqllm_attn_decode.hip",
-           "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode_fp8.hip", "sqllm_capi.hip"]
+           "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode_fp8.hip",
+           "sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip", "sqllm_capi.hip"]
 # measured-and-not-adopted kernels (round 3: the streaming batch-1 kernel, the column-pair-table kernel; round 4: the
 # dependency-gated persistent pass) and the host code that routes to them: csrc/experimental/, part of the MEASUREMENT
 # library only (options "stream" / "pair4", entry points sqllm_pass_*)
@@ -30,7 +31,7 @@ EXPERIMENTAL = os.path.join(CSRC, "experimental")
 EXPERIMENT_SOURCES = ["experimental/sqllm_ablation.hip", "experimental/sqllm_stream.hip", "experimental/sqllm_pair.hip",
                       "experimental/sqllm_pass.hip", "experimental/sqllm_experimental.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("sqllm_kernels.h", "sqllm_decode.h", "sqllm_roles.h", "sqllm_fused.h", "sqllm_ranges.h", "sqllm_split_common.h", "sqllm_host.h", "sqllm_probe.h",
-                                              "sqllm_pair_finish.h", "sqllm_rope_finish.h", "sqllm_norm_front.h", "sqllm_cache_finish.h", "sqllm_cache_fp8_finish.h")] + [os.path.join(INCLUDE, "sqllm_hip.h")]
+                                              "sqllm_pair_finish.h", "sqllm_rope_finish.h", "sqllm_norm_front.h", "sqllm_cache_finish.h", "sqllm_cache_fp8_finish.h", "sqllm_attn_append.h")] + [os.path.join(INCLUDE, "sqllm_hip.h")]
 EXPERIMENT_HEADERS = [os.path.join(EXPERIMENTAL, h) for h in ("sqllm_pass.h", "sqllm_pass_api.h", "sqllm_stream_api.h")]
 ARCH = "gfx950"
 # -amdgpu-kernarg-preload-count: the kernels' leading explicit arguments (the vec pointer) arrive in SGPRs instead of

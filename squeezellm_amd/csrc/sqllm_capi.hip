@@ -18,6 +18,9 @@
 namespace sqllm {
 FrontLauncher g_launch_front[kFrontKinds] = {};  // each slot set by its kernel file (sqllm_linear_gated.hip ... sqllm_linear_qkv_norm_cache_fp8.hip)
 hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
+hipError_t (*g_launch_attn_append)(const AttnAppend& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
+hipError_t (*g_launch_attn_append_fp8)(const AttnAppend& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_append_fp8.hip
+hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
 hipError_t (*g_launch_attn_decode_fp8)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode_fp8.hip
 hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
 }
@@ -1552,33 +1555,39 @@ int64_t sqllm_attn_decode_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
 }
 
 // `a8` (sqllm_attn_decode_fp8_*): the descriptor the fields of `a` were taken from -- the caches hold 1-byte e4m3fn elements,
-// their strides and extents count bytes and they need no alignment; its scales are judged last
-static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream, bool bf16, const sqllm_attn_decode_fp8* a8 = nullptr) {
+// their strides and extents count bytes and they need no alignment; its scales are judged last.
+// `q_len` >= 0 (sqllm_attn_append_*): a->batch counts sequences of q_len rows each, `q_lens` (or NULL) their real tokens; -1: the
+// one-query entries.
+static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream, bool bf16, const sqllm_attn_decode_fp8* a8 = nullptr,
+                              const int32_t* q_lens = nullptr, int32_t q_len = -1) {
+  const bool append = q_len != -1;
   const int celem = a8 ? 1 : 2;  // bytes per cache element
   if (!a || !a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || !a->workspace) return SQLLM_E_NULL;
   const int64_t D = a->head_dim;
   if (a->batch < 1 || a->n_q_heads < 1 || a->n_kv_heads < 1 || D < 1 || a->n_slots < 1 || a->block_size < 1 || a->max_blocks < 1 ||
-      a->table_stride < 1)
+      a->table_stride < 1 || (append && q_len < 1))
     return SQLLM_E_SHAPE;
+  const int64_t rows = append ? (int64_t)a->batch * q_len : a->batch;  // of q, out and the workspace
   const int64_t width = (int64_t)a->n_q_heads * D;
   if (a->slot_stride < D || a->head_stride < D || a->q_stride < width || a->out_stride < width) return SQLLM_E_SHAPE;
   if (a->max_blocks > a->table_stride) return SQLLM_E_SHAPE;
   // what the kernel serves
-  if ((D != 64 && D != 128) || a->n_q_heads % a->n_kv_heads || a->n_q_heads / a->n_kv_heads > 8 || a->batch > 64 || a->n_q_heads > 65535)
+  if ((D != 64 && D != 128) || a->n_q_heads % a->n_kv_heads || a->n_q_heads / a->n_kv_heads > 8 || rows > 64 || a->n_q_heads > 65535 ||
+      (append && q_len > 16))
     return SQLLM_E_SHAPE;
   // as for sqllm_kv_cache: 32 x 32 -> 64-bit products, and extents that do not wrap
   const int64_t H = a->n_kv_heads;
   if ((a->n_slots > 1 && a->slot_stride >= (1ll << 32)) || (H > 1 && a->head_stride >= (1ll << 32))) return SQLLM_E_SHAPE;
   const unsigned __int128 extent = (unsigned __int128)(a->n_slots - 1) * (uint64_t)a->slot_stride + (unsigned __int128)(H - 1) * (uint64_t)a->head_stride + (uint64_t)D;
-  const unsigned __int128 q_extent = (unsigned __int128)(a->batch - 1) * (uint64_t)a->q_stride + (uint64_t)width;
-  const unsigned __int128 out_extent = (unsigned __int128)(a->batch - 1) * (uint64_t)a->out_stride + (uint64_t)width;
+  const unsigned __int128 q_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->q_stride + (uint64_t)width;
+  const unsigned __int128 out_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->out_stride + (uint64_t)width;
   if (extent >= ((unsigned __int128)1 << 62) || q_extent >= ((unsigned __int128)1 << 62) || out_extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
   if (!__builtin_isfinite(a->scale)) return SQLLM_E_OPTION;
-  const int64_t ws_bytes = sqllm_attn_decode_workspace_bytes(a->batch, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
-  const void* const in[5] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens};
-  const int64_t in_bytes[5] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
-                               4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch};
-  for (int i = 0; i < 5; ++i)
+  const int64_t ws_bytes = sqllm_attn_decode_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
+  const void* const in[6] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens, q_lens};
+  const int64_t in_bytes[6] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
+                               4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch, 4 * (int64_t)a->batch};
+  for (int i = 0; i < (q_lens ? 6 : 5); ++i)
     if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i]))
       return SQLLM_E_SHAPE;
   if (ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
@@ -1616,6 +1625,14 @@ static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream,
   d.scale = scale;
   d.bf16 = bf16;
   d.v_scale = a8 ? a8->v_scale : 1.0f;
+  if (append) {
+    sqllm::AttnAppend p;
+    p.d = d;
+    p.q_lens = q_lens;
+    p.q_len = q_len;
+    const auto launch_append = a8 ? sqllm::g_launch_attn_append_fp8 : sqllm::g_launch_attn_append;
+    return static_cast<int>(launch_append ? launch_append(p, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
+  }
   const auto launch = a8 ? sqllm::g_launch_attn_decode_fp8 : sqllm::g_launch_attn_decode;
   const hipError_t e = launch ? launch(d, static_cast<hipStream_t>(stream)) : hipErrorNotSupported;
   return static_cast<int>(e);
@@ -1652,6 +1669,51 @@ int sqllm_attn_decode_fp8_bf16(const sqllm_attn_decode_fp8* a, sqllm_stream_t st
 
 int sqllm_attn_decode_f16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, false); }
 int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, true); }
+
+// Several new tokens per sequence (sqllm_attn_append_*): the one-query descriptor out of the leading fields, then the checks
+// and the launch above with the two fields behind them.  A negative q_len is a count < 1, not the one-query call.
+extern "C++" template <typename A>
+static void attn_append_fields(const A* p, sqllm_attn_decode* a) {
+  a->q = p->q;
+  a->out = p->out;
+  a->k_cache = p->k_cache;
+  a->v_cache = p->v_cache;
+  a->block_table = p->block_table;
+  a->seq_lens = p->seq_lens;
+  a->batch = p->batch;
+  a->n_q_heads = p->n_q_heads;
+  a->n_kv_heads = p->n_kv_heads;
+  a->head_dim = p->head_dim;
+  a->n_slots = p->n_slots;
+  a->block_size = p->block_size;
+  a->max_blocks = p->max_blocks;
+  a->table_stride = p->table_stride;
+  a->slot_stride = p->slot_stride;
+  a->head_stride = p->head_stride;
+  a->q_stride = p->q_stride;
+  a->out_stride = p->out_stride;
+  a->scale = p->scale;
+  a->workspace = p->workspace;
+}
+static int launch_attn_append(const sqllm_attn_append* p, sqllm_stream_t stream, bool bf16) {
+  if (!p) return SQLLM_E_NULL;
+  sqllm_attn_decode a;
+  attn_append_fields(p, &a);
+  return launch_attn_decode(&a, stream, bf16, nullptr, p->q_lens, p->q_len < 0 ? 0 : p->q_len);
+}
+static int launch_attn_append_fp8(const sqllm_attn_append_fp8* p, sqllm_stream_t stream, bool bf16) {
+  if (!p) return SQLLM_E_NULL;
+  sqllm_attn_decode a;
+  attn_append_fields(p, &a);
+  sqllm_attn_decode_fp8 a8 = {};
+  a8.k_scale = p->k_scale;
+  a8.v_scale = p->v_scale;
+  return launch_attn_decode(&a, stream, bf16, &a8, p->q_lens, p->q_len < 0 ? 0 : p->q_len);
+}
+int sqllm_attn_append_f16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_append(a, stream, false); }
+int sqllm_attn_append_bf16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_append(a, stream, true); }
+int sqllm_attn_append_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, false); }
+int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, true); }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

@@ -272,6 +272,66 @@ inline AttnArgs make_attn_args(const AttnDecode& d) {
 // the combine of sqllm_attn_decode.hip (it does not see the cache): one workgroup of head_dim threads per (query head, row) over
 // the partials in the workspace.  A hook that file sets, so that the byte caches' partials are followed by the same kernel.
 extern hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
+// decode attention for q_len new tokens per sequence (sqllm_attn_append_f16 / _bf16, _fp8_f16 / _fp8_bf16), on the kernels of
+// sqllm_attn_append.hip and sqllm_attn_append_fp8.hip: K and V of a sequence are read once for all its new tokens.  `d.batch`
+// counts SEQUENCES; q, out and the workspace have d.batch * q_len rows.  Hooks, as above.
+struct AttnAppend {
+  AttnDecode d;
+  const int* q_lens;  // int32 [d.batch], device memory, or null: q_len real tokens everywhere
+  int q_len;          // rows per sequence, 1 to 16: a HOST field
+};
+extern hipError_t (*g_launch_attn_append)(const AttnAppend& d, hipStream_t stream);
+extern hipError_t (*g_launch_attn_append_fp8)(const AttnAppend& d, hipStream_t stream);
+// The append kernels' argument: AttnArgs' fields (the kernels are copies of their one-query siblings) and the tokens.
+struct AttnAppendArgs {
+  const void* q;
+  void* out;
+  const void* k_cache;
+  const void* v_cache;
+  const int* block_table;  // [batch, table_stride]: one table row per sequence
+  const int* seq_lens;     // [batch]: keys of the sequence, its new tokens included
+  const int* q_lens;       // [batch] or null
+  float* ws_acc;  // [batch * q_len, n_q_heads, n_parts, head_dim]
+  float* ws_ml;   // [batch * q_len, n_q_heads, n_parts, 2]
+  long long q_stride, out_stride;
+  unsigned slot_stride, head_stride;  // (below 2^32 wherever they are multiplied: checked by the host)
+  int n_q_heads, group, n_slots, block_size, table_stride;
+  int capacity;  // min(max_blocks * block_size, INT32_MAX)
+  int n_parts;
+  int batch;     // sequences
+  int q_len;
+  float scale;
+};
+inline AttnAppendArgs make_attn_append_args(const AttnAppend& p) {
+  const AttnDecode& d = p.d;
+  AttnAppendArgs k;
+  k.q = d.q;
+  k.out = d.out;
+  k.k_cache = d.k_cache;
+  k.v_cache = d.v_cache;
+  k.block_table = d.block_table;
+  k.seq_lens = d.seq_lens;
+  k.q_lens = p.q_lens;
+  k.ws_acc = static_cast<float*>(d.workspace);
+  k.ws_ml = k.ws_acc + (long long)d.batch * p.q_len * d.n_q_heads * d.n_parts * d.head_dim;
+  k.q_stride = d.q_stride;
+  k.out_stride = d.out_stride;
+  k.slot_stride = (unsigned)d.slot_stride;
+  k.head_stride = (unsigned)d.head_stride;
+  k.n_q_heads = d.n_q_heads;
+  k.group = d.n_q_heads / d.n_kv_heads;
+  k.n_slots = d.n_slots;
+  k.block_size = d.block_size;
+  k.table_stride = d.table_stride;
+  k.capacity = d.capacity;
+  k.n_parts = d.n_parts;
+  k.batch = d.batch;
+  k.q_len = p.q_len;
+  k.scale = d.scale;
+  return k;
+}
+// the combine of sqllm_attn_append.hip: the one above with every row's own length.  A hook that file sets, for the byte caches.
+extern hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

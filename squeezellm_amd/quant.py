@@ -1046,7 +1046,34 @@ def fuse_qkv_rope(module: nn.Module, q: str = "q_proj", k: str = "k_proj", v: st
 
 _ATTN_ENTRY = {torch.float16: "sqllm_attn_decode_f16", torch.bfloat16: "sqllm_attn_decode_bf16"}
 _ATTN_FP8_ENTRY = {torch.float16: "sqllm_attn_decode_fp8_f16", torch.bfloat16: "sqllm_attn_decode_fp8_bf16"}
+_ATTN_APPEND_ENTRY = {torch.float16: "sqllm_attn_append_f16", torch.bfloat16: "sqllm_attn_append_bf16"}
+_ATTN_APPEND_FP8_ENTRY = {torch.float16: "sqllm_attn_append_fp8_f16", torch.bfloat16: "sqllm_attn_append_fp8_bf16"}
 ATTN_PARTITION = _lib.ATTN_PARTITION  # keys per partition of the decode attention's kernel (SQLLM_ATTN_PARTITION)
+ATTN_APPEND_MAX_Q_LEN = 16  # new tokens per sequence the append kernels serve
+
+
+def append_as_decode_rows(block_table: torch.Tensor, seq_lens: torch.Tensor, q_len: int, q_lens, block_size: int):
+    """The one-query call that sqllm_attn_append (include/sqllm_hip.h) is defined by: (table [batch * q_len, max_blocks],
+    lengths [batch * q_len]) for DecodeAttention without q_len -- row b * q_len + t carries sequence b's table row and
+    L(b, t) = seq_lens[b] - (n_b - 1 - t), n_b = q_lens[b] (q_len where q_lens is None, 0 where negative).  Padding rows
+    (t >= n_b) and L <= 0 become length 0, the +0 row; L beyond max_blocks * block_size and the rows of a sequence with
+    n_b > q_len become max_blocks * block_size + 1, the NaN row.  Dtypes and device are the operands'.  The torch fallback
+    of DecodeAttention(..., q_len=) runs on it, and it is the emulation the append kernels are measured and tested against:
+    correct, but K and V are read q_len times."""
+    T, B = int(q_len), block_table.shape[0]
+    dev = seq_lens.device
+    seq = seq_lens.reshape(-1).long()
+    n = torch.full_like(seq, T) if q_lens is None else q_lens.reshape(-1).long()
+    over = (n > T)[:, None]
+    n = n.clamp(min=0)
+    t = torch.arange(T, device=dev)[None, :]
+    cap = block_table.shape[1] * int(block_size)
+    nan_len = min(cap + 1, (1 << 31) - 1)
+    lens = (seq[:, None] - (n[:, None] - 1 - t)).clamp(min=0, max=nan_len)
+    lens = torch.where(t < n[:, None], lens, torch.zeros_like(lens))
+    lens = torch.where(over, torch.full_like(lens, nan_len), lens)
+    table = block_table[:, None, :].expand(B, T, block_table.shape[1]).reshape(B * T, block_table.shape[1])
+    return table, lens.reshape(-1).to(seq_lens.dtype)
 
 
 def static_cache_blocks(batch: int, n_kv_heads: int, device=None) -> torch.Tensor:
@@ -1149,9 +1176,27 @@ class DecodeAttention(nn.Module):
     writes them with the same two scales, take the kernels for byte caches (sqllm_attn_decode_fp8_f16 / _bf16; include/sqllm_hip.h,
     sqllm_attn_decode_fp8): float(k) = k_scale * f32(byte), float(v) = v_scale * f32(byte) in the formulas above, half the bytes
     read.  Both scales are required then; scales with a 16-bit cache, or an fp8 cache without them, are a ValueError.  The torch
-    fallback dequantises.  Speed against the 16-bit kernel: tools/attn_decode_bench.py --cache fp8, DESIGN.md 4.4."""
+    fallback dequantises.  Speed against the 16-bit kernel: tools/attn_decode_bench.py --cache fp8, DESIGN.md 4.4.
+
+    forward(..., q_len=None, q_lens=None).  SEVERAL new tokens per sequence -- the verification step of speculative decoding, a
+    chunk of a prompt -- behind a front that wrote all of them (include/sqllm_hip.h, sqllm_attn_append): `q` is
+    [batch * q_len, W] or [batch, q_len, W], row b * q_len + t new token t of sequence b; `block_table` [batch, max_blocks] and
+    `seq_lens` [batch] are per SEQUENCE, seq_lens counting the new tokens too; `q_lens`: int32 [batch] on the device (used
+    without a copy; int64 is converted) or None, the real tokens n_b of each sequence -- rows t >= n_b are padding and +0,
+    n_b > q_len makes the sequence's rows NaN.  Token t attends the keys below seq_lens[b] - (n_b - 1 - t), and its row holds
+    exactly the bits the one-query call gives a row of that length: append_as_decode_rows is that call's table and lengths.
+    The defaults keep today's call.  q_len 1 to 16 and batch * q_len <= 64 on the served shapes take kernels; which ones is
+    routed by measurement and changes no bit (`append_route`: "auto", or "kernel" / "emulate" to force): the append kernels
+    (`last_route` "attn_append": two kernel nodes, K and V read once per sequence) everywhere but over an fp8 cache at 64 rows,
+    which takes the expansion on the one-query kernels (`last_route` "attn_decode": append_as_decode_rows in every call, a
+    dozen small kernels and 24 - 34 us in a replayed graph, then the one-query kernels).  Kernel against kernel, with the
+    expansion prepared outside the timed region, the one-query kernels are the faster ones on 313 of 384 measured points (the
+    repeated rows hit the caches; the append kernels win by up to 3.0x with 32/32 heads, a 16-bit cache and 4096 keys); end to
+    end, as a caller of this module pays, the append route is faster on 361 of 384, by 0.90x - 3.2x (tools/attn_append_bench.py,
+    DESIGN.md 4.4, profiles/attn_append_bench.txt).  Everything else is the torch fallback on the expansion."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
+    append_route = "auto"  # forward(..., q_len=): "auto" routes by measurement, "kernel" / "emulate" force one way (same bits)
 
     def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None):
         super().__init__()
@@ -1168,7 +1213,7 @@ class DecodeAttention(nn.Module):
 
     @property
     def last_route(self):
-        """"attn_decode" or "fallback": the way the most recent forward went (None before the first)."""
+        """"attn_decode", "attn_append" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def _check_cache(self, q: torch.Tensor, k_cache, v_cache) -> None:
@@ -1190,7 +1235,9 @@ class DecodeAttention(nn.Module):
             raise ValueError(f"the strides of a cache view must be at least head_dim = {D}, got {k_cache.stride()}")
 
     def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
-                out=None, block_size=None, k_scale=None, v_scale=None) -> torch.Tensor:
+                out=None, block_size=None, k_scale=None, v_scale=None, q_len=None, q_lens=None) -> torch.Tensor:
+        if q_len is not None or q_lens is not None:
+            return self._forward_append(q, k_cache, v_cache, block_table, seq_lens, out, block_size, k_scale, v_scale, q_len, q_lens)
         D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
         W = HQ * D
         if q.shape[-1] != W or q.stride(-1) != 1:
@@ -1260,6 +1307,107 @@ class DecodeAttention(nn.Module):
         if fp8:
             a.k_scale, a.v_scale = k_scale, v_scale
         quant_cuda._launch(quant_cuda._fn((_ATTN_FP8_ENTRY if fp8 else _ATTN_ENTRY)[q.dtype]), dev, (ref,))
+        return o if out is not None else o.reshape(*lead, W)
+
+    def _forward_append(self, q, k_cache, v_cache, block_table, seq_lens, out, block_size, k_scale, v_scale, q_len, q_lens) -> torch.Tensor:
+        """forward(..., q_len=T, q_lens=None): T new tokens per sequence in one read of K and V (sqllm_attn_append_*)."""
+        D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
+        W = HQ * D
+        if q_len is None:
+            raise ValueError("q_lens needs q_len, the rows per sequence")
+        T = int(q_len)
+        if T < 1:
+            raise ValueError(f"q_len must be positive, got {q_len}")
+        if q.shape[-1] != W or q.stride(-1) != 1:
+            raise ValueError(f"q must be [..., {W}] with a contiguous last dimension, got {tuple(q.shape)} with strides {q.stride()}")
+        if q.dim() not in (2, 3) or (q.dim() == 3 and q.shape[1] != T):
+            raise ValueError(f"q must be [batch * {T}, {W}] or [batch, {T}, {W}], got {tuple(q.shape)}")
+        bs = self.block_size if block_size is None else int(block_size)
+        if bs is None or bs < 1:
+            raise ValueError("block_size must be given, at construction or per call, and be positive")
+        self._check_cache(q, k_cache, v_cache)
+        fp8 = k_cache.dtype in FP8_KV_DTYPES and k_cache.dtype != q.dtype
+        k_scale, v_scale = _check_fp8_scales(fp8, k_scale, v_scale)
+        if fp8 and not math.isfinite(float(torch.tensor(self.scale, dtype=torch.float32) * torch.tensor(k_scale, dtype=torch.float32))):
+            raise ValueError(f"scale * k_scale must be finite in fp32, got {self.scale} * {k_scale}")
+        lead = q.shape[:-1]
+        q2 = q if q.dim() == 2 else q.reshape(-1, W)
+        rows = q2.shape[0]
+        if rows < 1 or rows % T:
+            raise ValueError(f"q must have a positive multiple of q_len = {T} rows, got {rows}")
+        batch = rows // T
+        if (not isinstance(block_table, torch.Tensor) or block_table.dtype not in (torch.int32, torch.int64) or block_table.dim() != 2
+                or block_table.shape[0] != batch or block_table.shape[1] < 1 or block_table.device != q.device):
+            raise ValueError(f"block_table must be int32 (or int64) [{batch}, max_blocks] on {q.device}: one row per sequence")
+        for name, t in (("seq_lens", seq_lens), ("q_lens", q_lens)):
+            if t is None and name == "q_lens":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64) or t.numel() != batch or t.device != q.device:
+                raise ValueError(f"{name} must be {batch} int32 (or int64) values on {q.device}: one per sequence")
+        if out is not None:
+            if (not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or out.shape != (rows, W)
+                    or out.stride(1) != 1 or (rows > 1 and out.stride(0) < W)):
+                raise ValueError(f"out must be a {q.dtype} [{rows}, {W}] tensor on {q.device} with a contiguous last dimension")
+        if rows > 1 and q2.stride(0) < W:
+            q2 = q2.contiguous()
+        kernel = (q.dtype in _ATTN_APPEND_ENTRY and q.is_cuda and D in (64, 128) and HQ // H <= 8 and T <= ATTN_APPEND_MAX_Q_LEN
+                  and rows <= 64)
+        if not kernel:
+            self.__dict__["_last_route"] = "fallback"
+            table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
+            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
+            if out is not None:
+                out.copy_(o)
+                return out
+            return o.reshape(*lead, W)
+        if self.append_route not in ("auto", "kernel", "emulate"):
+            raise ValueError(f"append_route must be 'auto', 'kernel' or 'emulate', got {self.append_route!r}")
+        # routed by measurement, END TO END (tools/attn_append_bench.py `route_emul` against `append`, DESIGN.md 4.4): the expansion
+        # below is a dozen small kernels in every call, 24 - 34 us in a replayed graph, which the one-query kernels win back only
+        # over an fp8 cache at 64 rows (by up to 10 %); everywhere else the append kernels are faster.  The same bits either way.
+        if self.append_route == "emulate" or (self.append_route == "auto" and fp8 and rows >= 64):
+            table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
+            o = self.forward(q2, k_cache, v_cache, table, lens, out=out, block_size=bs, k_scale=k_scale if fp8 else None,
+                             v_scale=v_scale if fp8 else None)  # (`last_route` "attn_decode")
+            return o if out is not None else o.reshape(*lead, W)
+        bt = block_table if block_table.dtype == torch.int32 else block_table.to(torch.int32)  # (a kernel)
+        if bt.stride(1) != 1 or (batch > 1 and bt.stride(0) < bt.shape[1]):
+            bt = bt.contiguous()
+
+        def int32_vector(t):
+            t = t.reshape(-1)
+            if t.dtype != torch.int32:
+                t = t.to(torch.int32)  # (a kernel)
+            return t if t.is_contiguous() else t.contiguous()
+
+        sl = int32_vector(seq_lens)
+        ql = None if q_lens is None else int32_vector(q_lens)
+        self.__dict__["_last_route"] = "attn_append"
+        dev = q.get_device()
+        o = out if out is not None else torch.empty((rows, W), dtype=q.dtype, device=q.device)
+        stream = quant_cuda._raw_stream(dev)
+        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.attn_decode_workspace_bytes(rows, HQ, D, bt.shape[1], bs), q.device,
+                           self.GRAPH_WS_MAX_BYTES)
+        descs = self.__dict__.setdefault("_desc_append8" if fp8 else "_desc_append", {})
+        hit = descs.get((dev, stream))
+        if hit is None:
+            a = _lib.SqllmAttnAppendFp8() if fp8 else _lib.SqllmAttnAppend()
+            hit = descs[(dev, stream)] = (a, ctypes.byref(a))
+        a, ref = hit
+        a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+        a.block_table, a.seq_lens = bt.data_ptr(), sl.data_ptr()
+        a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
+        a.batch, a.n_q_heads, a.n_kv_heads, a.head_dim = batch, HQ, H, D
+        a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, bt.shape[1]
+        a.table_stride = bt.stride(0) if batch > 1 else bt.shape[1]
+        a.slot_stride = k_cache.stride(0)
+        a.head_stride = k_cache.stride(1) if H > 1 else D  # (one head: its stride is anything, and never used)
+        a.q_stride = q2.stride(0) if rows > 1 else W
+        a.out_stride = o.stride(0) if rows > 1 else W
+        a.scale, a.workspace = self.scale, ws.data_ptr()
+        if fp8:
+            a.k_scale, a.v_scale = k_scale, v_scale
+        quant_cuda._launch(quant_cuda._fn((_ATTN_APPEND_FP8_ENTRY if fp8 else _ATTN_APPEND_ENTRY)[q.dtype]), dev, (ref,))
         return o if out is not None else o.reshape(*lead, W)
 
 
