@@ -1,11 +1,12 @@
 // sqllm_attn_append.hip -- decode attention for SEVERAL new tokens per sequence in one read of K and V (include/sqllm_hip.h:
 // sqllm_attn_append_f16 / _bf16).  Row (b, t) holds the bits sqllm_attn_decode_* gives a row with table row b and length
-// L(b, t) = seq_lens[b] - (n_b - 1 - t): the kernels here are the ones of sqllm_attn_decode.hip, copied, with one change of
+// L(b, t) = seq_lens[b] - (n_b - 1 - t): the kernel BODIES here are the ones of sqllm_attn_decode.hip, copied, with one change of
 // meaning -- a workgroup's heads are VIRTUAL heads, (new token, query head of the kv group) pairs, each with its own length.
+// What is still a copy is the bodies alone: the lane helpers, phase 0 and the launch ladder are sqllm_attn.h's, shared by the four files.
 //
 // Launch 1 (partials), one workgroup of 256 threads per (partition of kAttnPartition keys, kv head, sequence, chunk of up to 8
 // virtual heads); the chunks of a (partition, kv head, sequence) read the same keys and are the slowest grid dimension:
-//   0. (sqllm_attn_append.h) the chunk's virtual heads and the keys nv[h] of this partition each of them attends; rows that need no
+//   0. (sqllm_attn.h: append_phase0) the chunk's virtual heads and the keys nv[h] of this partition each of them attends; rows that need no
 //      keys; the partition's slots, once, for the longest head.  A head that meets a bad table entry ends as its one-query
 //      sibling does, the heads that end below the entry go on.
 //   1. QK as there, for the keys of the longest head; a score at or beyond the head's own nv[h] is -inf in LDS.
@@ -28,57 +29,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sqllm_attn_append.h"
+#include "sqllm_attn.h"
 #include "sqllm_decode.h"
 #include "sqllm_kernels.h"
 
 namespace sqllm {
 
-constexpr int kAppendUnroll = 4;  // 16-byte loads in flight per lane before the first use
-
-// 16 bytes of 16-bit elements that are aligned to their elements only
-struct __attribute__((packed, aligned(2))) AppendPacked8 {
-  uint32_t w[4];
-};
-
-template <typename OT>
-__device__ __forceinline__ void append_widen8(const AppendPacked8& p, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (std::is_same<OT, __bf16>::value) {
-      f[2 * i] = __builtin_bit_cast(float, p.w[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, p.w[i] & 0xffff0000u);
-    } else {
-      f[2 * i] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] & 0xffffu));
-      f[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] >> 16));
-    }
-  }
-}
-
-// the sum over the LPK lanes of a key, in every one of them (a + b and b + a: the same bits on both sides of each exchange)
-template <int LPK>
-__device__ __forceinline__ float append_key_sum(float v) {
-  v += dpp_f32<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f32<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f32<0x141, 0xf>(v);  // row_half_mirror: the other quad of the 8 lanes
-  if constexpr (LPK == 16) v += dpp_f32<0x140, 0xf>(v);  // row_mirror: the other half of the row
-  return v;
-}
-
-__device__ __forceinline__ float append_wave_max(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
 template <int D, int GC, typename OT>
-__global__ void __launch_bounds__(kAppendThreads) sqllm_attn_append_kernel(const AttnAppendArgs a) {
+__global__ void __launch_bounds__(kAttnThreads) sqllm_attn_append_kernel(const AttnAppendArgs a) {
   constexpr int P = kAttnPartition;
   constexpr int LPK = D / 8;         // lanes per key
   constexpr int KPW = 64 / LPK;      // keys per wave instruction
   constexpr int KPS = KPW * 4;       // keys per step of the workgroup
   constexpr int STEPS = P / KPS;
-  constexpr int U = kAppendUnroll;
+  constexpr int U = kAttnUnroll;
   constexpr int HC = GC < 4 ? GC : 4;  // heads per round of the key-lane exchange
   static_assert(STEPS % U == 0, "whole unrolled rounds");
   __shared__ float sc[GC][P];
@@ -111,7 +75,7 @@ __global__ void __launch_bounds__(kAppendThreads) sqllm_attn_append_kernel(const
       if (live >> h & 1) {
         const AppendHead v = append_head(a, hk, b, chunk * GC + h);
         const OT* q = reinterpret_cast<const OT*>(a.q) + (long long)v.row * a.q_stride + (long long)v.head * D + sub * 8;
-        append_widen8<OT>(*reinterpret_cast<const AppendPacked8*>(q), qf[h]);
+        widen8<OT>(*reinterpret_cast<const Packed8*>(q), qf[h]);
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) qf[h][j] = 0.0f;
@@ -120,24 +84,24 @@ __global__ void __launch_bounds__(kAppendThreads) sqllm_attn_append_kernel(const
     const int my_nv = sub < GC ? nvl[sub < GC ? sub : 0] : 0;
     const OT* kc = reinterpret_cast<const OT*>(a.k_cache);
     for (int s0 = 0; s0 < nsteps; s0 += U) {
-      AppendPacked8 kr[U];
+      Packed8 kr[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
-        kr[u] = *reinterpret_cast<const AppendPacked8*>(kc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+        kr[u] = *reinterpret_cast<const Packed8*>(kc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
         float kf[8];
-        append_widen8<OT>(kr[u], kf);
+        widen8<OT>(kr[u], kf);
         float mine = 0.0f;
 #pragma unroll
         for (int h = 0; h < GC; ++h) {
           float dot = qf[h][0] * kf[0];
 #pragma unroll
           for (int j = 1; j < 8; ++j) dot = fmaf(qf[h][j], kf[j], dot);
-          dot = append_key_sum<LPK>(dot);
+          dot = key_sum<LPK>(dot);
           if (sub == h) mine = dot;
         }
         if (sub < GC) sc[sub][kl] = kl < my_nv ? a.scale * mine : -__builtin_inff();
@@ -157,7 +121,7 @@ __global__ void __launch_bounds__(kAppendThreads) sqllm_attn_append_kernel(const
       s[i] = kl < n_valid ? sc[h][kl] : -__builtin_inff();
       m = fmaxf(m, s[i]);
     }
-    m = append_wave_max(m);
+    m = wave_max(m);
     float l = 0.0f;
 #pragma unroll
     for (int i = 0; i < P / 64; ++i) {
@@ -186,18 +150,18 @@ __global__ void __launch_bounds__(kAppendThreads) sqllm_attn_append_kernel(const
     // left out whole, which leaves what its fmaf(0, 0, acc) leaves)
     const int shared_steps = n_min / KPS;
     for (int s0 = 0; s0 < shared_steps; s0 += U) {
-      AppendPacked8 vr[U];
+      Packed8 vr[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
-        vr[u] = *reinterpret_cast<const AppendPacked8*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+        vr[u] = *reinterpret_cast<const Packed8*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
         if (s0 + u >= shared_steps) break;  // (uniform)
         float vf[8];
-        append_widen8<OT>(vr[u], vf);
+        widen8<OT>(vr[u], vf);
 #pragma unroll
         for (int h = 0; h < GC; ++h) {
           const float w = sc[h][kl];  // (a head that is not served here gathers what nobody reads)
@@ -212,9 +176,9 @@ __global__ void __launch_bounds__(kAppendThreads) sqllm_attn_append_kernel(const
     // another token's real data, with any bits, so it is left out by a SELECT on the accumulator, never by a factor 0
     for (int s0 = shared_steps; s0 < nsteps; ++s0) {
       const int kl = s0 * KPS + wave * KPW + grp;
-      const AppendPacked8 vr = *reinterpret_cast<const AppendPacked8*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+      const Packed8 vr = *reinterpret_cast<const Packed8*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
       float vf[8];
-      append_widen8<OT>(vr, vf);
+      widen8<OT>(vr, vf);
 #pragma unroll
       for (int h = 0; h < GC; ++h) {
         const bool mine = kl < nvl[h];  // (from LDS: eight more scalars held across the loops do not fit)
@@ -236,7 +200,7 @@ __global__ void __launch_bounds__(kAppendThreads) sqllm_attn_append_kernel(const
       at[1] = f32x4{acc[h0 + hh][4], acc[h0 + hh][5], acc[h0 + hh][6], acc[h0 + hh][7]};
     }
     __syncthreads();
-    for (int i = tid; i < HC * D; i += kAppendThreads) {
+    for (int i = tid; i < HC * D; i += kAttnThreads) {
       const int hh = i / D, d = i % D, h = h0 + hh;
       if (nvl[h] == 0) continue;
       const AppendHead v = append_head(a, hk, b, chunk * GC + h);
@@ -284,53 +248,20 @@ __global__ void __launch_bounds__(D) sqllm_attn_append_combine_kernel(const Attn
   out[d] = (OT)(t / l);
 }
 
+struct AttnAppendTag : AttnTokens {
+  static constexpr bool fp8 = false;
+  template <int D, int GC, typename OT>
+  static auto kernel() { return sqllm_attn_append_kernel<D, GC, OT>; }
+  template <int D, typename OT>
+  static auto combine_kernel() { return sqllm_attn_append_combine_kernel<D, OT>; }
+};
+
 // the combine alone: behind this file's partials, and behind those of sqllm_attn_append_fp8.hip
-static hipError_t launch_attn_append_combine(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) {
-  if (head_dim != 64 && head_dim != 128) return hipErrorInvalidValue;
-  const dim3 grid(k.n_q_heads, k.batch * k.q_len);
-  if (head_dim == 64) {
-    if (bf16) hipLaunchKernelGGL((sqllm_attn_append_combine_kernel<64, __bf16>), grid, dim3(64), 0, stream, k);
-    else hipLaunchKernelGGL((sqllm_attn_append_combine_kernel<64, _Float16>), grid, dim3(64), 0, stream, k);
-  } else {
-    if (bf16) hipLaunchKernelGGL((sqllm_attn_append_combine_kernel<128, __bf16>), grid, dim3(128), 0, stream, k);
-    else hipLaunchKernelGGL((sqllm_attn_append_combine_kernel<128, _Float16>), grid, dim3(128), 0, stream, k);
-  }
-  return hipGetLastError();
+static hipError_t launch_attn_combine_tokens(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) {
+  return launch_attn_combine<AttnAppendTag>(k, head_dim, bf16, dim3(k.n_q_heads, k.batch * k.q_len), stream);
 }
 
-// chunks of GC virtual heads: the slowest grid dimension, so that the workgroups which read the same keys lie
-// n_parts * n_kv_heads * batch apart in linear id (on one XCD where that product is a multiple of 8: 16 partitions of a 4096-key
-// capacity are, 9 partitions of one kv head and one sequence are not; no other order was measured)
-template <int D, int GC, typename OT>
-static hipError_t launch_append_inst(const AttnAppendArgs& k, int n_kv_heads, bool bf16, hipStream_t stream) {
-  const int chunks = (k.q_len * k.group + GC - 1) / GC;
-  hipLaunchKernelGGL((sqllm_attn_append_kernel<D, GC, OT>), dim3(k.n_parts, n_kv_heads, k.batch * chunks), dim3(kAppendThreads), 0, stream, k);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess || k.n_parts == 1) return e;
-  return launch_attn_append_combine(k, D, bf16, stream);
-}
-
-template <int D, typename OT>
-static hipError_t launch_append_group(const AttnAppendArgs& k, int n_kv_heads, bool bf16, hipStream_t stream) {
-  switch (k.q_len * k.group) {  // the virtual heads of a (kv head, sequence)
-    case 1: return launch_append_inst<D, 1, OT>(k, n_kv_heads, bf16, stream);
-    case 2: return launch_append_inst<D, 2, OT>(k, n_kv_heads, bf16, stream);
-    case 3: case 4: return launch_append_inst<D, 4, OT>(k, n_kv_heads, bf16, stream);
-    default: return launch_append_inst<D, 8, OT>(k, n_kv_heads, bf16, stream);
-  }
-}
-
-static hipError_t launch_attn_append(const AttnAppend& p, hipStream_t stream) {
-  const AttnDecode& d = p.d;
-  if ((d.head_dim != 64 && d.head_dim != 128) || d.n_kv_heads < 1 || d.n_q_heads % d.n_kv_heads || d.n_q_heads / d.n_kv_heads > 8 ||
-      d.batch < 1 || d.n_parts < 1 || p.q_len < 1 || p.q_len > 16)
-    return hipErrorInvalidValue;
-  const AttnAppendArgs k = make_attn_append_args(p);
-  if (d.bf16) return d.head_dim == 64 ? launch_append_group<64, __bf16>(k, d.n_kv_heads, true, stream) : launch_append_group<128, __bf16>(k, d.n_kv_heads, true, stream);
-  return d.head_dim == 64 ? launch_append_group<64, _Float16>(k, d.n_kv_heads, false, stream) : launch_append_group<128, _Float16>(k, d.n_kv_heads, false, stream);
-}
-
-// the host layer reaches the launchers through these hooks (sqllm_kernels.h), so that it links without this file too
-static const bool g_attn_append_registered = (g_launch_attn_append = launch_attn_append, g_launch_attn_append_combine = launch_attn_append_combine, true);
+// the host layer reaches the launcher through its slot of g_launch_attn (sqllm_kernels.h), so that it links without this file too
+static const bool g_attn_append_registered = (g_launch_attn[kAttnAppend] = launch_attn<AttnAppendTag>, g_launch_attn_append_combine = launch_attn_combine_tokens, true);
 
 }  // namespace sqllm

@@ -1,7 +1,7 @@
 // sqllm_attn_append_fp8.hip -- decode attention for several new tokens per sequence over a KV cache of 1-byte OCP e4m3fn elements
 // (include/sqllm_hip.h: sqllm_attn_append_fp8_f16 / _bf16; the suffix names the type of q and out).  Row (b, t) holds the bits
-// sqllm_attn_decode_fp8_* gives a row with table row b and length L(b, t).  The partial kernel of sqllm_attn_decode_fp8.hip, copied,
-// with the virtual heads of sqllm_attn_append.hip (phases 0 to 4 are described there, the lanes and the 16 elements per lane in
+// sqllm_attn_decode_fp8_* gives a row with table row b and length L(b, t).  The BODY of the partial kernel of sqllm_attn_decode_fp8.hip,
+// copied (the lane helpers, phase 0 and the launch ladder are not copies: sqllm_attn.h), with the virtual heads of sqllm_attn_append.hip (phases 0 to 4 are described there, the lanes and the 16 elements per lane in
 // sqllm_attn_decode_fp8.hip); with more than one partition the combine of sqllm_attn_append.hip follows, reached through
 // g_launch_attn_append_combine (it does not see the cache).  k_scale is folded into the score's scale on the host; v_scale
 // multiplies each partition's sum over the keys once per (virtual head, d).
@@ -13,76 +13,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sqllm_attn_append.h"
+#include "sqllm_attn.h"
 #include "sqllm_decode.h"
 #include "sqllm_kernels.h"
 
 namespace sqllm {
 
-constexpr int kAppendFp8Unroll = 4;  // 16-byte loads in flight per lane before the first use
-
-// 16 bytes that are aligned to one byte only
-struct __attribute__((packed, aligned(1))) AppendBytes16 {
-  uint32_t w[4];
-};
-// 16 bytes of 16-bit elements that are aligned to their elements only (q)
-struct __attribute__((packed, aligned(2))) AppendHalves8 {
-  uint32_t w[4];
-};
-
-typedef float append_f32x2 __attribute__((ext_vector_type(2)));
-
-// 16 e4m3fn bytes as fp32 (a NaN byte is a NaN)
-__device__ __forceinline__ void append_widen_e4m3(const AppendBytes16& p, float (&f)[16]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const append_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)p.w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)p.w[i], true);
-    f[4 * i] = lo[0];
-    f[4 * i + 1] = lo[1];
-    f[4 * i + 2] = hi[0];
-    f[4 * i + 3] = hi[1];
-  }
-}
-
-template <typename OT>
-__device__ __forceinline__ void append_widen_q8(const AppendHalves8& p, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (std::is_same<OT, __bf16>::value) {
-      f[2 * i] = __builtin_bit_cast(float, p.w[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, p.w[i] & 0xffff0000u);
-    } else {
-      f[2 * i] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] & 0xffffu));
-      f[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] >> 16));
-    }
-  }
-}
-
-// the sum over the LPK lanes of a key, in every one of them (a + b and b + a: the same bits on both sides of each exchange)
-template <int LPK>
-__device__ __forceinline__ float append_key_sum_fp8(float v) {
-  static_assert(LPK == 4 || LPK == 8, "head_dim 64 or 128");
-  v += dpp_f32<0xB1, 0xf>(v);  // quad_perm [1,0,3,2]
-  v += dpp_f32<0x4E, 0xf>(v);  // quad_perm [2,3,0,1]
-  if constexpr (LPK == 8) v += dpp_f32<0x141, 0xf>(v);  // row_half_mirror: the other quad of the 8 lanes
-  return v;
-}
-
-__device__ __forceinline__ float append_wave_max_fp8(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
 template <int D, int GC, typename OT>
-__global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kernel(const AttnAppendArgs a, const float v_scale) {
+__global__ void __launch_bounds__(kAttnThreads, 2) sqllm_attn_append_fp8_kernel(const AttnAppendArgs a, const float v_scale) {
   constexpr int P = kAttnPartition;
   constexpr int E = 16;              // elements (bytes) per lane and key
   constexpr int LPK = D / E;         // lanes per key
   constexpr int KPW = 64 / LPK;      // keys per wave instruction
   constexpr int KPS = KPW * 4;       // keys per step of the workgroup
   constexpr int STEPS = P / KPS;
-  constexpr int U = kAppendFp8Unroll;
+  constexpr int U = kAttnUnroll;
   constexpr int HC = GC < 2 ? GC : 2;          // heads per round of the key-lane exchange
   constexpr int R = (GC + LPK - 1) / LPK;      // heads whose score one lane of a key stores
   static_assert(STEPS % U == 0, "whole unrolled rounds");
@@ -114,8 +59,8 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
       if (nv[h] > 0) {
         const AppendHead v = append_head(a, hk, b, chunk * GC + h);
         const OT* q = reinterpret_cast<const OT*>(a.q) + (long long)v.row * a.q_stride + (long long)v.head * D + sub * E;
-        append_widen_q8<OT>(*reinterpret_cast<const AppendHalves8*>(q), qf[h]);
-        append_widen_q8<OT>(*reinterpret_cast<const AppendHalves8*>(q + 8), qf[h] + 8);
+        widen8<OT>(*reinterpret_cast<const Packed8*>(q), qf[h]);
+        widen8<OT>(*reinterpret_cast<const Packed8*>(q + 8), qf[h] + 8);
       } else {
 #pragma unroll
         for (int j = 0; j < E; ++j) qf[h][j] = 0.0f;
@@ -123,17 +68,17 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
     }
     const uint8_t* kc = reinterpret_cast<const uint8_t*>(a.k_cache);
     for (int s0 = 0; s0 < nsteps; s0 += U) {
-      AppendBytes16 kr[U];
+      Bytes16 kr[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
-        kr[u] = *reinterpret_cast<const AppendBytes16*>(kc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+        kr[u] = *reinterpret_cast<const Bytes16*>(kc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
         float kf[E];
-        append_widen_e4m3(kr[u], kf);
+        widen_e4m3(kr[u], kf);
         float mine[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) mine[r] = 0.0f;
@@ -142,7 +87,7 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
           float dot = qf[h][0] * kf[0];
 #pragma unroll
           for (int j = 1; j < E; ++j) dot = fmaf(qf[h][j], kf[j], dot);
-          dot = append_key_sum_fp8<LPK>(dot);
+          dot = key_sum_fp8<LPK>(dot);
           if (sub == h % LPK) mine[h / LPK] = dot;
         }
 #pragma unroll
@@ -166,7 +111,7 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
       s[i] = kl < n_valid ? sc[h][kl] : -__builtin_inff();
       m = fmaxf(m, s[i]);
     }
-    m = append_wave_max_fp8(m);
+    m = wave_max(m);
     float l = 0.0f;
 #pragma unroll
     for (int i = 0; i < P / 64; ++i) {
@@ -195,18 +140,18 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
     // left out whole, which leaves what its fmaf(0, 0, acc) leaves)
     const int shared_steps = n_min / KPS;
     for (int s0 = 0; s0 < shared_steps; s0 += U) {
-      AppendBytes16 vr[U];
+      Bytes16 vr[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
-        vr[u] = *reinterpret_cast<const AppendBytes16*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+        vr[u] = *reinterpret_cast<const Bytes16*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int kl = (s0 + u) * KPS + wave * KPW + grp;
         if (s0 + u >= shared_steps) break;  // (uniform)
         float vf[E];
-        append_widen_e4m3(vr[u], vf);
+        widen_e4m3(vr[u], vf);
 #pragma unroll
         for (int h = 0; h < GC; ++h) {
           const float w = sc[h][kl];  // (a head that is not served here gathers what nobody reads)
@@ -220,9 +165,9 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
     // another token's real data, with any bits, so it is left out by a SELECT on the accumulator, never by a factor 0
     for (int s0 = shared_steps; s0 < nsteps; ++s0) {
       const int kl = s0 * KPS + wave * KPW + grp;
-      const AppendBytes16 vr = *reinterpret_cast<const AppendBytes16*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
+      const Bytes16 vr = *reinterpret_cast<const Bytes16*>(vc + ((unsigned long long)(unsigned)slots[kl] * a.slot_stride + head_off));
       float vf[E];
-      append_widen_e4m3(vr, vf);
+      widen_e4m3(vr, vf);
 #pragma unroll
       for (int h = 0; h < GC; ++h) {
         const bool mine = kl < nv[h];
@@ -245,7 +190,7 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
         at[i] = f32x4{acc[h0 + hh][4 * i], acc[h0 + hh][4 * i + 1], acc[h0 + hh][4 * i + 2], acc[h0 + hh][4 * i + 3]};
     }
     __syncthreads();
-    for (int i = tid; i < HC * D; i += kAppendThreads) {
+    for (int i = tid; i < HC * D; i += kAttnThreads) {
       const int hh = i / D, d = i % D, h = h0 + hh;
       if (nvl[h] == 0) continue;
       const AppendHead v = append_head(a, hk, b, chunk * GC + h);
@@ -267,40 +212,13 @@ __global__ void __launch_bounds__(kAppendThreads, 2) sqllm_attn_append_fp8_kerne
   }
 }
 
-template <int D, int GC, typename OT>
-static hipError_t launch_append_fp8_inst(const AttnAppendArgs& k, float v_scale, int n_kv_heads, bool bf16, hipStream_t stream) {
-  if (k.n_parts > 1 && !g_launch_attn_append_combine) return hipErrorNotSupported;  // (a missing kernel is an error, before anything is launched)
-  const int chunks = (k.q_len * k.group + GC - 1) / GC;
-  hipLaunchKernelGGL((sqllm_attn_append_fp8_kernel<D, GC, OT>), dim3(k.n_parts, n_kv_heads, k.batch * chunks), dim3(kAppendThreads), 0, stream, k, v_scale);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess || k.n_parts == 1) return e;
-  return g_launch_attn_append_combine(k, D, bf16, stream);
-}
+struct AttnAppendFp8Tag : AttnTokens {  // (no combine of its own: g_launch_attn_append_combine, the 16-bit file's)
+  static constexpr bool fp8 = true;
+  template <int D, int GC, typename OT>
+  static auto kernel() { return sqllm_attn_append_fp8_kernel<D, GC, OT>; }
+};
 
-template <int D, typename OT>
-static hipError_t launch_append_fp8_group(const AttnAppendArgs& k, float v_scale, int n_kv_heads, bool bf16, hipStream_t stream) {
-  switch (k.q_len * k.group) {  // the virtual heads of a (kv head, sequence)
-    case 1: return launch_append_fp8_inst<D, 1, OT>(k, v_scale, n_kv_heads, bf16, stream);
-    case 2: return launch_append_fp8_inst<D, 2, OT>(k, v_scale, n_kv_heads, bf16, stream);
-    case 3: case 4: return launch_append_fp8_inst<D, 4, OT>(k, v_scale, n_kv_heads, bf16, stream);
-    default: return launch_append_fp8_inst<D, 8, OT>(k, v_scale, n_kv_heads, bf16, stream);
-  }
-}
-
-static hipError_t launch_attn_append_fp8(const AttnAppend& p, hipStream_t stream) {
-  const AttnDecode& d = p.d;
-  if ((d.head_dim != 64 && d.head_dim != 128) || d.n_kv_heads < 1 || d.n_q_heads % d.n_kv_heads || d.n_q_heads / d.n_kv_heads > 8 ||
-      d.batch < 1 || d.n_parts < 1 || p.q_len < 1 || p.q_len > 16)
-    return hipErrorInvalidValue;
-  const AttnAppendArgs k = make_attn_append_args(p);
-  if (d.bf16)
-    return d.head_dim == 64 ? launch_append_fp8_group<64, __bf16>(k, d.v_scale, d.n_kv_heads, true, stream)
-                            : launch_append_fp8_group<128, __bf16>(k, d.v_scale, d.n_kv_heads, true, stream);
-  return d.head_dim == 64 ? launch_append_fp8_group<64, _Float16>(k, d.v_scale, d.n_kv_heads, false, stream)
-                          : launch_append_fp8_group<128, _Float16>(k, d.v_scale, d.n_kv_heads, false, stream);
-}
-
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_attn_append_fp8_registered = (g_launch_attn_append_fp8 = launch_attn_append_fp8, true);
+// the host layer reaches the launcher through its slot of g_launch_attn (sqllm_kernels.h), so that it links without this file too
+static const bool g_attn_append_fp8_registered = (g_launch_attn[kAttnAppendFp8] = launch_attn<AttnAppendFp8Tag>, true);
 
 }  // namespace sqllm

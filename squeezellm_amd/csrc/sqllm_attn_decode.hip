@@ -26,54 +26,20 @@
 //
 // Registers: q (group x 8 fp32) lives in phase 1 only, acc (group x 8 fp32) in phase 3 only; no scratch, no spills
 // (tests/test_codegen_attn_decode_cpu.py).  LDS: scores 8 KiB at most, slots 1 KiB, the key-lane exchange 32 KiB at most: three workgroups per CU.
+//
+// This file holds the two kernels, a tag that names them and one registration line.  The lane helpers and the launch ladder
+// (type x head_dim x group class, then the combine) are sqllm_attn.h's, shared with the three sibling files; the kernel BODIES
+// of the siblings are copies of the ones here ("Not shared either").
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sqllm_attn.h"
 #include "sqllm_decode.h"
 #include "sqllm_kernels.h"
 
 namespace sqllm {
 
-constexpr int kAttnThreads = 256;
-constexpr int kAttnUnroll = 4;  // 16-byte loads in flight per lane before the first use
-static_assert(kAttnPartition == kAttnThreads, "phase 0 resolves one key per thread");
-
-// (AttnArgs, the kernels' argument: sqllm_kernels.h)
-
-// 16 bytes of 16-bit elements that are aligned to their elements only
-struct __attribute__((packed, aligned(2))) Packed8 {
-  uint32_t w[4];
-};
-
-template <typename OT>
-__device__ __forceinline__ void widen8(const Packed8& p, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (std::is_same<OT, __bf16>::value) {
-      f[2 * i] = __builtin_bit_cast(float, p.w[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, p.w[i] & 0xffff0000u);
-    } else {
-      f[2 * i] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] & 0xffffu));
-      f[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] >> 16));
-    }
-  }
-}
-
-// the sum over the LPK lanes of a key, in every one of them (a + b and b + a: the same bits on both sides of each exchange)
-template <int LPK>
-__device__ __forceinline__ float key_sum(float v) {
-  v += dpp_f32<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f32<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f32<0x141, 0xf>(v);  // row_half_mirror: the other quad of the 8 lanes
-  if constexpr (LPK == 16) v += dpp_f32<0x140, 0xf>(v);  // row_mirror: the other half of the row
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
+// (AttnArgs, the kernels' argument: sqllm_kernels.h; the lane helpers and the launch ladder: sqllm_attn.h)
 
 template <int D, int GC, typename OT>
 __global__ void __launch_bounds__(kAttnThreads) sqllm_attn_decode_kernel(const AttnArgs a) {
@@ -296,49 +262,20 @@ __global__ void __launch_bounds__(D) sqllm_attn_combine_kernel(const AttnArgs a)
   out[d] = (OT)(t / l);
 }
 
-template <int D, int GC, typename OT>
-static hipError_t launch_attn_inst(const AttnArgs& k, int n_kv_heads, int batch, hipStream_t stream) {
-  hipLaunchKernelGGL((sqllm_attn_decode_kernel<D, GC, OT>), dim3(k.n_parts, n_kv_heads, batch), dim3(kAttnThreads), 0, stream, k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || k.n_parts == 1) return e;
-  hipLaunchKernelGGL((sqllm_attn_combine_kernel<D, OT>), dim3(k.n_q_heads, batch), dim3(D), 0, stream, k);
-  return hipGetLastError();
+struct AttnDecodeTag : AttnOneQuery {
+  static constexpr bool fp8 = false;
+  template <int D, int GC, typename OT>
+  static auto kernel() { return sqllm_attn_decode_kernel<D, GC, OT>; }
+  template <int D, typename OT>
+  static auto combine_kernel() { return sqllm_attn_combine_kernel<D, OT>; }
+};
+
+// the combine alone: behind this file's partials, and behind those of sqllm_attn_decode_fp8.hip
+static hipError_t launch_attn_combine_rows(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) {
+  return launch_attn_combine<AttnDecodeTag>(k, head_dim, bf16, dim3(k.n_q_heads, batch), stream);
 }
 
-template <int D, typename OT>
-static hipError_t launch_attn_group(const AttnArgs& k, int n_kv_heads, int batch, hipStream_t stream) {
-  switch (k.group) {
-    case 1: return launch_attn_inst<D, 1, OT>(k, n_kv_heads, batch, stream);
-    case 2: return launch_attn_inst<D, 2, OT>(k, n_kv_heads, batch, stream);
-    case 3: case 4: return launch_attn_inst<D, 4, OT>(k, n_kv_heads, batch, stream);
-    default: return launch_attn_inst<D, 8, OT>(k, n_kv_heads, batch, stream);
-  }
-}
-
-static hipError_t launch_attn_decode(const AttnDecode& d, hipStream_t stream) {
-  if ((d.head_dim != 64 && d.head_dim != 128) || d.n_kv_heads < 1 || d.n_q_heads % d.n_kv_heads || d.n_q_heads / d.n_kv_heads > 8 ||
-      d.batch < 1 || d.n_parts < 1)
-    return hipErrorInvalidValue;
-  const AttnArgs k = make_attn_args(d);
-  if (d.bf16) return d.head_dim == 64 ? launch_attn_group<64, __bf16>(k, d.n_kv_heads, d.batch, stream) : launch_attn_group<128, __bf16>(k, d.n_kv_heads, d.batch, stream);
-  return d.head_dim == 64 ? launch_attn_group<64, _Float16>(k, d.n_kv_heads, d.batch, stream) : launch_attn_group<128, _Float16>(k, d.n_kv_heads, d.batch, stream);
-}
-
-// the combine alone, behind partials that another file's kernels left in the workspace (sqllm_attn_decode_fp8.hip)
-static hipError_t launch_attn_combine(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) {
-  if (head_dim != 64 && head_dim != 128) return hipErrorInvalidValue;
-  const dim3 grid(k.n_q_heads, batch);
-  if (head_dim == 64) {
-    if (bf16) hipLaunchKernelGGL((sqllm_attn_combine_kernel<64, __bf16>), grid, dim3(64), 0, stream, k);
-    else hipLaunchKernelGGL((sqllm_attn_combine_kernel<64, _Float16>), grid, dim3(64), 0, stream, k);
-  } else {
-    if (bf16) hipLaunchKernelGGL((sqllm_attn_combine_kernel<128, __bf16>), grid, dim3(128), 0, stream, k);
-    else hipLaunchKernelGGL((sqllm_attn_combine_kernel<128, _Float16>), grid, dim3(128), 0, stream, k);
-  }
-  return hipGetLastError();
-}
-
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_attn_decode_registered = (g_launch_attn_decode = launch_attn_decode, g_launch_attn_combine = launch_attn_combine, true);
+// the host layer reaches the launcher through its slot of g_launch_attn (sqllm_kernels.h), so that it links without this file too
+static const bool g_attn_decode_registered = (g_launch_attn[kAttnDecode] = launch_attn<AttnDecodeTag>, g_launch_attn_combine = launch_attn_combine_rows, true);
 
 }  // namespace sqllm

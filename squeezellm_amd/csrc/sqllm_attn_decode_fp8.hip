@@ -1,6 +1,6 @@
 // sqllm_attn_decode_fp8.hip -- decode attention over a KV cache of 1-byte OCP e4m3fn elements with one fp32 scale per cache
 // (include/sqllm_hip.h: sqllm_attn_decode_fp8_f16 / _bf16; the suffix names the type of q and out).  The partial kernel of
-// sqllm_attn_decode.hip for bytes: the same phases, the same partitions of kAttnPartition keys, the same workspace, and --
+// sqllm_attn_decode.hip for bytes (its BODY is a copy, edited; helpers and the launch ladder are shared: sqllm_attn.h): the same phases, the same partitions of kAttnPartition keys, the same workspace, and --
 // with more than one partition -- the SAME combine kernel behind it, reached through g_launch_attn_combine (it does not see the
 // cache).  float(k) = k_scale * f32(byte): k_scale is folded into the score's scale on the host, so phase 1 multiplies raw
 // bytes' values; float(v) = v_scale * f32(byte): v_scale multiplies each partition's sum over the keys once per (head, d), in
@@ -26,77 +26,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sqllm_attn.h"
 #include "sqllm_decode.h"
 #include "sqllm_kernels.h"
 
 namespace sqllm {
 
-constexpr int kAttnFp8Threads = 256;
-constexpr int kAttnFp8Unroll = 4;  // 16-byte loads in flight per lane before the first use
-static_assert(kAttnPartition == kAttnFp8Threads, "phase 0 resolves one key per thread");
-
-// 16 bytes that are aligned to one byte only
-struct __attribute__((packed, aligned(1))) Bytes16 {
-  uint32_t w[4];
-};
-// 16 bytes of 16-bit elements that are aligned to their elements only (q)
-struct __attribute__((packed, aligned(2))) Halves8 {
-  uint32_t w[4];
-};
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// 16 e4m3fn bytes as fp32 (a NaN byte is a NaN)
-__device__ __forceinline__ void widen_e4m3(const Bytes16& p, float (&f)[16]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)p.w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)p.w[i], true);
-    f[4 * i] = lo[0];
-    f[4 * i + 1] = lo[1];
-    f[4 * i + 2] = hi[0];
-    f[4 * i + 3] = hi[1];
-  }
-}
-
-template <typename OT>
-__device__ __forceinline__ void widen_q8(const Halves8& p, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (std::is_same<OT, __bf16>::value) {
-      f[2 * i] = __builtin_bit_cast(float, p.w[i] << 16);
-      f[2 * i + 1] = __builtin_bit_cast(float, p.w[i] & 0xffff0000u);
-    } else {
-      f[2 * i] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] & 0xffffu));
-      f[2 * i + 1] = (float)__builtin_bit_cast(_Float16, (unsigned short)(p.w[i] >> 16));
-    }
-  }
-}
-
-// the sum over the LPK lanes of a key, in every one of them (a + b and b + a: the same bits on both sides of each exchange)
-template <int LPK>
-__device__ __forceinline__ float key_sum_fp8(float v) {
-  static_assert(LPK == 4 || LPK == 8, "head_dim 64 or 128");
-  v += dpp_f32<0xB1, 0xf>(v);  // quad_perm [1,0,3,2]
-  v += dpp_f32<0x4E, 0xf>(v);  // quad_perm [2,3,0,1]
-  if constexpr (LPK == 8) v += dpp_f32<0x141, 0xf>(v);  // row_half_mirror: the other quad of the 8 lanes
-  return v;
-}
-
-__device__ __forceinline__ float wave_max_fp8(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
+// (the lane helpers of the byte caches and the launch ladder: sqllm_attn.h)
 
 template <int D, int GC, typename OT>
-__global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(const AttnArgs a, const float v_scale) {
+__global__ void __launch_bounds__(kAttnThreads) sqllm_attn_decode_fp8_kernel(const AttnArgs a, const float v_scale) {
   constexpr int P = kAttnPartition;
   constexpr int E = 16;              // elements (bytes) per lane and key
   constexpr int LPK = D / E;         // lanes per key
   constexpr int KPW = 64 / LPK;      // keys per wave instruction
   constexpr int KPS = KPW * 4;       // keys per step of the workgroup
   constexpr int STEPS = P / KPS;
-  constexpr int U = kAttnFp8Unroll;
+  constexpr int U = kAttnUnroll;
   constexpr int HC = GC < 2 ? GC : 2;          // heads per round of the key-lane exchange
   constexpr int R = (GC + LPK - 1) / LPK;      // heads whose score one lane of a key stores
   static_assert(STEPS % U == 0, "whole unrolled rounds");
@@ -117,7 +63,7 @@ __global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(
   if (len <= 0 || len > a.capacity) {
     if (single) {  // (otherwise the combine writes these rows)
       const OT c = len <= 0 ? (OT)0.0f : (OT)__builtin_nanf("");
-      for (int i = tid; i < g * D; i += kAttnFp8Threads) out[i] = c;
+      for (int i = tid; i < g * D; i += kAttnThreads) out[i] = c;
     }
     return;
   }
@@ -135,9 +81,9 @@ __global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(
     if (__syncthreads_or(bad)) {  // NaN, and nothing of the caches is read
       const float nan = __builtin_nanf("");
       if (single) {
-        for (int i = tid; i < g * D; i += kAttnFp8Threads) out[i] = (OT)nan;
+        for (int i = tid; i < g * D; i += kAttnThreads) out[i] = (OT)nan;
       } else {
-        for (int i = tid; i < g * D; i += kAttnFp8Threads) {
+        for (int i = tid; i < g * D; i += kAttnThreads) {
           const long long at = ((long long)b * a.n_q_heads + hk * g + i / D) * a.n_parts + part;
           a.ws_acc[at * D + i % D] = nan;
           if (i % D == 0) {
@@ -159,8 +105,8 @@ __global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(
 #pragma unroll
     for (int h = 0; h < GC; ++h) {
       if (h < g) {
-        widen_q8<OT>(*reinterpret_cast<const Halves8*>(q + h * D), qf[h]);
-        widen_q8<OT>(*reinterpret_cast<const Halves8*>(q + h * D + 8), qf[h] + 8);
+        widen8<OT>(*reinterpret_cast<const Packed8*>(q + h * D), qf[h]);
+        widen8<OT>(*reinterpret_cast<const Packed8*>(q + h * D + 8), qf[h] + 8);
       } else {
 #pragma unroll
         for (int j = 0; j < E; ++j) qf[h][j] = 0.0f;
@@ -209,7 +155,7 @@ __global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(
       s[i] = kl < n_valid ? sc[h][kl] : -__builtin_inff();
       m = fmaxf(m, s[i]);
     }
-    m = wave_max_fp8(m);
+    m = wave_max(m);
     float l = 0.0f;
 #pragma unroll
     for (int i = 0; i < P / 64; ++i) {
@@ -274,7 +220,7 @@ __global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(
         at[i] = f32x4{acc[h0 + hh][4 * i], acc[h0 + hh][4 * i + 1], acc[h0 + hh][4 * i + 2], acc[h0 + hh][4 * i + 3]};
     }
     __syncthreads();
-    for (int i = tid; i < HC * D; i += kAttnFp8Threads) {
+    for (int i = tid; i < HC * D; i += kAttnThreads) {
       const int hh = i / D, d = i % D, h = h0 + hh;
       if (h >= g) break;
       float t = red[0][hh][d];
@@ -295,38 +241,13 @@ __global__ void __launch_bounds__(kAttnFp8Threads) sqllm_attn_decode_fp8_kernel(
   }
 }
 
-template <int D, int GC, typename OT>
-static hipError_t launch_attn_fp8_inst(const AttnArgs& k, float v_scale, int n_kv_heads, int batch, bool bf16, hipStream_t stream) {
-  if (k.n_parts > 1 && !g_launch_attn_combine) return hipErrorNotSupported;  // (a missing kernel is an error, before anything is launched)
-  hipLaunchKernelGGL((sqllm_attn_decode_fp8_kernel<D, GC, OT>), dim3(k.n_parts, n_kv_heads, batch), dim3(kAttnFp8Threads), 0, stream, k, v_scale);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || k.n_parts == 1) return e;
-  return g_launch_attn_combine(k, D, bf16, batch, stream);
-}
+struct AttnDecodeFp8Tag : AttnOneQuery {  // (no combine of its own: g_launch_attn_combine, the 16-bit file's)
+  static constexpr bool fp8 = true;
+  template <int D, int GC, typename OT>
+  static auto kernel() { return sqllm_attn_decode_fp8_kernel<D, GC, OT>; }
+};
 
-template <int D, typename OT>
-static hipError_t launch_attn_fp8_group(const AttnArgs& k, float v_scale, int n_kv_heads, int batch, bool bf16, hipStream_t stream) {
-  switch (k.group) {
-    case 1: return launch_attn_fp8_inst<D, 1, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
-    case 2: return launch_attn_fp8_inst<D, 2, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
-    case 3: case 4: return launch_attn_fp8_inst<D, 4, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
-    default: return launch_attn_fp8_inst<D, 8, OT>(k, v_scale, n_kv_heads, batch, bf16, stream);
-  }
-}
-
-static hipError_t launch_attn_decode_fp8(const AttnDecode& d, hipStream_t stream) {
-  if ((d.head_dim != 64 && d.head_dim != 128) || d.n_kv_heads < 1 || d.n_q_heads % d.n_kv_heads || d.n_q_heads / d.n_kv_heads > 8 ||
-      d.batch < 1 || d.n_parts < 1)
-    return hipErrorInvalidValue;
-  const AttnArgs k = make_attn_args(d);
-  if (d.bf16)
-    return d.head_dim == 64 ? launch_attn_fp8_group<64, __bf16>(k, d.v_scale, d.n_kv_heads, d.batch, true, stream)
-                            : launch_attn_fp8_group<128, __bf16>(k, d.v_scale, d.n_kv_heads, d.batch, true, stream);
-  return d.head_dim == 64 ? launch_attn_fp8_group<64, _Float16>(k, d.v_scale, d.n_kv_heads, d.batch, false, stream)
-                          : launch_attn_fp8_group<128, _Float16>(k, d.v_scale, d.n_kv_heads, d.batch, false, stream);
-}
-
-// the host layer reaches the launcher through this hook (sqllm_kernels.h), so that it links without this file too
-static const bool g_attn_decode_fp8_registered = (g_launch_attn_decode_fp8 = launch_attn_decode_fp8, true);
+// the host layer reaches the launcher through its slot of g_launch_attn (sqllm_kernels.h), so that it links without this file too
+static const bool g_attn_decode_fp8_registered = (g_launch_attn[kAttnDecodeFp8] = launch_attn<AttnDecodeFp8Tag>, true);
 
 }  // namespace sqllm

@@ -17,12 +17,9 @@
 
 namespace sqllm {
 FrontLauncher g_launch_front[kFrontKinds] = {};  // each slot set by its kernel file (sqllm_linear_gated.hip ... sqllm_linear_qkv_norm_cache_fp8.hip)
-hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
-hipError_t (*g_launch_attn_append)(const AttnAppend& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
-hipError_t (*g_launch_attn_append_fp8)(const AttnAppend& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_append_fp8.hip
-hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
-hipError_t (*g_launch_attn_decode_fp8)(const AttnDecode& d, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode_fp8.hip
+AttnLauncher g_launch_attn[kAttnKinds] = {};  // each slot set by its kernel file (sqllm_attn_decode.hip ... sqllm_attn_append_fp8.hip)
 hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
+hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
 }
 
 namespace sqllm_host {
@@ -1554,15 +1551,23 @@ int64_t sqllm_attn_decode_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
   return (int64_t)batch * n_q_heads * attn_parts(max_blocks, block_size) * (head_dim + 2) * 4;
 }
 
-// `a8` (sqllm_attn_decode_fp8_*): the descriptor the fields of `a` were taken from -- the caches hold 1-byte e4m3fn elements,
-// their strides and extents count bytes and they need no alignment; its scales are judged last.
-// `q_len` >= 0 (sqllm_attn_append_*): a->batch counts sequences of q_len rows each, `q_lens` (or NULL) their real tokens; -1: the
-// one-query entries.
-static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream, bool bf16, const sqllm_attn_decode_fp8* a8 = nullptr,
-                              const int32_t* q_lens = nullptr, int32_t q_len = -1) {
-  const bool append = q_len != -1;
-  const int celem = a8 ? 1 : 2;  // bytes per cache element
-  if (!a || !a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || !a->workspace) return SQLLM_E_NULL;
+// The eight attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
+// follows them is passed on by each entry:
+//   `kv_scales` (the fp8 entries): {k_scale, v_scale} of the descriptor -- the caches hold 1-byte e4m3fn elements, their strides
+//     and extents count bytes and they need no alignment; the scales are judged last.  NULL: 16-bit caches.
+//   `tokens` (sqllm_attn_append_*): lead.batch counts sequences of q_len rows each, `q_lens` (or NULL) their real tokens.  NULL:
+//     the one-query entries -- so a q_len below 1 in an append descriptor is a count < 1, never the one-query call.
+struct AttnTokensTail {
+  const int32_t* q_lens;
+  int32_t q_len;
+};
+static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, bool bf16, const float* kv_scales, const AttnTokensTail* tokens) {
+  const sqllm_attn_decode* const a = &lead;
+  const bool append = tokens != nullptr;
+  const int32_t q_len = append ? tokens->q_len : 0;
+  const int32_t* const q_lens = append ? tokens->q_lens : nullptr;
+  const int celem = kv_scales ? 1 : 2;  // bytes per cache element
+  if (!a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || !a->workspace) return SQLLM_E_NULL;
   const int64_t D = a->head_dim;
   if (a->batch < 1 || a->n_q_heads < 1 || a->n_kv_heads < 1 || D < 1 || a->n_slots < 1 || a->block_size < 1 || a->max_blocks < 1 ||
       a->table_stride < 1 || (append && q_len < 1))
@@ -1592,123 +1597,99 @@ static int launch_attn_decode(const sqllm_attn_decode* a, sqllm_stream_t stream,
       return SQLLM_E_SHAPE;
   if (ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
   if (((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->out)) & 1u) != 0 ||
-      (!a8 && ((reinterpret_cast<uintptr_t>(a->k_cache) | reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0) ||
+      (!kv_scales && ((reinterpret_cast<uintptr_t>(a->k_cache) | reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0) ||
       (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0)
     return SQLLM_E_ALIGN;
   float scale = a->scale;
-  if (a8) {
-    if (!fp8_scale_ok(a8->k_scale) || !fp8_scale_ok(a8->v_scale)) return SQLLM_E_OPTION;
-    scale = a->scale * a8->k_scale;  // (rounded once, here)
+  if (kv_scales) {
+    if (!fp8_scale_ok(kv_scales[0]) || !fp8_scale_ok(kv_scales[1])) return SQLLM_E_OPTION;
+    scale = a->scale * kv_scales[0];  // (rounded once, here)
     if (!__builtin_isfinite(scale)) return SQLLM_E_OPTION;
   }
-  sqllm::AttnDecode d;
-  d.q = a->q;
-  d.out = a->out;
-  d.k_cache = a->k_cache;
-  d.v_cache = a->v_cache;
-  d.block_table = a->block_table;
-  d.seq_lens = a->seq_lens;
-  d.workspace = a->workspace;
-  d.batch = a->batch;
-  d.n_q_heads = a->n_q_heads;
-  d.n_kv_heads = a->n_kv_heads;
-  d.head_dim = a->head_dim;
-  d.n_slots = a->n_slots;
-  d.block_size = a->block_size;
-  d.table_stride = a->table_stride;
-  d.capacity = (int)attn_capacity(a->max_blocks, a->block_size);
-  d.n_parts = (int)attn_parts(a->max_blocks, a->block_size);
-  d.slot_stride = a->slot_stride;
-  d.head_stride = a->head_stride;
-  d.q_stride = a->q_stride;
-  d.out_stride = a->out_stride;
-  d.scale = scale;
-  d.bf16 = bf16;
-  d.v_scale = a8 ? a8->v_scale : 1.0f;
-  if (append) {
-    sqllm::AttnAppend p;
-    p.d = d;
-    p.q_lens = q_lens;
-    p.q_len = q_len;
-    const auto launch_append = a8 ? sqllm::g_launch_attn_append_fp8 : sqllm::g_launch_attn_append;
-    return static_cast<int>(launch_append ? launch_append(p, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
-  }
-  const auto launch = a8 ? sqllm::g_launch_attn_decode_fp8 : sqllm::g_launch_attn_decode;
-  const hipError_t e = launch ? launch(d, static_cast<hipStream_t>(stream)) : hipErrorNotSupported;
-  return static_cast<int>(e);
+  sqllm::AttnCall c;
+  c.q = a->q;
+  c.out = a->out;
+  c.k_cache = a->k_cache;
+  c.v_cache = a->v_cache;
+  c.block_table = a->block_table;
+  c.seq_lens = a->seq_lens;
+  c.workspace = a->workspace;
+  c.batch = a->batch;
+  c.n_q_heads = a->n_q_heads;
+  c.n_kv_heads = a->n_kv_heads;
+  c.head_dim = a->head_dim;
+  c.n_slots = a->n_slots;
+  c.block_size = a->block_size;
+  c.table_stride = a->table_stride;
+  c.capacity = (int)attn_capacity(a->max_blocks, a->block_size);
+  c.n_parts = (int)attn_parts(a->max_blocks, a->block_size);
+  c.slot_stride = a->slot_stride;
+  c.head_stride = a->head_stride;
+  c.q_stride = a->q_stride;
+  c.out_stride = a->out_stride;
+  c.scale = scale;
+  c.bf16 = bf16;
+  c.fp8 = kv_scales != nullptr;
+  c.v_scale = kv_scales ? kv_scales[1] : 1.0f;
+  c.q_lens = q_lens;
+  c.q_len = q_len;  // (0: one query per sequence; an append call has passed q_len >= 1 above)
+  const sqllm::AttnLauncher launch = sqllm::g_launch_attn[sqllm::attn_kind(c)];
+  return static_cast<int>(launch ? launch(c, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
 }
 
-// the fp8 entries: the fields the two descriptors share, then the checks and the launch above
-static int launch_attn_decode_fp8(const sqllm_attn_decode_fp8* a8, sqllm_stream_t stream, bool bf16) {
-  if (!a8) return SQLLM_E_NULL;
-  sqllm_attn_decode a;
-  a.q = a8->q;
-  a.out = a8->out;
-  a.k_cache = a8->k_cache;
-  a.v_cache = a8->v_cache;
-  a.block_table = a8->block_table;
-  a.seq_lens = a8->seq_lens;
-  a.batch = a8->batch;
-  a.n_q_heads = a8->n_q_heads;
-  a.n_kv_heads = a8->n_kv_heads;
-  a.head_dim = a8->head_dim;
-  a.n_slots = a8->n_slots;
-  a.block_size = a8->block_size;
-  a.max_blocks = a8->max_blocks;
-  a.table_stride = a8->table_stride;
-  a.slot_stride = a8->slot_stride;
-  a.head_stride = a8->head_stride;
-  a.q_stride = a8->q_stride;
-  a.out_stride = a8->out_stride;
-  a.scale = a8->scale;
-  a.workspace = a8->workspace;
-  return launch_attn_decode(&a, stream, bf16, a8);
-}
-int sqllm_attn_decode_fp8_f16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream) { return launch_attn_decode_fp8(a, stream, false); }
-int sqllm_attn_decode_fp8_bf16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream) { return launch_attn_decode_fp8(a, stream, true); }
+// every leading field of the three longer descriptors sits where sqllm_attn_decode has it, so its first bytes ARE one
+#define SQLLM_ATTN_LEAD_AT(S, F) (offsetof(S, F) == offsetof(sqllm_attn_decode, F) && sizeof(S::F) == sizeof(sqllm_attn_decode::F))
+#define SQLLM_ATTN_LEAD(S)                                                                                                        \
+  static_assert(SQLLM_ATTN_LEAD_AT(S, q) && SQLLM_ATTN_LEAD_AT(S, out) && SQLLM_ATTN_LEAD_AT(S, k_cache) && SQLLM_ATTN_LEAD_AT(S, v_cache) && \
+                    SQLLM_ATTN_LEAD_AT(S, block_table) && SQLLM_ATTN_LEAD_AT(S, seq_lens) && SQLLM_ATTN_LEAD_AT(S, batch) &&       \
+                    SQLLM_ATTN_LEAD_AT(S, n_q_heads) && SQLLM_ATTN_LEAD_AT(S, n_kv_heads) && SQLLM_ATTN_LEAD_AT(S, head_dim) &&    \
+                    SQLLM_ATTN_LEAD_AT(S, n_slots) && SQLLM_ATTN_LEAD_AT(S, block_size) && SQLLM_ATTN_LEAD_AT(S, max_blocks) &&    \
+                    SQLLM_ATTN_LEAD_AT(S, table_stride) && SQLLM_ATTN_LEAD_AT(S, slot_stride) && SQLLM_ATTN_LEAD_AT(S, head_stride) && \
+                    SQLLM_ATTN_LEAD_AT(S, q_stride) && SQLLM_ATTN_LEAD_AT(S, out_stride) && SQLLM_ATTN_LEAD_AT(S, scale) &&        \
+                    SQLLM_ATTN_LEAD_AT(S, workspace) && offsetof(S, workspace) + sizeof(void*) == sizeof(sqllm_attn_decode),       \
+                #S " begins with the fields of sqllm_attn_decode")
+SQLLM_ATTN_LEAD(sqllm_attn_decode_fp8);
+SQLLM_ATTN_LEAD(sqllm_attn_append);
+SQLLM_ATTN_LEAD(sqllm_attn_append_fp8);
+#undef SQLLM_ATTN_LEAD
+#undef SQLLM_ATTN_LEAD_AT
 
-int sqllm_attn_decode_f16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, false); }
-int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream) { return launch_attn_decode(a, stream, true); }
-
-// Several new tokens per sequence (sqllm_attn_append_*): the one-query descriptor out of the leading fields, then the checks
-// and the launch above with the two fields behind them.  A negative q_len is a count < 1, not the one-query call.
+// the leading fields of a descriptor, by copy (not through a pointer of another struct's type)
 extern "C++" template <typename A>
-static void attn_append_fields(const A* p, sqllm_attn_decode* a) {
-  a->q = p->q;
-  a->out = p->out;
-  a->k_cache = p->k_cache;
-  a->v_cache = p->v_cache;
-  a->block_table = p->block_table;
-  a->seq_lens = p->seq_lens;
-  a->batch = p->batch;
-  a->n_q_heads = p->n_q_heads;
-  a->n_kv_heads = p->n_kv_heads;
-  a->head_dim = p->head_dim;
-  a->n_slots = p->n_slots;
-  a->block_size = p->block_size;
-  a->max_blocks = p->max_blocks;
-  a->table_stride = p->table_stride;
-  a->slot_stride = p->slot_stride;
-  a->head_stride = p->head_stride;
-  a->q_stride = p->q_stride;
-  a->out_stride = p->out_stride;
-  a->scale = p->scale;
-  a->workspace = p->workspace;
+static sqllm_attn_decode attn_lead(const A* p) {
+  sqllm_attn_decode lead;
+  memcpy(&lead, p, sizeof(lead));
+  return lead;
 }
-static int launch_attn_append(const sqllm_attn_append* p, sqllm_stream_t stream, bool bf16) {
-  if (!p) return SQLLM_E_NULL;
-  sqllm_attn_decode a;
-  attn_append_fields(p, &a);
-  return launch_attn_decode(&a, stream, bf16, nullptr, p->q_lens, p->q_len < 0 ? 0 : p->q_len);
+extern "C++" template <typename A>
+static int launch_attn_fp8(const A* p, sqllm_stream_t stream, bool bf16, const AttnTokensTail* tokens) {
+  const float kv_scales[2] = {p->k_scale, p->v_scale};
+  return launch_attn(attn_lead(p), stream, bf16, kv_scales, tokens);
 }
-static int launch_attn_append_fp8(const sqllm_attn_append_fp8* p, sqllm_stream_t stream, bool bf16) {
-  if (!p) return SQLLM_E_NULL;
-  sqllm_attn_decode a;
-  attn_append_fields(p, &a);
-  sqllm_attn_decode_fp8 a8 = {};
-  a8.k_scale = p->k_scale;
-  a8.v_scale = p->v_scale;
-  return launch_attn_decode(&a, stream, bf16, &a8, p->q_lens, p->q_len < 0 ? 0 : p->q_len);
+extern "C++" template <typename A>
+static AttnTokensTail attn_tokens(const A* p) { return {p->q_lens, p->q_len}; }
+
+int sqllm_attn_decode_f16(const sqllm_attn_decode* a, sqllm_stream_t stream) {
+  return a ? launch_attn(*a, stream, false, nullptr, nullptr) : SQLLM_E_NULL;
+}
+int sqllm_attn_decode_bf16(const sqllm_attn_decode* a, sqllm_stream_t stream) {
+  return a ? launch_attn(*a, stream, true, nullptr, nullptr) : SQLLM_E_NULL;
+}
+int sqllm_attn_decode_fp8_f16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream) {
+  return a ? launch_attn_fp8(a, stream, false, nullptr) : SQLLM_E_NULL;
+}
+int sqllm_attn_decode_fp8_bf16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream) {
+  return a ? launch_attn_fp8(a, stream, true, nullptr) : SQLLM_E_NULL;
+}
+static int launch_attn_append(const sqllm_attn_append* a, sqllm_stream_t stream, bool bf16) {
+  if (!a) return SQLLM_E_NULL;
+  const AttnTokensTail t = attn_tokens(a);
+  return launch_attn(attn_lead(a), stream, bf16, nullptr, &t);
+}
+static int launch_attn_append_fp8(const sqllm_attn_append_fp8* a, sqllm_stream_t stream, bool bf16) {
+  if (!a) return SQLLM_E_NULL;
+  const AttnTokensTail t = attn_tokens(a);
+  return launch_attn_fp8(a, stream, bf16, &t);
 }
 int sqllm_attn_append_f16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_append(a, stream, false); }
 int sqllm_attn_append_bf16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_append(a, stream, true); }

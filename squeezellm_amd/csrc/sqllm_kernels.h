@@ -205,10 +205,13 @@ inline FrontKind front_kind(const FrontCall& f) {
 }
 typedef hipError_t (*FrontLauncher)(int bits, const LaunchArgs& a, const FrontCall& f, hipStream_t stream);
 extern FrontLauncher g_launch_front[kFrontKinds];
-// decode attention over that cache (sqllm_attn_decode_f16 / _bf16), on the kernels of sqllm_attn_decode.hip: the partials of
-// every (row, kv head, partition of kAttnPartition keys), then -- with more than one partition -- the combine.  A hook, as above.
+// Decode attention over that cache (sqllm_attn_decode_* / sqllm_attn_append_*, 16-bit and e4m3fn caches): the partials of every
+// (row, kv head, partition of kAttnPartition keys), then -- with more than one partition -- the combine.  Four kinds, each one
+// kernel file that registers its launcher in g_launch_attn when it is linked in (a table as g_launch_front above: defined all
+// null in sqllm_capi.hip, a null slot is hipErrorNotSupported); the launchers are one ladder, launch_attn<TAG> of sqllm_attn.h.
 constexpr int kAttnPartition = 256;  // keys per partition (SQLLM_ATTN_PARTITION of include/sqllm_hip.h)
-struct AttnDecode {
+// one call, as the host layer validated it: HOST fields only, never device data
+struct AttnCall {
   const void* q;
   void* out;
   const void* k_cache;
@@ -218,17 +221,25 @@ struct AttnDecode {
   void* workspace;         // n_parts x (head_dim + 2) floats per (row, query head); contents irrelevant
   int batch, n_q_heads, n_kv_heads, head_dim, n_slots, block_size, table_stride;
   int capacity;            // min(max_blocks * block_size, INT32_MAX) keys
-  int n_parts;             // ceil(capacity / kAttnPartition): HOST fields only, never device data
-  int64_t slot_stride, head_stride, q_stride, out_stride;  // in elements
+  int n_parts;             // ceil(capacity / kAttnPartition)
+  int64_t slot_stride, head_stride, q_stride, out_stride;  // in elements (the first two in bytes with fp8)
   float scale;
   bool bf16;
-  float v_scale;           // the fp8 entries only (scale then holds scale * k_scale, rounded once)
+  bool fp8;                // the caches hold 1-byte e4m3fn elements: scale then holds scale * k_scale, rounded once, and
+  float v_scale;           // ... v_scale the cache's (1 otherwise)
+  // several new tokens per sequence (sqllm_attn_append_*): `batch` counts SEQUENCES; q, out and the workspace have batch * q_len rows
+  const int* q_lens;       // int32 [batch], device memory, or null: q_len real tokens everywhere
+  int q_len;               // rows per sequence, 1 to 16; 0: the one-query entries
 };
-extern hipError_t (*g_launch_attn_decode)(const AttnDecode& d, hipStream_t stream);
-// ... over a cache of 1-byte e4m3fn elements (sqllm_attn_decode_fp8_f16 / _bf16), on the partial kernels of sqllm_attn_decode_fp8.hip;
-// strides in bytes.  A hook, as above.
-extern hipError_t (*g_launch_attn_decode_fp8)(const AttnDecode& d, hipStream_t stream);
+enum AttnKind { kAttnDecode, kAttnDecodeFp8, kAttnAppend, kAttnAppendFp8, kAttnKinds };
+inline AttnKind attn_kind(const AttnCall& c) {
+  if (c.q_len) return c.fp8 ? kAttnAppendFp8 : kAttnAppend;
+  return c.fp8 ? kAttnDecodeFp8 : kAttnDecode;
+}
+typedef hipError_t (*AttnLauncher)(const AttnCall& c, hipStream_t stream);
+extern AttnLauncher g_launch_attn[kAttnKinds];
 // The kernels' argument (sqllm_attn_decode.hip: the partials and the combine; sqllm_attn_decode_fp8.hip: the partials over bytes).
+// Its layout is part of the generated code: field order and types stay.
 struct AttnArgs {
   const void* q;
   void* out;
@@ -245,44 +256,7 @@ struct AttnArgs {
   int n_parts;
   float scale;
 };
-inline AttnArgs make_attn_args(const AttnDecode& d) {
-  AttnArgs k;
-  k.q = d.q;
-  k.out = d.out;
-  k.k_cache = d.k_cache;
-  k.v_cache = d.v_cache;
-  k.block_table = d.block_table;
-  k.seq_lens = d.seq_lens;
-  k.ws_acc = static_cast<float*>(d.workspace);
-  k.ws_ml = k.ws_acc + (long long)d.batch * d.n_q_heads * d.n_parts * d.head_dim;
-  k.q_stride = d.q_stride;
-  k.out_stride = d.out_stride;
-  k.slot_stride = (unsigned)d.slot_stride;
-  k.head_stride = (unsigned)d.head_stride;
-  k.n_q_heads = d.n_q_heads;
-  k.group = d.n_q_heads / d.n_kv_heads;
-  k.n_slots = d.n_slots;
-  k.block_size = d.block_size;
-  k.table_stride = d.table_stride;
-  k.capacity = d.capacity;
-  k.n_parts = d.n_parts;
-  k.scale = d.scale;
-  return k;
-}
-// the combine of sqllm_attn_decode.hip (it does not see the cache): one workgroup of head_dim threads per (query head, row) over
-// the partials in the workspace.  A hook that file sets, so that the byte caches' partials are followed by the same kernel.
-extern hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
-// decode attention for q_len new tokens per sequence (sqllm_attn_append_f16 / _bf16, _fp8_f16 / _fp8_bf16), on the kernels of
-// sqllm_attn_append.hip and sqllm_attn_append_fp8.hip: K and V of a sequence are read once for all its new tokens.  `d.batch`
-// counts SEQUENCES; q, out and the workspace have d.batch * q_len rows.  Hooks, as above.
-struct AttnAppend {
-  AttnDecode d;
-  const int* q_lens;  // int32 [d.batch], device memory, or null: q_len real tokens everywhere
-  int q_len;          // rows per sequence, 1 to 16: a HOST field
-};
-extern hipError_t (*g_launch_attn_append)(const AttnAppend& d, hipStream_t stream);
-extern hipError_t (*g_launch_attn_append_fp8)(const AttnAppend& d, hipStream_t stream);
-// The append kernels' argument: AttnArgs' fields (the kernels are copies of their one-query siblings) and the tokens.
+// The append kernels' argument: AttnArgs' fields (the kernel bodies are copies of their one-query siblings) and the tokens.
 struct AttnAppendArgs {
   const void* q;
   void* out;
@@ -302,35 +276,42 @@ struct AttnAppendArgs {
   int q_len;
   float scale;
 };
-inline AttnAppendArgs make_attn_append_args(const AttnAppend& p) {
-  const AttnDecode& d = p.d;
-  AttnAppendArgs k;
-  k.q = d.q;
-  k.out = d.out;
-  k.k_cache = d.k_cache;
-  k.v_cache = d.v_cache;
-  k.block_table = d.block_table;
-  k.seq_lens = d.seq_lens;
-  k.q_lens = p.q_lens;
-  k.ws_acc = static_cast<float*>(d.workspace);
-  k.ws_ml = k.ws_acc + (long long)d.batch * p.q_len * d.n_q_heads * d.n_parts * d.head_dim;
-  k.q_stride = d.q_stride;
-  k.out_stride = d.out_stride;
-  k.slot_stride = (unsigned)d.slot_stride;
-  k.head_stride = (unsigned)d.head_stride;
-  k.n_q_heads = d.n_q_heads;
-  k.group = d.n_q_heads / d.n_kv_heads;
-  k.n_slots = d.n_slots;
-  k.block_size = d.block_size;
-  k.table_stride = d.table_stride;
-  k.capacity = d.capacity;
-  k.n_parts = d.n_parts;
-  k.batch = d.batch;
-  k.q_len = p.q_len;
-  k.scale = d.scale;
+inline void attn_token_args(AttnArgs&, const AttnCall&) {}
+inline void attn_token_args(AttnAppendArgs& k, const AttnCall& c) {
+  k.q_lens = c.q_lens;
+  k.batch = c.batch;
+  k.q_len = c.q_len;
+}
+template <typename ARGS>
+inline ARGS make_attn_args(const AttnCall& c) {
+  ARGS k;
+  k.q = c.q;
+  k.out = c.out;
+  k.k_cache = c.k_cache;
+  k.v_cache = c.v_cache;
+  k.block_table = c.block_table;
+  k.seq_lens = c.seq_lens;
+  k.ws_acc = static_cast<float*>(c.workspace);
+  k.ws_ml = k.ws_acc + (long long)c.batch * (c.q_len ? c.q_len : 1) * c.n_q_heads * c.n_parts * c.head_dim;
+  k.q_stride = c.q_stride;
+  k.out_stride = c.out_stride;
+  k.slot_stride = (unsigned)c.slot_stride;
+  k.head_stride = (unsigned)c.head_stride;
+  k.n_q_heads = c.n_q_heads;
+  k.group = c.n_q_heads / c.n_kv_heads;
+  k.n_slots = c.n_slots;
+  k.block_size = c.block_size;
+  k.table_stride = c.table_stride;
+  k.capacity = c.capacity;
+  k.n_parts = c.n_parts;
+  k.scale = c.scale;
+  attn_token_args(k, c);
   return k;
 }
-// the combine of sqllm_attn_append.hip: the one above with every row's own length.  A hook that file sets, for the byte caches.
+// The combines (they do not see the cache): one workgroup of head_dim threads per (query head, row) over the partials in the
+// workspace -- sqllm_attn_decode.hip's, and sqllm_attn_append.hip's with every row's own length.  Hooks those files set, so that
+// the byte caches' partials are followed by the same kernels.
+extern hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
 extern hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)

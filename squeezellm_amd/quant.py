@@ -1044,10 +1044,26 @@ def fuse_qkv_rope(module: nn.Module, q: str = "q_proj", k: str = "k_proj", v: st
     return n
 
 
-_ATTN_ENTRY = {torch.float16: "sqllm_attn_decode_f16", torch.bfloat16: "sqllm_attn_decode_bf16"}
-_ATTN_FP8_ENTRY = {torch.float16: "sqllm_attn_decode_fp8_f16", torch.bfloat16: "sqllm_attn_decode_fp8_bf16"}
-_ATTN_APPEND_ENTRY = {torch.float16: "sqllm_attn_append_f16", torch.bfloat16: "sqllm_attn_append_bf16"}
-_ATTN_APPEND_FP8_ENTRY = {torch.float16: "sqllm_attn_append_fp8_f16", torch.bfloat16: "sqllm_attn_append_fp8_bf16"}
+# The four kinds of DecodeAttention._launch, kind = 2 * (several new tokens per sequence) + (fp8 cache): the descriptor and the
+# entry of each dtype
+_ATTN_KINDS = (
+    (_lib.SqllmAttnDecode, {torch.float16: "sqllm_attn_decode_f16", torch.bfloat16: "sqllm_attn_decode_bf16"}),
+    (_lib.SqllmAttnDecodeFp8, {torch.float16: "sqllm_attn_decode_fp8_f16", torch.bfloat16: "sqllm_attn_decode_fp8_bf16"}),
+    (_lib.SqllmAttnAppend, {torch.float16: "sqllm_attn_append_f16", torch.bfloat16: "sqllm_attn_append_bf16"}),
+    (_lib.SqllmAttnAppendFp8, {torch.float16: "sqllm_attn_append_fp8_f16", torch.bfloat16: "sqllm_attn_append_fp8_bf16"}),
+)
+_ATTN_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _int32_vector(t: torch.Tensor) -> torch.Tensor:
+    """`t` as a contiguous int32 vector; what already is one is returned as it is, so that a captured graph follows it."""
+    if t.dim() != 1:
+        t = t.reshape(-1)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)  # (a kernel)
+    return t if t.is_contiguous() else t.contiguous()
+
+
 ATTN_PARTITION = _lib.ATTN_PARTITION  # keys per partition of the decode attention's kernel (SQLLM_ATTN_PARTITION)
 ATTN_APPEND_MAX_Q_LEN = 16  # new tokens per sequence the append kernels serve
 
@@ -1234,93 +1250,15 @@ class DecodeAttention(nn.Module):
         if k_cache.stride(0) < D or (k_cache.stride(1) < D and H > 1):
             raise ValueError(f"the strides of a cache view must be at least head_dim = {D}, got {k_cache.stride()}")
 
-    def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
-                out=None, block_size=None, k_scale=None, v_scale=None, q_len=None, q_lens=None) -> torch.Tensor:
-        if q_len is not None or q_lens is not None:
-            return self._forward_append(q, k_cache, v_cache, block_table, seq_lens, out, block_size, k_scale, v_scale, q_len, q_lens)
-        D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
-        W = HQ * D
+    def _check_operands(self, q, k_cache, v_cache, block_table, seq_lens, out, block_size, k_scale, v_scale, T, q_lens):
+        """Every operand check of forward, for one query per sequence (T None) and for T new tokens per sequence.
+        -> (q2 [rows, W] with rows at least W apart, rows, block size, fp8 cache?, k_scale, v_scale).  The number of sequences is
+        block_table.shape[0] from here on: rows for one query per sequence, rows / T otherwise."""
+        D, H = self.head_dim, self.n_kv_heads
+        W = self.n_heads * D
         if q.shape[-1] != W or q.stride(-1) != 1:
             raise ValueError(f"q must be [..., {W}] with a contiguous last dimension, got {tuple(q.shape)} with strides {q.stride()}")
-        bs = self.block_size if block_size is None else int(block_size)
-        if bs is None or bs < 1:
-            raise ValueError("block_size must be given, at construction or per call, and be positive")
-        self._check_cache(q, k_cache, v_cache)
-        fp8 = k_cache.dtype in FP8_KV_DTYPES and k_cache.dtype != q.dtype
-        k_scale, v_scale = _check_fp8_scales(fp8, k_scale, v_scale)
-        if fp8 and not math.isfinite(float(torch.tensor(self.scale, dtype=torch.float32) * torch.tensor(k_scale, dtype=torch.float32))):
-            raise ValueError(f"scale * k_scale must be finite in fp32, got {self.scale} * {k_scale}")
-        lead = q.shape[:-1]
-        q2 = q if q.dim() == 2 else q.reshape(-1, W)
-        rows = q2.shape[0]
-        if rows < 1:
-            raise ValueError("q has no rows")
-        if (not isinstance(block_table, torch.Tensor) or block_table.dtype not in (torch.int32, torch.int64) or block_table.dim() != 2
-                or block_table.shape[0] != rows or block_table.shape[1] < 1 or block_table.device != q.device):
-            raise ValueError(f"block_table must be int32 (or int64) [{rows}, max_blocks] on {q.device}")
-        if not isinstance(seq_lens, torch.Tensor) or seq_lens.dtype not in (torch.int32, torch.int64) or seq_lens.numel() != rows or seq_lens.device != q.device:
-            raise ValueError(f"seq_lens must be {rows} int32 (or int64) values on {q.device}")
-        if out is not None:
-            if (not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or out.shape != (rows, W)
-                    or out.stride(1) != 1 or (rows > 1 and out.stride(0) < W)):
-                raise ValueError(f"out must be a {q.dtype} [{rows}, {W}] tensor on {q.device} with a contiguous last dimension")
-        if rows > 1 and q2.stride(0) < W:
-            q2 = q2.contiguous()
-        kernel = q.dtype in _ATTN_ENTRY and q.is_cuda and D in (64, 128) and HQ // H <= 8 and rows <= 64
-        if not kernel:
-            self.__dict__["_last_route"] = "fallback"
-            o = _torch_attn_decode(q2, k_cache, v_cache, block_table, seq_lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
-            if out is not None:
-                out.copy_(o)
-                return out
-            return o.reshape(*lead, W)
-        bt = block_table if block_table.dtype == torch.int32 else block_table.to(torch.int32)  # (a kernel)
-        if bt.stride(1) != 1 or (rows > 1 and bt.stride(0) < bt.shape[1]):
-            bt = bt.contiguous()
-        sl = seq_lens.reshape(-1)
-        if sl.dtype != torch.int32:
-            sl = sl.to(torch.int32)  # (a kernel)
-        if not sl.is_contiguous():
-            sl = sl.contiguous()
-        self.__dict__["_last_route"] = "attn_decode"
-        dev = q.get_device()
-        o = out if out is not None else torch.empty((rows, W), dtype=q.dtype, device=q.device)
-        stream = quant_cuda._raw_stream(dev)
-        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.attn_decode_workspace_bytes(rows, HQ, D, bt.shape[1], bs), q.device,
-                           self.GRAPH_WS_MAX_BYTES)
-        descs = self.__dict__.setdefault("_desc8" if fp8 else "_desc", {})
-        hit = descs.get((dev, stream))
-        if hit is None:
-            a = _lib.SqllmAttnDecodeFp8() if fp8 else _lib.SqllmAttnDecode()
-            hit = descs[(dev, stream)] = (a, ctypes.byref(a))
-        a, ref = hit
-        a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
-        a.block_table, a.seq_lens = bt.data_ptr(), sl.data_ptr()
-        a.batch, a.n_q_heads, a.n_kv_heads, a.head_dim = rows, HQ, H, D
-        a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, bt.shape[1]
-        a.table_stride = bt.stride(0) if rows > 1 else bt.shape[1]
-        a.slot_stride = k_cache.stride(0)
-        a.head_stride = k_cache.stride(1) if H > 1 else D  # (one head: its stride is anything, and never used)
-        a.q_stride = q2.stride(0) if rows > 1 else W
-        a.out_stride = o.stride(0) if rows > 1 else W
-        a.scale, a.workspace = self.scale, ws.data_ptr()
-        if fp8:
-            a.k_scale, a.v_scale = k_scale, v_scale
-        quant_cuda._launch(quant_cuda._fn((_ATTN_FP8_ENTRY if fp8 else _ATTN_ENTRY)[q.dtype]), dev, (ref,))
-        return o if out is not None else o.reshape(*lead, W)
-
-    def _forward_append(self, q, k_cache, v_cache, block_table, seq_lens, out, block_size, k_scale, v_scale, q_len, q_lens) -> torch.Tensor:
-        """forward(..., q_len=T, q_lens=None): T new tokens per sequence in one read of K and V (sqllm_attn_append_*)."""
-        D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
-        W = HQ * D
-        if q_len is None:
-            raise ValueError("q_lens needs q_len, the rows per sequence")
-        T = int(q_len)
-        if T < 1:
-            raise ValueError(f"q_len must be positive, got {q_len}")
-        if q.shape[-1] != W or q.stride(-1) != 1:
-            raise ValueError(f"q must be [..., {W}] with a contiguous last dimension, got {tuple(q.shape)} with strides {q.stride()}")
-        if q.dim() not in (2, 3) or (q.dim() == 3 and q.shape[1] != T):
+        if T is not None and (q.dim() not in (2, 3) or (q.dim() == 3 and q.shape[1] != T)):
             raise ValueError(f"q must be [batch * {T}, {W}] or [batch, {T}, {W}], got {tuple(q.shape)}")
         bs = self.block_size if block_size is None else int(block_size)
         if bs is None or bs < 1:
@@ -1330,85 +1268,115 @@ class DecodeAttention(nn.Module):
         k_scale, v_scale = _check_fp8_scales(fp8, k_scale, v_scale)
         if fp8 and not math.isfinite(float(torch.tensor(self.scale, dtype=torch.float32) * torch.tensor(k_scale, dtype=torch.float32))):
             raise ValueError(f"scale * k_scale must be finite in fp32, got {self.scale} * {k_scale}")
-        lead = q.shape[:-1]
         q2 = q if q.dim() == 2 else q.reshape(-1, W)
         rows = q2.shape[0]
-        if rows < 1 or rows % T:
-            raise ValueError(f"q must have a positive multiple of q_len = {T} rows, got {rows}")
-        batch = rows // T
+        if T is None:
+            if rows < 1:
+                raise ValueError("q has no rows")
+            batch, per_table, per_value = rows, "", ""
+        else:
+            if rows < 1 or rows % T:
+                raise ValueError(f"q must have a positive multiple of q_len = {T} rows, got {rows}")
+            batch, per_table, per_value = rows // T, ": one row per sequence", ": one per sequence"
         if (not isinstance(block_table, torch.Tensor) or block_table.dtype not in (torch.int32, torch.int64) or block_table.dim() != 2
                 or block_table.shape[0] != batch or block_table.shape[1] < 1 or block_table.device != q.device):
-            raise ValueError(f"block_table must be int32 (or int64) [{batch}, max_blocks] on {q.device}: one row per sequence")
-        for name, t in (("seq_lens", seq_lens), ("q_lens", q_lens)):
-            if t is None and name == "q_lens":
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64) or t.numel() != batch or t.device != q.device:
-                raise ValueError(f"{name} must be {batch} int32 (or int64) values on {q.device}: one per sequence")
+            raise ValueError(f"block_table must be int32 (or int64) [{batch}, max_blocks] on {q.device}{per_table}")
+        if (not isinstance(seq_lens, torch.Tensor) or seq_lens.dtype not in (torch.int32, torch.int64) or seq_lens.numel() != batch
+                or seq_lens.device != q.device):
+            raise ValueError(f"seq_lens must be {batch} int32 (or int64) values on {q.device}{per_value}")
+        if q_lens is not None and (not isinstance(q_lens, torch.Tensor) or q_lens.dtype not in (torch.int32, torch.int64)
+                                   or q_lens.numel() != batch or q_lens.device != q.device):
+            raise ValueError(f"q_lens must be {batch} int32 (or int64) values on {q.device}{per_value}")
         if out is not None:
             if (not isinstance(out, torch.Tensor) or out.dtype != q.dtype or out.device != q.device or out.shape != (rows, W)
                     or out.stride(1) != 1 or (rows > 1 and out.stride(0) < W)):
                 raise ValueError(f"out must be a {q.dtype} [{rows}, {W}] tensor on {q.device} with a contiguous last dimension")
         if rows > 1 and q2.stride(0) < W:
             q2 = q2.contiguous()
-        kernel = (q.dtype in _ATTN_APPEND_ENTRY and q.is_cuda and D in (64, 128) and HQ // H <= 8 and T <= ATTN_APPEND_MAX_Q_LEN
-                  and rows <= 64)
-        if not kernel:
-            self.__dict__["_last_route"] = "fallback"
-            table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
-            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
-            if out is not None:
-                out.copy_(o)
-                return out
-            return o.reshape(*lead, W)
-        if self.append_route not in ("auto", "kernel", "emulate"):
-            raise ValueError(f"append_route must be 'auto', 'kernel' or 'emulate', got {self.append_route!r}")
-        # routed by measurement, END TO END (tools/attn_append_bench.py `route_emul` against `append`): the expansion
-        # below is a dozen small kernels in every call, 24 - 34 us in a replayed graph, which the one-query kernels win back only
-        # over an fp8 cache at 64 rows (by up to 10 %); everywhere else the append kernels are faster.  The same bits either way.
-        if self.append_route == "emulate" or (self.append_route == "auto" and fp8 and rows >= 64):
-            table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
-            o = self.forward(q2, k_cache, v_cache, table, lens, out=out, block_size=bs, k_scale=k_scale if fp8 else None,
-                             v_scale=v_scale if fp8 else None)  # (`last_route` "attn_decode")
-            return o if out is not None else o.reshape(*lead, W)
-        bt = block_table if block_table.dtype == torch.int32 else block_table.to(torch.int32)  # (a kernel)
-        if bt.stride(1) != 1 or (batch > 1 and bt.stride(0) < bt.shape[1]):
+        return q2, rows, bs, fp8, k_scale, v_scale
+
+    @staticmethod
+    def _int32_operands(block_table, seq_lens, q_lens):
+        """The table and the lengths as the kernels read them: int32 (a conversion is a kernel), table rows at least a row apart,
+        vectors contiguous; what already is, is used WITHOUT a copy."""
+        bt = block_table if block_table.dtype == torch.int32 else block_table.to(torch.int32)
+        if bt.stride(1) != 1 or (bt.shape[0] > 1 and bt.stride(0) < bt.shape[1]):
             bt = bt.contiguous()
+        return bt, _int32_vector(seq_lens), (None if q_lens is None else _int32_vector(q_lens))
 
-        def int32_vector(t):
-            t = t.reshape(-1)
-            if t.dtype != torch.int32:
-                t = t.to(torch.int32)  # (a kernel)
-            return t if t.is_contiguous() else t.contiguous()
-
-        sl = int32_vector(seq_lens)
-        ql = None if q_lens is None else int32_vector(q_lens)
-        self.__dict__["_last_route"] = "attn_append"
-        dev = q.get_device()
-        o = out if out is not None else torch.empty((rows, W), dtype=q.dtype, device=q.device)
+    def _launch(self, kind: int, q2, k_cache, v_cache, bt, sl, ql, T, out, bs, k_scale, v_scale) -> torch.Tensor:
+        """Kind `kind` of _ATTN_KINDS on the current stream: the workspace, the kind's descriptor of this (device, stream), the
+        entry.  bt has one row per sequence.  -> out, or a new [rows, W]."""
+        D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
+        rows, W = q2.shape
+        batch, max_blocks = bt.shape
+        dev = q2.get_device()
+        o = out if out is not None else torch.empty((rows, W), dtype=q2.dtype, device=q2.device)
         stream = quant_cuda._raw_stream(dev)
-        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.attn_decode_workspace_bytes(rows, HQ, D, bt.shape[1], bs), q.device,
+        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.attn_decode_workspace_bytes(rows, HQ, D, max_blocks, bs), q2.device,
                            self.GRAPH_WS_MAX_BYTES)
-        descs = self.__dict__.setdefault("_desc_append8" if fp8 else "_desc_append", {})
-        hit = descs.get((dev, stream))
+        struct, entries = _ATTN_KINDS[kind]
+        descs = self.__dict__.setdefault("_desc", {})
+        hit = descs.get((kind, dev, stream))
         if hit is None:
-            a = _lib.SqllmAttnAppendFp8() if fp8 else _lib.SqllmAttnAppend()
-            hit = descs[(dev, stream)] = (a, ctypes.byref(a))
+            a = struct()
+            hit = descs[(kind, dev, stream)] = (a, ctypes.byref(a))
         a, ref = hit
         a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
         a.block_table, a.seq_lens = bt.data_ptr(), sl.data_ptr()
-        a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
         a.batch, a.n_q_heads, a.n_kv_heads, a.head_dim = batch, HQ, H, D
-        a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, bt.shape[1]
-        a.table_stride = bt.stride(0) if batch > 1 else bt.shape[1]
+        a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, max_blocks
+        a.table_stride = bt.stride(0) if batch > 1 else max_blocks
         a.slot_stride = k_cache.stride(0)
         a.head_stride = k_cache.stride(1) if H > 1 else D  # (one head: its stride is anything, and never used)
         a.q_stride = q2.stride(0) if rows > 1 else W
         a.out_stride = o.stride(0) if rows > 1 else W
         a.scale, a.workspace = self.scale, ws.data_ptr()
-        if fp8:
+        if kind & 1:
             a.k_scale, a.v_scale = k_scale, v_scale
-        quant_cuda._launch(quant_cuda._fn((_ATTN_APPEND_FP8_ENTRY if fp8 else _ATTN_APPEND_ENTRY)[q.dtype]), dev, (ref,))
-        return o if out is not None else o.reshape(*lead, W)
+        if kind & 2:
+            a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
+        quant_cuda._launch(quant_cuda._fn(entries[q2.dtype]), dev, (ref,))
+        return o
+
+    def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
+                out=None, block_size=None, k_scale=None, v_scale=None, q_len=None, q_lens=None) -> torch.Tensor:
+        D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
+        W = HQ * D
+        T = None  # one query per sequence; forward(..., q_len=T, q_lens=None): T new tokens per sequence (sqllm_attn_append_*)
+        if q_len is not None or q_lens is not None:
+            if q_len is None:
+                raise ValueError("q_lens needs q_len, the rows per sequence")
+            T = int(q_len)
+            if T < 1:
+                raise ValueError(f"q_len must be positive, got {q_len}")
+        q2, rows, bs, fp8, k_scale, v_scale = self._check_operands(q, k_cache, v_cache, block_table, seq_lens, out, block_size,
+                                                                   k_scale, v_scale, T, q_lens)
+        kernel = (q.dtype in _ATTN_DTYPES and q.is_cuda and D in (64, 128) and HQ // H <= 8 and rows <= 64
+                  and (T is None or T <= ATTN_APPEND_MAX_Q_LEN))
+        if not kernel:
+            self.__dict__["_last_route"] = "fallback"
+            table, lens = (block_table, seq_lens) if T is None else append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
+            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
+            if out is not None:
+                out.copy_(o)
+                return out
+            return o.reshape(*q.shape[:-1], W)
+        if T is not None:
+            if self.append_route not in ("auto", "kernel", "emulate"):
+                raise ValueError(f"append_route must be 'auto', 'kernel' or 'emulate', got {self.append_route!r}")
+            # routed by measurement, END TO END (tools/attn_append_bench.py `route_emul` against `append`, DESIGN.md 4.4): the expansion
+            # below is a dozen small kernels in every call, 24 - 34 us in a replayed graph, which the one-query kernels win back only
+            # over an fp8 cache at 64 rows (by up to 10 %); everywhere else the append kernels are faster.  The same bits either way.
+            if self.append_route == "emulate" or (self.append_route == "auto" and fp8 and rows >= 64):
+                table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
+                o = self.forward(q2, k_cache, v_cache, table, lens, out=out, block_size=bs, k_scale=k_scale if fp8 else None,
+                                 v_scale=v_scale if fp8 else None)  # (`last_route` "attn_decode")
+                return o if out is not None else o.reshape(*q.shape[:-1], W)
+        bt, sl, ql = self._int32_operands(block_table, seq_lens, q_lens)
+        self.__dict__["_last_route"] = "attn_decode" if T is None else "attn_append"
+        o = self._launch(2 * (T is not None) + fp8, q2, k_cache, v_cache, bt, sl, ql, T, out, bs, k_scale, v_scale)
+        return o if out is not None else o.reshape(*q.shape[:-1], W)
 
 
 def fuse_decode_attention(module: nn.Module, n_heads=None, n_kv_heads=None) -> int:

@@ -164,21 +164,22 @@ def test_the_sources_are_part_of_the_product_build():
     for src in ("sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip"):
         assert src in B.SOURCES and B.SOURCES.index(src) < B.SOURCES.index("sqllm_capi.hip")
     assert B.SOURCES[-1] == "sqllm_capi.hip"
-    assert os.path.join(B.CSRC, "sqllm_attn_append.h") in B.HEADERS  # (a changed header makes the library stale)
+    assert os.path.join(B.CSRC, "sqllm_attn.h") in B.HEADERS  # (a changed header makes the library stale)
 
 
 def test_launch_hooks_on_the_host_layer_alone(tmp_path):
-    """a missing kernel is an error, not a fallback; each entry reaches the hook of its cache type with the tokens' fields"""
+    """a missing kernel is an error, not a fallback; each of the eight entries (the four here, the four one-query ones) reaches the
+    slot of its own kind and no other, with the tokens' fields"""
     from squeezellm_amd import build as B
 
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not found: the host layer cannot be built alone")
     native = os.path.join(H.ROOT, "tests", "native")
-    exe = str(tmp_path / "attn_append_hooks")
+    exe = str(tmp_path / "attn_hooks")
     r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-DSQLLM_RECORDER_NO_MAIN", f"-I{B.INCLUDE}", f"-I{B.CSRC}",
                         os.path.join(B.CSRC, "sqllm_capi.hip"), os.path.join(native, "launch_recorder.cpp"),
-                        os.path.join(native, "attn_append_hooks.cpp"), "-o", exe], capture_output=True, text=True, timeout=600)
+                        os.path.join(native, "attn_hooks.cpp"), "-o", exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -192,3 +193,16 @@ def test_launch_hooks_on_the_host_layer_alone(tmp_path):
     assert lines["fp8_f16"] == dict(common, calls="2,1", bf16="0", scale="0.0625", v_scale="4")
     assert lines["fp8_bf16"] == dict(common, calls="2,2", bf16="1", scale="0.0625", v_scale="4")
     assert lines["null_q_lens"] == dict(common, calls="3,2", bf16="0", scale="0.125", v_scale="1", q_len="1", q_lens="0")
+    # the four one-query entries: the same steps on their own two slots
+    assert lines["nohook_decode"] == {"notsupported": ns, "f16": ns, "bf16": ns, "fp8_f16": ns, "fp8_bf16": ns}
+    # exactly one slot filled, each in turn: its f16 and bf16 entry succeed, the other six fail, and only that slot is called
+    entries = ("decode_f16", "decode_bf16", "decode_fp8_f16", "decode_fp8_bf16", "append_f16", "append_bf16", "append_fp8_f16", "append_fp8_bf16")
+    for k, slot in enumerate(("decode", "decode_fp8", "append", "append_fp8")):
+        want = {e: ("0" if e.rsplit("_", 1)[0] == slot else ns) for e in entries}
+        assert lines["only_" + slot] == dict(want, notsupported=ns, calls=",".join("2" if i == k else "0" for i in range(4))), slot
+    one = dict(common, q_len="0", q_lens="0")  # (no tokens: q_len 0 names the one-query kernels)
+    assert lines["decode_f16"] == dict(one, calls="1,0", bf16="0", scale="0.125", v_scale="1")
+    assert lines["decode_bf16"] == dict(one, calls="2,0", bf16="1", scale="0.125", v_scale="1")
+    assert lines["decode_fp8_f16"] == dict(one, calls="2,1", bf16="0", scale="0.0625", v_scale="4")
+    assert lines["decode_fp8_bf16"] == dict(one, calls="2,2", bf16="1", scale="0.0625", v_scale="4")
+    assert lines["slots"] == {"decode": "2", "decode_fp8": "2", "append": "3", "append_fp8": "2"}  # nine calls, each in its own slot

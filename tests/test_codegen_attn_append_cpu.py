@@ -41,9 +41,14 @@ def test_exactly_the_expected_instances(kernels):
     k16, k8 = kernels
     assert sorted(k16) == sorted([_partial(d, gc, ot) for d in DIMS for gc in CLASSES for ot in TYPES] + [_combine(d, ot) for d in DIMS for ot in TYPES])
     assert sorted(k8) == sorted(_partial_fp8(d, gc, ot) for d in DIMS for gc in CLASSES for ot in TYPES)  # (the combine is the other source's)
-    for name, inst in (("sqllm_attn_append.hip", r"launch_append_inst<D, (\d), OT>"), ("sqllm_attn_append_fp8.hip", r"launch_append_fp8_inst<D, (\d), OT>")):
+    # one instantiation per virtual-head class: the shared ladder's, over the kernel each file's tag names
+    ladder = open(os.path.join(B.CSRC, "sqllm_attn.h")).read()
+    assert sorted(int(c) for c in re.findall(r"launch_attn_inst<TAG, D, (\d), OT>", ladder)) == list(CLASSES)
+    assert "switch (TAG::heads(k))" in ladder and "return k.q_len * k.group;" in ladder
+    for name, kern, tag in (("sqllm_attn_append.hip", "sqllm_attn_append_kernel", "g_launch_attn[kAttnAppend] = launch_attn<AttnAppendTag>"),
+                            ("sqllm_attn_append_fp8.hip", "sqllm_attn_append_fp8_kernel", "g_launch_attn[kAttnAppendFp8] = launch_attn<AttnAppendFp8Tag>")):
         src = open(os.path.join(B.CSRC, name)).read()
-        assert sorted(int(c) for c in re.findall(inst, src)) == list(CLASSES)
+        assert f"return {kern}<D, GC, OT>;" in src and tag in src
         assert "template <int D, int GC, typename OT>\n__global__" in src  # head_dim, virtual-head class and output type only
 
 

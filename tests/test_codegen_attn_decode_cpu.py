@@ -39,7 +39,10 @@ def test_exactly_the_expected_instances(kernels):
     want = [_partial(d, gc, ot) for d in DIMS for gc in CLASSES for ot in TYPES] + [_combine(d, ot) for d in DIMS for ot in TYPES]
     assert sorted(kernels) == sorted(want)
     src = open(os.path.join(B.CSRC, "sqllm_attn_decode.hip")).read()
-    assert sorted(int(c) for c in re.findall(r"launch_attn_inst<D, (\d), OT>", src)) == list(CLASSES)
+    # one instantiation per group class: the shared ladder's, over the kernel this file's tag names
+    ladder = open(os.path.join(B.CSRC, "sqllm_attn.h")).read()
+    assert sorted(int(c) for c in re.findall(r"launch_attn_inst<TAG, D, (\d), OT>", ladder)) == list(CLASSES)
+    assert "return sqllm_attn_decode_kernel<D, GC, OT>;" in src and "g_launch_attn[kAttnDecode] = launch_attn<AttnDecodeTag>" in src
     assert "template <int D, int GC, typename OT>\n__global__" in src  # head_dim, group class and output type only
 
 

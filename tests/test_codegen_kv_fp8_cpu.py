@@ -110,8 +110,13 @@ def test_exactly_the_expected_partials_and_the_16_bit_source_keeps_its_kernels(r
     from tests import test_codegen_attn_decode_cpu as T
     assert sorted(old) == sorted([T._partial(d, gc, ot) for d in DIMS for gc in CLASSES for ot in OTS] + [T._combine(d, ot) for d in DIMS for ot in OTS])
     src = open(os.path.join(B.CSRC, "sqllm_attn_decode_fp8.hip")).read()
-    assert sorted(int(c) for c in re.findall(r"launch_attn_fp8_inst<D, (\d), OT>", src)) == list(CLASSES)
-    assert "g_launch_attn_combine(k, D, bf16, batch, stream)" in src and "sqllm_attn_combine_kernel" not in src
+    # one instantiation per group class: the shared ladder's, over the kernel this file's tag names; the combine is reached through
+    # the hook, and the file has no combine kernel
+    ladder = open(os.path.join(B.CSRC, "sqllm_attn.h")).read()
+    assert sorted(int(c) for c in re.findall(r"launch_attn_inst<TAG, D, (\d), OT>", ladder)) == list(CLASSES)
+    assert "return sqllm_attn_decode_fp8_kernel<D, GC, OT>;" in src and "g_launch_attn[kAttnDecodeFp8] = launch_attn<AttnDecodeFp8Tag>" in src
+    assert "struct AttnDecodeFp8Tag : AttnOneQuery" in src and "g_launch_attn_combine(k, c.head_dim, c.bf16, c.batch, stream)" in ladder
+    assert "combine_kernel" not in src
     assert "16 ELEMENTS = 16 bytes per key" in src and "The cross-lane reduction this implies" in src  # the header comment's choice
 
 

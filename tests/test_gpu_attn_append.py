@@ -468,3 +468,23 @@ def test_module_surface(gpu):
     one.append_route = "sideways"
     with pytest.raises(ValueError):
         one(d1.q, d1.k, d1.v, d1.table, d1.seq, q_len=16, **d1.kw)
+
+
+@gpu_test
+def test_one_instance_serves_the_four_kinds_in_turn_from_one_descriptor_cache(gpu):
+    """one-query 16-bit, one-query fp8, append 16-bit, append fp8, twice round on one instance and one stream: each call fills the
+    descriptor of its own kind, so every output is what a fresh instance gives for the same call.  2 sequences of 2 new tokens
+    (300 keys: two partitions and the combine; 17 keys: one partition), 4 query heads over 2 kv heads of 64, blocks of 16"""
+    import torch
+
+    d16 = _dev(gpu, "paged", 2, 64, 4, 2, "fp16", (300, 17))
+    d8 = _dev(gpu, "paged", 2, 64, 4, 2, "fp16", (300, 17), None, True)
+    assert d16.base.block_size == 16 and d16.table.shape[1] * 16 > P  # (more than one partition: the workspace and the combine are in use)
+    calls = [(d16, Dev.decode), (d8, Dev.decode), (d16, Dev.append), (d8, Dev.append)]
+    want = [call(d, d.module()) for d, call in calls]
+    assert all(bool(torch.isfinite(y).all()) for y in want) and not torch.equal(want[0], want[1])  # (the fp8 cache is other data)
+    att = d16.module()
+    for _ in range(2):
+        for (d, call), y in zip(calls, want):
+            assert torch.equal(call(d, att), y)
+    assert sorted(k[0] for k in att._desc) == [0, 1, 2, 3]  # one descriptor per kind

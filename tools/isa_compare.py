@@ -7,7 +7,8 @@
 source file present in A only.  A source file present in B only (a source B added) is listed as "new in B" with its kernel
 count and NOT counted; `dump` skips product sources the tree does not have (an older tree).
 `dump` uses the command of tests/test_codegen_cpu.py (build.FLAGS without -fPIC, -S --cuda-device-only), once plain
-for the product sources and once with -DSQLLM_ABLATION_BUILD for the kernel sources of the measurement library.
+for the product sources -- build.SOURCES of the tree it lies in, without the host layer -- and once with
+-DSQLLM_ABLATION_BUILD for those and the kernel sources of the measurement library.
 To dump a commit that does not have this script yet, copy the script into that tree's tools/ first (it reads the
 sources and the flags of the tree it lies in).
 """
@@ -20,10 +21,9 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from squeezellm_amd import build as B  # noqa: E402
 
-PRODUCT = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "sqllm_dequant.hip", "sqllm_linear_bf16.hip", "sqllm_linear_gated.hip",
-           "sqllm_linear_ep.hip", "sqllm_linear_qkv.hip", "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip", "sqllm_linear_qkv_cache.hip",
-           "sqllm_linear_qkv_norm_cache.hip", "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode.hip",
-           "sqllm_attn_decode_fp8.hip"]
+# every kernel source of the product: build.SOURCES without the host layer (its last entry), so that a new kernel file cannot be forgotten
+PRODUCT = B.SOURCES[:-1]
+assert B.SOURCES[-1] == "sqllm_capi.hip"
 META = (".vgpr_count", ".sgpr_count", ".agpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size",
         ".vgpr_spill_count", ".sgpr_spill_count")
 CLASSES = ("v_mfma", "ds_read", "global_load", "buffer_load", "s_load", "s_barrier", "s_waitcnt")
