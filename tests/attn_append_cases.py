@@ -109,3 +109,40 @@ def reference(kind, T, D, HQ, H, dtype_name, seqs, q_lens=None):
     """(base, expansion, want, gate): the fp64 oracle and the gate of attn_decode_cases on the expansion, computed once"""
     base, case = build(kind, T, D, HQ, H, dtype_name, seqs, q_lens)
     return (base, case, *C.reference_of(case))
+
+
+# ---- sharp softmax (attn_decode_cases.sharpen) under several new tokens ----
+
+# A token that attends two or three keys -- or whose two or three top keys carry the row -- at scores beyond +-100 has a result
+# whose last bits follow from the ORDER of the fp32 dot products (a unit in the last place of such a score is 1.5e-5; an fp16
+# output near zero is finer).  The gate's yardstick for that is ONE draw, model32's own rounding of that (row, head); 16 new tokens
+# behind sequences of 7 and 2P + 3 keys hold a hundred such (row, head)s, and on 21 of the 648 (case, cache, T) of the sharp-softmax
+# tests the fp32 model in the kernels' own structure (attn_decode_cases.model_parts) exceeds the gate on the first draw of the
+# new tokens' q: those cases are unfair to any fp32 implementation of that structure, and take the next draw on which the model is
+# inside (tests/test_attn_ranges_cpu.py asserts all of it: every draw below the listed one is outside, the used ones inside, the
+# unlisted cases inside on their first draw -- on the CPU, from the model alone).  All 21 are fp16 outputs; all but one T = 16.
+# Key: (geometry, head_dim, query heads, type, profile, fp8 cache?, T).
+SHARP_DRAWS = {
+    ("paged", 64, 8, "fp16", "ramp_up", True, 16): 1, ("paged", 64, 8, "fp16", "all_low", True, 16): 1, ("paged", 64, 8, "fp16", "all_high", True, 16): 1,
+    ("paged", 128, 4, "fp16", "all_low", True, 16): 1, ("paged", 128, 4, "fp16", "all_high", True, 16): 1,
+    ("paged", 64, 16, "fp16", "all_low", False, 16): 3, ("paged", 64, 16, "fp16", "all_low", True, 16): 3,
+    ("paged", 64, 16, "fp16", "all_high", False, 16): 3, ("paged", 64, 16, "fp16", "all_high", True, 16): 3,
+    ("padded", 64, 8, "fp16", "ramp_up", True, 2): 1, ("padded", 64, 8, "fp16", "all_low", True, 16): 1, ("padded", 64, 8, "fp16", "all_high", True, 16): 1,
+    ("padded", 128, 4, "fp16", "ramp_up", False, 16): 1,
+    ("padded", 64, 16, "fp16", "all_low", False, 16): 1, ("padded", 64, 16, "fp16", "all_low", True, 16): 2,
+    ("padded", 64, 16, "fp16", "all_high", False, 16): 1, ("padded", 64, 16, "fp16", "all_high", True, 16): 2,
+    ("bhsd", 64, 8, "fp16", "all_low", False, 16): 1, ("bhsd", 64, 8, "fp16", "all_high", False, 16): 1,
+    ("bhsd", 128, 4, "fp16", "ramp_up", True, 16): 1, ("bhsd", 64, 16, "fp16", "ramp_up", True, 16): 1,
+}
+
+
+def sharp_expand(base, T, fp8=False, draw=None):
+    """the expansion of a sharpened case (or of its fp8 shadow) for T new tokens per sequence, q sharpened the same way; `draw`:
+    which draw of the new tokens' q (None: the one SHARP_DRAWS lists for the case, else the first)"""
+    if draw is None:
+        dt = {v: k for k, v in C.DTYPES.items()}[base.dtype]
+        draw = SHARP_DRAWS.get((base.kind, base.D, base.HQ, dt, base.profile, bool(fp8), T), 0)
+    if draw:
+        base = copy.copy(base)
+        base.seed = base.seed + [1000 + draw]
+    return C.sharpen_q(expand(base, T), base.sharp_c)
