@@ -1191,6 +1191,7 @@ static int launch_group_with_events(const sqllm_op* ops, int n, sqllm_stream_t s
         break;
       case kColsGroup:
       case kPerOpCols:
+        if (g_experimental.decorate) g_experimental.decorate(&a);  // (measurement library: timeline buffer of the one-row instantiations, tools/timeline.py --cols)
         e = sqllm::launch_batched_cols(op->bits, a, s);
         break;
       case kFusedSmall:

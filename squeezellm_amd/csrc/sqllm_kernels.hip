@@ -415,7 +415,9 @@ sqllm_sparse_batched(const float* x, const GroupArgs ga, const float* xT, int Bp
 //       of 32 k's (4 x s_load_dwordx8 into one of two sets of 32 SGPRs), so a scalar load is in flight during one stage
 //       in four only; in the other three the wait for stage s is a counted lgkmcnt(reads of s + 1) BEHIND the issue of stage
 //       s + 1 (LDS returns in order) -- one full drain per 32 weights instead of four; and chunk pairs whose units all exist
-//       run without the dead-unit selects (the piece's last pair(s) take the guarded copy).  Same FMAs on the same
+//       run without the dead-unit selects (the piece's last pair(s) take the guarded copy); a piece's FIRST group is requested with the
+//       piece's first loads, above the table build (behind the table barrier it was a second memory round trip of 0.16-0.20 us in front of
+//       every piece's first FMA: profiles/cols_head_timeline.txt).  Same FMAs on the same
 //       accumulators in the same order: results are bit-identical to the staged loop's.
 // Work is cut as in the matrix-core kernel: equal contiguous ranges of the flattened
 // (column tile, unit) space, one per workgroup, a range crossing a tile boundary = two pieces.
@@ -469,7 +471,9 @@ template <int BITS, int BT, int WAVES>
 __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, const uint32_t* __restrict__ q,
                                                 float* __restrict__ y, const float* __restrict__ lut, int K, int N,
                                                 int b0, int nb, int bid, int n_col_tiles, int units_total,
-                                                int units_per_wg, int units_stride, float* lds) {
+                                                int units_per_wg, int units_stride, float* lds, unsigned long long* tl) {
+  // timeline probe (sqllm_probe.h; nothing in the product; tools/timeline.py --cols): thread 0 stamps 0 entry, 1 table barrier passed,
+  // 4 in front of the first FMA, 2 wave 0 done decoding, 3 atomics issued (a range of two pieces: the second piece's stamps stay)
   using F = Fmt<BITS>;
   constexpr int L = F::kLut, R = F::kRows, KU = F::kK;
   constexpr int ST = cols_stage_k(BT);        // k's per stage
@@ -485,6 +489,7 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
   __builtin_amdgcn_s_waitcnt(0);
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  SQLLM_PROBE(tl, 0, tid == 0);
   char* table = reinterpret_cast<char*>(lds);
   float* slabs = lds + cols_table_floats(BITS);
   // 4-bit: byte 1 of the lane word is the index of the zero row -- a lookup's v_perm takes its entry
@@ -554,6 +559,37 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
     uint32_t wbuf[NB][D][R];
 #pragma unroll
     for (int k = 0; k < NB; ++k) load_chunk(k, wbuf[k]);
+    // (one row) vec by groups of GS stages = 32 k's, two sets of 32 SGPRs: see the one-row loop below.
+    constexpr int GS = 32 / ST;                 // stages per vec group
+    [[maybe_unused]] XV xs[2][GS];
+    // vec of the group that starts at stage st0 of chunk cc.  Guarded copy: a unit past the wave's last one reads a line of ZEROS (xzero) as
+    // its vec, not the piece's last unit again -- its weights are the table's zero row, and zero times an infinite element of a re-read
+    // vec would be NaN in every column of the tile; a scalar select of the base pointer, no vector work.  The unguarded copy never
+    // requests the vec of a dead unit that is used (see c_full below) and keeps the clamp, which only keeps its addresses in bounds.
+    [[maybe_unused]] auto vec_group = [&](int st0, int cc, XV (&xg)[GS], auto guard) {
+#pragma unroll
+      for (int g = 0; g < GS; ++g) {
+        const int j = (st0 + g) / SPU, sub = (st0 + g) % SPU;
+        int u = u0 + w + (cc * D + j) * WAVES;
+        if constexpr (decltype(guard)::value) {
+          const bool past = u > u1 - 1;
+          if (past) u = 0;
+          uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
+          asm volatile("" : "+s"(koff));
+          xg[g] = XVec<ST>::load(past ? xzero : xrow[0], koff);
+        } else {
+          if (u > u1 - 1) u = u1 - 1;
+          uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
+          asm volatile("" : "+s"(koff));
+          xg[g] = XVec<ST>::load(xrow[0], koff);
+        }
+      }
+    };
+    // One row: the piece's FIRST group goes out here, with the codebook values and the weight chunks and above the table build -- it depends on
+    // nothing but u0, w and the row pointer, and behind the table barrier it was a second memory round trip in front of the piece's first FMA
+    // (every workgroup of a launch pays it together).  The drain in front of the first lookups stays where it was.  (The first chunk may hold
+    // dead units: the guarded form, once per piece.)  No control flow between these loads and the table build: see the staging of sqllm_fused.h.
+    if constexpr (BT == 1) vec_group(0, 0, xs[0], std::true_type{});
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     if (!first) __syncthreads();  // everybody has left the previous piece's table and slabs
@@ -566,6 +602,10 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
       for (int i0 = 0; i0 < 8; ++i0) *reinterpret_cast<f32x2*>(table + (8 * w + i0) * 512 + lane_base) = f32x2{tv[i0], thi};
     }
     __syncthreads();
+    // (one row: with vec's first group gone from here the first lookups' address work would rise above the barrier, and with it the wait for
+    // the first weight chunk -- the first weight word is pinned behind the barrier, so the table build waits for the codebook values alone)
+    if constexpr (BT == 1) asm volatile("" : "+v"(wbuf[0][0][0]));
+    SQLLM_PROBE(tl, 1, tid == 0);
 
     f32x2 acc[BT][NA];
 #pragma unroll
@@ -626,11 +666,9 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
       // Chunk pairs whose units all exist take the loop without the dead-unit selects; the piece's last pair(s) take the
       // guarded copy.  A dead unit's vec is a line of zeros in the guarded copy; the unguarded one never uses a dead unit's (c_full).
       // Every column's sum runs over k in the same order and on the same accumulators as in the staged loop below.
-      constexpr int GS = 32 / ST;                 // stages per vec group
       constexpr int LPS = BITS == 4 ? 2 * NP : NP;  // LDS reads per stage
       static_assert(NS % GS == 0 && (NB * NS / GS) % 2 == 0, "vec groups alternate between two SGPR sets");
       struct V { f32x2 v[NP]; };
-      XV xs[2][GS];
       auto look = [&](const uint32_t (&buf)[D][R], int st, int cc, V& o, auto guard) {
         const int j = st / SPU, sub = st % SPU;
         bool live = true;
@@ -650,29 +688,6 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
           for (int m = 0; m < NP; ++m)
             o.v[m] = *reinterpret_cast<const f32x2 __attribute__((address_space(3)))*>(
                 lane_or_dead | field6_x512(buf[j][0], buf[j][1], buf[j][2], sub * NP + m));
-        }
-      };
-      // vec of the group that starts at stage st0 of chunk cc.  Guarded copy: a unit past the wave's last one reads a line of ZEROS (xzero) as
-      // its vec, not the piece's last unit again -- its weights are the table's zero row, and zero times an infinite element of a re-read
-      // vec would be NaN in every column of the tile; a scalar select of the base pointer, no vector work.  The unguarded copy never
-      // requests the vec of a dead unit that is used (see c_full below) and keeps the clamp, which only keeps its addresses in bounds.
-      auto vec_group = [&](int st0, int cc, XV (&xg)[GS], auto guard) {
-#pragma unroll
-        for (int g = 0; g < GS; ++g) {
-          const int j = (st0 + g) / SPU, sub = (st0 + g) % SPU;
-          int u = u0 + w + (cc * D + j) * WAVES;
-          if constexpr (decltype(guard)::value) {
-            const bool past = u > u1 - 1;
-            if (past) u = 0;
-            uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
-            asm volatile("" : "+s"(koff));
-            xg[g] = XVec<ST>::load(past ? xzero : xrow[0], koff);
-          } else {
-            if (u > u1 - 1) u = u1 - 1;
-            uint32_t koff = 4u * (uint32_t)(u * KU + sub * ST);
-            asm volatile("" : "+s"(koff));
-            xg[g] = XVec<ST>::load(xrow[0], koff);
-          }
         }
       };
       auto fma1 = [&](const V& o, const XV& xv) {
@@ -710,8 +725,9 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      vec_group(0, 0, xs[0], std::true_type{});  // (the first chunk may hold dead units: once per piece)
+      // (xs[0] holds the piece's first group: requested with the piece's first loads, above the table build)
       __builtin_amdgcn_s_waitcnt(0xC07F);  // (no scalar load in flight when the loop's counted waits begin)
+      SQLLM_PROBE(tl, 4, tid == 0);
       look(wbuf[0], 0, 0, va, std::true_type{});
       __builtin_amdgcn_sched_barrier(0);
       // Chunks [0, c_full) take the unguarded copy: pairs whose units all exist AND whose last vec request -- the first group (32 k's:
@@ -752,6 +768,7 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
     }
     }
 
+    SQLLM_PROBE(tl, 2, tid == 0);
     // ---- waves meet in LDS: slab [wave][row][column], then one atomic per (row, column) ----
 #pragma unroll
     for (int b = 0; b < BT; ++b) {
@@ -768,6 +785,7 @@ __device__ __forceinline__ void dense_role_cols(const float* __restrict__ x, con
       for (int ww = 0; ww < WAVES; ++ww) sum += slabs[(ww * BT + b) * 64 + c];
       if (b < nb && col0 + c < N) acc_add(y + (size_t)(b0 + b) * N + col0 + c, sum);
     }
+    SQLLM_PROBE(tl, 3, tid == 0);
   }
 }
 
@@ -807,7 +825,8 @@ sqllm_fused_cols(const float* x, const GroupArgs ga) {
     // differently -- profiles/refactor_kernel_glue_isa.txt; re-test with tools/isa_compare.py before folding it in)
     dense_role_cols<BITS, BT, WAVES>(x, sg.q, sg.y, sg.lut, gm.K, gm.N, b0, nb, d, gm.col_tiles, gm.units_total,
                                      gm.units_per_wg,
-                                     gm.dense_blocks == gm.col_tiles * gm.k_slices ? gm.k_slices * gm.units_per_wg : gm.units_total, lds);
+                                     gm.dense_blocks == gm.col_tiles * gm.k_slices ? gm.k_slices * gm.units_per_wg : gm.units_total, lds,
+                                     BT == 1 ? SQLLM_PROBE_PTR(sg) : nullptr);  // (the one-row instantiations only: the measurement library's others stay the product's)
   } else if (sp >= 0 && sp < gm.csr_blocks) {
     csr_role<T, BT, float, float>(x, sg.y, sg.rows, sg.cols, sg.vals, gm.nnz, gm.K, gm.N, b0, nb, sp, lds, nullptr, 0);
   } else if (sp >= gm.csr_blocks && sp < gm.csr_blocks + gm.topx_blocks) {
