@@ -13,9 +13,11 @@ from __future__ import annotations
 
 import ctypes
 import math
+import operator
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib, quant_cuda
 
@@ -155,10 +157,14 @@ class QuantLinearLUT(nn.Module):
 
 
 _is_capturing = torch.cuda.is_current_stream_capturing
-# activation dtypes of the fused forward -> the entry point that takes them (one sqllm_linear descriptor serves both)
-_FUSED_ENTRY = {torch.float16: "sqllm_linear_f16", torch.bfloat16: "sqllm_linear_bf16"}
-# ... and the entry point of the same linear with an epilogue (QuantLinearLUTFused.act, forward's residual / out)
-_EP_ENTRY = {torch.float16: "sqllm_linear_ep_f16", torch.bfloat16: "sqllm_linear_ep_bf16"}
+_FRONT_DTYPES = (torch.float16, torch.bfloat16)  # the activation dtypes the front kernels take; anything else is a torch route
+# (front, norm prologue, KV cache, fp8 cache, activation dtype) -> the entry point of include/sqllm_hip.h.  "linear_ep" is the
+# linear with an epilogue (QuantLinearLUTFused.act, forward's residual / out); one descriptor per front serves both dtypes.
+_FRONT_ENTRY = {
+    (front, "norm" in variant, "cache" in variant, "fp8" in variant, dtype): f"sqllm_{front}{variant}_{sfx}"
+    for front, variants in (("linear", ("",)), ("linear_ep", ("",)), ("gated", ("", "_norm")),
+                            ("qkv_rope", ("", "_norm", "_cache", "_norm_cache", "_cache_fp8", "_norm_cache_fp8")))
+    for variant in variants for dtype, sfx in zip(_FRONT_DTYPES, ("f16", "bf16"))}
 _EP_ACT = {None: _lib.ACT_IDENTITY, "relu": _lib.ACT_RELU, "silu": _lib.ACT_SILU, "gelu": _lib.ACT_GELU, "gelu_tanh": _lib.ACT_GELU_TANH}
 
 
@@ -178,14 +184,25 @@ def _torch_epilogue(y: torch.Tensor, act, residual, dtype) -> torch.Tensor:
     return v.to(dtype)
 
 
-def _workspace_of(cache: dict, need: int, device, graph_max: int) -> torch.Tensor:
-    """The workspace rules of QuantLinearLUTFused._workspace (see there) on a module's cache dict, for `need` bytes."""
+_ws_need = {}  # (_lib.option_epoch, a *_workspace_bytes function of _lib, its arguments) -> bytes
+
+
+def _workspace_of(mod: nn.Module, size, shape: tuple, device, stream=None) -> torch.Tensor:
+    """The workspace rules of QuantLinearLUTFused._workspace (see there) on a module's cache dict `_ws`, for `size(*shape)` bytes:
+    `size` is one of _lib's *_workspace_bytes, a call into the library, so each answer is kept.  `stream`: the raw current one."""
+    key = (_lib.option_epoch, size, shape)
+    need = _ws_need.get(key)
+    if need is None:
+        need = _ws_need[key] = size(*shape)
+    cache, graph_max = mod.__dict__.setdefault("_ws", {}), mod.GRAPH_WS_MAX_BYTES
     if _is_capturing():
         ws = cache.get((device, "graph"))
         if ws is not None and ws.numel() >= need:
             return ws
         return torch.zeros(need, dtype=torch.uint8, device=device)  # (not remembered: it belongs to this graph's pool)
-    key = (device, quant_cuda._raw_stream(device.index if device.index is not None else torch.cuda.current_device()))
+    if stream is None:
+        stream = quant_cuda._raw_stream(device.index if device.index is not None else torch.cuda.current_device())
+    key = (device, stream)
     ws = cache.get(key)
     if ws is None or ws.numel() < need:
         ws = torch.zeros(need, dtype=torch.uint8, device=device)  # zero-filled once
@@ -197,6 +214,83 @@ def _workspace_of(cache: dict, need: int, device, graph_max: int) -> torch.Tenso
                 cache.setdefault("retired", []).append(gws)
             cache[(device, "graph")] = torch.zeros(need, dtype=torch.uint8, device=device)
     return ws
+
+
+# ---- what the front modules share on the host ("Adding a front"): intake, torch sums, descriptors, side structs ----
+
+def _rows_of(x: torch.Tensor, K: int, contiguous: bool = True):
+    """-> (x2: x as [rows, K], rows, batch: the descriptors' row count, 0 for one row).  x2 is made contiguous unless
+    `contiguous` is False: a front whose remaining operand checks come before that copy makes it behind them."""
+    if x.shape[-1] != K:
+        raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
+    x2 = x if x.dim() == 2 else x.reshape(-1, K)
+    if contiguous and not x2.is_contiguous():
+        x2 = x2.contiguous()
+    rows = x2.shape[0]
+    return x2, rows, 0 if rows == 1 else rows
+
+
+def _fp32_sums(members, xin: torch.Tensor) -> list:
+    """The dense route of a call with an epilogue, a norm or a rotation, fp32 from end to end so that the kernel's ONE rounding is
+    the only one here too: per member its fp32 matrix (a temporary, 4 * K * N bytes) under torch's fp32 GEMM, plus the bias.
+    (_forward_dense, the plain linear's and the plain pair's, keeps 16 bits: there the sum is rounded to 16 bits either way.)"""
+    sums = []
+    for m in members:
+        s = F.linear(xin, m.dequantize(torch.float32))
+        sums.append(s if m.bias is None else s + m.bias)
+    return sums
+
+
+def _composite_descriptor(cache: dict, dev: int, stream: int, members, build):
+    """The descriptor of (device, stream) a front keeps in `cache` over its members' own sqllm_linear entries
+    (QuantLinearLUTFused._descriptor): `build(entries)`, called only when one of those was rebuilt, returns the front's struct.
+    -> entry = (struct, byref, the members' entries: they keep the folded CSRs alive).  Cached for every front as (those entries,
+    entry, entry): the span-ladder suites read a cached descriptor at [1] (epilogue linear, q/k/v) and at [2] (the pair)."""
+    member = QuantLinearLUTFused._descriptor
+    entries = [member(m, dev, stream) for m in members]
+    hit = cache.get((dev, stream))
+    if hit is not None and all(map(operator.is_, hit[0], entries)):  # (a member's entry is the same object until it is rebuilt)
+        return hit[1]
+    s = build(entries)
+    entry = (s, ctypes.byref(s), entries)
+    cache[(dev, stream)] = (entries, entry, entry)
+    return entry
+
+
+def _side_struct(cache: dict, key, struct):
+    """(the `struct` a front keeps for (device, stream) beside its descriptor -- filled anew by every call --, byref)"""
+    hit = cache.get(key)
+    if hit is None:
+        s = struct()
+        hit = cache[key] = (s, ctypes.byref(s))
+    return hit
+
+
+def _norm_ref(cache: dict, key, norm_weight: torch.Tensor, norm_eps: float):
+    """The sqllm_rmsnorm of (device, stream), filled for this call; the ctypes reference to it."""
+    nm, ref = _side_struct(cache, key, _lib.SqllmRmsNorm)
+    nm.weight, nm.eps = norm_weight.data_ptr(), norm_eps
+    return ref
+
+
+def _kv_ref(cache: dict, key, k_cache: torch.Tensor, v_cache: torch.Tensor, slots: torch.Tensor, head_dim: int, scales=None):
+    """The sqllm_kv_cache (with `scales`: the sqllm_kv_cache_fp8, in a dict of its own) of (device, stream), filled for this call."""
+    c, ref = _side_struct(cache, key, _lib.SqllmKvCache if scales is None else _lib.SqllmKvCacheFp8)
+    c.k_cache, c.v_cache, c.slots = k_cache.data_ptr(), v_cache.data_ptr(), slots.data_ptr()
+    c.n_slots, c.slot_stride = k_cache.shape[0], k_cache.stride(0)
+    c.head_stride = k_cache.stride(1) if k_cache.shape[1] > 1 else head_dim  # (one head: its stride is anything, and never used)
+    if scales is not None:
+        c.k_scale, c.v_scale = scales
+    return ref
+
+
+def _int32_vector(t: torch.Tensor) -> torch.Tensor:
+    """`t` as a contiguous int32 vector; what already is one is returned as it is, so that a captured graph follows it."""
+    if t.dim() != 1:
+        t = t.reshape(-1)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)  # (a kernel)
+    return t if t.is_contiguous() else t.contiguous()
 
 
 class QuantLinearLUTFused(QuantLinearLUT):
@@ -255,14 +349,14 @@ class QuantLinearLUTFused(QuantLinearLUT):
 
     def _forward_dense(self, x: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
         w = self.dequantize(x2.dtype)  # a temporary of this call (fp16 or bf16, as the activations)
-        y = torch.nn.functional.linear(x2, w)
+        y = F.linear(x2, w)
         if self.bias is not None:
             y = (y.float() + self.bias).to(x2.dtype)
         return y.reshape(*x.shape[:-1], self.outfeatures)
 
     GRAPH_WS_MAX_BYTES = 4 << 20  # eager calls keep a second, graph-only workspace ready up to this size (decode batches)
 
-    def _workspace(self, batch: int, device) -> torch.Tensor:
+    def _workspace(self, batch: int, device, stream=None) -> torch.Tensor:
         """ONE zero-filled workspace per (device, stream), sized for the largest batch seen so far: a
         launch uses the first 8 * batch * N bytes and leaves them zero-filled, so smaller batches
         reuse the same buffer (a cache keyed by batch size would grow without bound under variable
@@ -279,8 +373,7 @@ class QuantLinearLUTFused(QuantLinearLUT):
         share it: replaying two of them CONCURRENTLY on different streams is not supported (set GRAPH_WS_MAX_BYTES = 0
         on the module for private, in-graph workspaces).  Without a prepared buffer (no eager call of this size before
         the capture) the workspace is a zero-filled temporary of the captured region."""
-        return _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.linear_workspace_bytes(self.outfeatures, batch), device,
-                             self.GRAPH_WS_MAX_BYTES)
+        return _workspace_of(self, _lib.linear_workspace_bytes, (self.outfeatures, batch), device, stream)
 
     def _check_csr_once(self) -> None:
         """The fused kernel detects completion by COUNTING the contributions `rows` announces: an
@@ -366,28 +459,23 @@ class QuantLinearLUTFused(QuantLinearLUT):
             cache[(dev, stream)] = entry
         return entry[1]
 
+    @staticmethod
+    def _build_epilogue(entries):
+        e = _lib.SqllmLinearEp()
+        e.lin = entries[0][0]  # (a copy)
+        return e
+
     def _epilogue_descriptor(self, dev: int, stream: int):
         """The sqllm_linear_ep of (device, stream): the module's own pre-marshalled sqllm_linear (see _descriptor) copied
         into it, rebuilt when that one is; residual, act, vec / mul, the batch and the workspace are set per call."""
-        lin = self._descriptor(dev, stream)
-        cache = self.__dict__.setdefault("_ep_desc", {})
-        hit = cache.get((dev, stream))
-        if hit is not None and hit[0] is lin[0]:
-            return hit[1]
-        e = _lib.SqllmLinearEp()
-        e.lin = lin[0]  # (a copy)
-        entry = (e, ctypes.byref(e), lin)  # (the linear's entry keeps the folded CSR alive)
-        cache[(dev, stream)] = (lin[0], entry)
-        return entry
+        return _composite_descriptor(self.__dict__.setdefault("_ep_desc", {}), dev, stream, (self,), self._build_epilogue)
 
-    def _forward_epilogue(self, x: torch.Tensor, residual, out) -> torch.Tensor:
-        act = self.act
+    def _check_epilogue(self, x: torch.Tensor, act, residual, out):
+        """The checks of a call with an epilogue, in their order -> _rows_of's (x2, rows, batch), not yet copied, and the shape."""
         if act not in _EP_ACT:
             raise ValueError(f"act must be one of None, 'relu', 'silu', 'gelu', 'gelu_tanh', got {act!r}")
-        K, N = self.infeatures, self.outfeatures
-        if x.shape[-1] != K:
-            raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
-        shape = (*x.shape[:-1], N)
+        intake = _rows_of(x, self.infeatures, False)
+        shape = (*x.shape[:-1], self.outfeatures)
         for name, t in (("residual", residual), ("out", out)):
             if t is None:
                 continue
@@ -397,64 +485,51 @@ class QuantLinearLUTFused(QuantLinearLUT):
             lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * out.element_size()
             if residual.data_ptr() < hi and lo < residual.data_ptr() + residual.numel() * residual.element_size():
                 raise ValueError("out must be residual itself or must not overlap it")
-        if x.dtype not in _FUSED_ENTRY or not x.is_cuda:
-            y = _torch_epilogue(QuantLinearLUT.forward(self, x), act, residual, x.dtype)
-            return y if out is None else out.copy_(y)
-        x2 = x if x.dim() == 2 else x.reshape(-1, K)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        rows = x2.shape[0]
-        if self.dense_min_rows is not None and rows >= self.dense_min_rows:
-            self.__dict__["_last_route"] = "dense"
-            # fp32 from end to end, so that the ONE rounding of the kernel is the only one here too: the layer's matrix in fp32
-            # (a temporary of this call, 4 * K * N bytes) and torch's fp32 GEMM.  (_forward_dense, the route without an
-            # epilogue, keeps its 16-bit matrix and GEMM: there the sum is rounded to 16 bits either way.)
-            y = torch.nn.functional.linear(x2.float(), self.dequantize(torch.float32)).reshape(shape)
-            if self.bias is not None:
-                y = y + self.bias
-            y = _torch_epilogue(y, act, residual, x.dtype)
-            return y if out is None else out.copy_(y)
-        self.__dict__["_last_route"] = "fused_ep"
-        dev = x.get_device()
-        if out is None:
-            out = torch.empty(shape, dtype=x.dtype, device=x.device)
-        e, ref, _keep = self._epilogue_descriptor(dev, quant_cuda._raw_stream(dev))
-        batch = 0 if rows == 1 else rows
-        ws = self._workspace(batch, self.qweight.device)
-        o = e.lin.op
-        o.batch, o.vec, o.mul = batch, x2.data_ptr(), out.data_ptr()
-        e.lin.workspace = ws.data_ptr()
-        e.residual = None if residual is None else residual.data_ptr()
-        e.act = _EP_ACT[act]
-        quant_cuda._launch(quant_cuda._fn(_EP_ENTRY[x.dtype]), dev, (ref,))
-        return out
+        return (*intake, shape)
 
     def forward(self, x: torch.Tensor, residual=None, out=None) -> torch.Tensor:
-        if self.act is not None or residual is not None or out is not None:
-            return self._forward_epilogue(x, residual, out)
-        if x.dtype not in _FUSED_ENTRY or not x.is_cuda:
+        act = self.act
+        ep = act is not None or residual is not None or out is not None  # (a call with an epilogue: sqllm_linear_ep)
+        dtype = x.dtype
+        kernel = dtype in _FRONT_DTYPES and x.is_cuda
+        if ep:
+            x2, rows, batch, shape = self._check_epilogue(x, act, residual, out)
+            if not kernel:
+                y = _torch_epilogue(QuantLinearLUT.forward(self, x), act, residual, dtype)
+                return y if out is None else out.copy_(y)
+            if not x2.is_contiguous():
+                x2 = x2.contiguous()
+        elif not kernel:
             return super().forward(x)
-        K, N = self.infeatures, self.outfeatures
-        if x.shape[-1] != K:
-            raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
-        x2 = x if x.dim() == 2 else x.reshape(-1, K)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        rows = x2.shape[0]
+        else:
+            x2, rows, batch = _rows_of(x, self.infeatures)
         if self.dense_min_rows is not None and rows >= self.dense_min_rows:
             self.__dict__["_last_route"] = "dense"
-            return self._forward_dense(x, x2)
-        self.__dict__["_last_route"] = "fused"
+            if not ep:
+                return self._forward_dense(x, x2)
+            y = _torch_epilogue(_fp32_sums((self,), x2.float())[0].reshape(shape), act, residual, dtype)
+            return y if out is None else out.copy_(y)
         dev = x.get_device()
-        out = torch.empty((rows, N), dtype=x.dtype, device=x.device)
-        lin, ref, _keep = self._descriptor(dev, quant_cuda._raw_stream(dev))
-        batch = 0 if rows == 1 else rows
-        ws = self._workspace(batch, self.qweight.device)  # (one buffer per device and stream, grown to the largest batch seen)
+        stream = quant_cuda._raw_stream(dev)
+        if ep:
+            self.__dict__["_last_route"] = "fused_ep"
+            if out is None:
+                out = torch.empty(shape, dtype=dtype, device=x.device)
+            e, ref, _keep = self._epilogue_descriptor(dev, stream)
+            lin = e.lin
+            e.residual = None if residual is None else residual.data_ptr()
+            e.act = _EP_ACT[act]
+        else:
+            self.__dict__["_last_route"] = "fused"
+            out = torch.empty((rows, self.outfeatures), dtype=dtype, device=x.device)
+            lin, ref, _keep = self._descriptor(dev, stream)
         o = lin.op
         o.batch, o.vec, o.mul = batch, x2.data_ptr(), out.data_ptr()
+        # (qweight straight from the buffer dict, as in _descriptor; `ws` lives until the launch is queued: a captured call's temporary)
+        ws = self._workspace(batch, self._buffers["qweight"].device, stream)
         lin.workspace = ws.data_ptr()
-        quant_cuda._launch(quant_cuda._fn(_FUSED_ENTRY[x.dtype]), dev, (ref,))
-        return out.reshape(*x.shape[:-1], N)
+        quant_cuda._launch(quant_cuda._fn(_FRONT_ENTRY["linear_ep" if ep else "linear", False, False, False, dtype]), dev, (ref,))
+        return out if ep else out.reshape(*x.shape[:-1], self.outfeatures)
 
 
 def fuse_quant_lut(module: nn.Module) -> int:
@@ -466,13 +541,6 @@ def fuse_quant_lut(module: nn.Module) -> int:
             m.__class__ = QuantLinearLUTFused
             n += 1
     return n
-
-
-_GATED_ENTRY = {torch.float16: "sqllm_gated_f16", torch.bfloat16: "sqllm_gated_bf16"}
-
-
-_GATED_NORM_ENTRY = {torch.float16: "sqllm_gated_norm_f16", torch.bfloat16: "sqllm_gated_norm_bf16"}
-_QKV_NORM_ENTRY = {torch.float16: "sqllm_qkv_rope_norm_f16", torch.bfloat16: "sqllm_qkv_rope_norm_bf16"}
 
 
 def _check_norm_weight(x: torch.Tensor, norm_weight: torch.Tensor, K: int, norm_eps: float) -> torch.Tensor:
@@ -492,16 +560,6 @@ def _torch_rmsnorm(x2: torch.Tensor, norm_weight: torch.Tensor, norm_eps: float)
     xf = x2.float()
     r = 1.0 / torch.sqrt(xf.pow(2).mean(dim=-1, keepdim=True) + norm_eps)
     return xf * norm_weight.float() * r
-
-
-def _norm_ref(cache: dict, key, norm_weight: torch.Tensor, norm_eps: float):
-    """The sqllm_rmsnorm of (device, stream), filled for this call; the ctypes reference to it."""
-    hit = cache.get(key)
-    if hit is None:
-        nm = _lib.SqllmRmsNorm()
-        hit = cache[key] = (nm, ctypes.byref(nm))
-    hit[0].weight, hit[0].eps = norm_weight.data_ptr(), norm_eps
-    return hit[1]
 
 
 class QuantGatedLUTFused(nn.Module):
@@ -559,70 +617,57 @@ class QuantGatedLUTFused(nn.Module):
     def _descriptor(self, dev: int, stream: int):
         """The sqllm_gated of (device, stream): the members' own pre-marshalled descriptors (QuantLinearLUTFused._descriptor:
         rebuilt when a buffer or a routing attribute of the member changes) copied side by side, rebuilt when either is."""
-        lg = QuantLinearLUTFused._descriptor(self.gate, dev, stream)
-        lu = QuantLinearLUTFused._descriptor(self.up, dev, stream)
-        cache = self.__dict__.setdefault("_desc", {})
-        hit = cache.get((dev, stream))
-        if hit is not None and hit[0] is lg[0] and hit[1] is lu[0]:
-            return hit[2]
+        return _composite_descriptor(self.__dict__.setdefault("_desc", {}), dev, stream, (self.gate, self.up), self._build)
+
+    @staticmethod
+    def _build(entries):
+        lg, lu = entries[0][0], entries[1][0]
         g = _lib.SqllmGated()
-        g.gate, g.up = lg[0].op, lu[0].op  # (copies)
+        g.gate, g.up = lg.op, lu.op  # (copies)
         g.gate.mul = g.up.mul = None
-        g.bias_gate, g.bias_up = lg[0].bias, lu[0].bias
+        g.bias_gate, g.bias_up = lg.bias, lu.bias
         g.act = _lib.ACT_SILU
-        entry = (g, ctypes.byref(g), (lg, lu))  # (the members' entries keep the folded CSRs alive)
-        cache[(dev, stream)] = (lg[0], lu[0], entry)
-        return entry
+        return g
 
     def forward(self, x: torch.Tensor, norm_weight=None, norm_eps: float = 1e-6) -> torch.Tensor:
         gate, up = self.gate, self.up
         K, N = gate.infeatures, gate.outfeatures
-        if norm_weight is not None:
-            if x.shape[-1] != K:
-                raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
+        norm = norm_weight is not None
+        if norm:
+            x2, rows, batch = _rows_of(x, K, False)
             norm_weight = _check_norm_weight(x, norm_weight, K, norm_eps)
-        if x.dtype not in _GATED_ENTRY or not x.is_cuda:
+        dtype = x.dtype
+        if dtype not in _FRONT_DTYPES or not x.is_cuda:
             self.__dict__["_last_route"] = "fallback"
-            if norm_weight is not None:  # (fp32 from end to end, one rounding)
-                xn = _torch_rmsnorm(x.reshape(-1, K), norm_weight, norm_eps)
-                y = torch.nn.functional.silu(QuantLinearLUT.forward(gate, xn).float()) * QuantLinearLUT.forward(up, xn).float()
-                return y.to(x.dtype).reshape(*x.shape[:-1], N)
-            return torch.nn.functional.silu(gate(x)) * up(x)
-        if x.shape[-1] != K:
-            raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
-        x2 = x if x.dim() == 2 else x.reshape(-1, K)
-        if not x2.is_contiguous():
+            if norm:  # (fp32 from end to end, one rounding)
+                xn = _torch_rmsnorm(x2, norm_weight, norm_eps)
+                y = F.silu(QuantLinearLUT.forward(gate, xn).float()) * QuantLinearLUT.forward(up, xn).float()
+                return y.to(dtype).reshape(*x.shape[:-1], N)
+            return F.silu(gate(x)) * up(x)
+        if not norm:
+            x2, rows, batch = _rows_of(x, K)
+        elif not x2.is_contiguous():
             x2 = x2.contiguous()
-        rows = x2.shape[0]
         dense_min_rows = getattr(gate, "dense_min_rows", None)
         if dense_min_rows is not None and rows >= dense_min_rows:
             self.__dict__["_last_route"] = "dense"
-            if norm_weight is not None:  # (fp32 from end to end: the kernel's one rounding is the only one here too)
-                xn = _torch_rmsnorm(x2, norm_weight, norm_eps)
-                sums = []
-                for m in (gate, up):
-                    t = torch.nn.functional.linear(xn, m.dequantize(torch.float32))
-                    sums.append(t if m.bias is None else t + m.bias)
-                return (torch.nn.functional.silu(sums[0]) * sums[1]).to(x.dtype).reshape(*x.shape[:-1], N)
+            if norm:
+                sums = _fp32_sums((gate, up), _torch_rmsnorm(x2, norm_weight, norm_eps))
+                return (F.silu(sums[0]) * sums[1]).to(dtype).reshape(*x.shape[:-1], N)
             dense = QuantLinearLUTFused._forward_dense
             # (the two 16-bit sums widened: activation and product in fp32, one rounding -- as the kernel evaluates them)
-            return (torch.nn.functional.silu(dense(gate, x, x2).float()) * dense(up, x, x2).float()).to(x.dtype)
-        self.__dict__["_last_route"] = "gated" if norm_weight is None else "gated_norm"
+            return (F.silu(dense(gate, x, x2).float()) * dense(up, x, x2).float()).to(dtype)
+        self.__dict__["_last_route"] = "gated_norm" if norm else "gated"
         dev = x.get_device()
-        out = torch.empty((rows, N), dtype=x.dtype, device=x.device)
+        out = torch.empty((rows, N), dtype=dtype, device=x.device)
         stream = quant_cuda._raw_stream(dev)
         g, ref, _keep = self._descriptor(dev, stream)
-        batch = 0 if rows == 1 else rows
-        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.gated_workspace_bytes(N, batch), gate.qweight.device,
-                           self.GRAPH_WS_MAX_BYTES)
         g.gate.batch = g.up.batch = batch
         g.gate.vec = g.up.vec = x2.data_ptr()
+        ws = _workspace_of(self, _lib.gated_workspace_bytes, (N, batch), gate._buffers["qweight"].device, stream)
         g.out, g.workspace = out.data_ptr(), ws.data_ptr()
-        if norm_weight is not None:
-            nref = _norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps)
-            quant_cuda._launch(quant_cuda._fn(_GATED_NORM_ENTRY[x.dtype]), dev, (ref, nref))
-        else:
-            quant_cuda._launch(quant_cuda._fn(_GATED_ENTRY[x.dtype]), dev, (ref,))
+        args = (ref, _norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps)) if norm else (ref,)
+        quant_cuda._launch(quant_cuda._fn(_FRONT_ENTRY["gated", norm, False, False, dtype]), dev, args)
         return out.reshape(*x.shape[:-1], N)
 
 
@@ -651,7 +696,6 @@ def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_pr
     return n
 
 
-_QKV_ENTRY = {torch.float16: "sqllm_qkv_rope_f16", torch.bfloat16: "sqllm_qkv_rope_bf16"}
 _ROPE_LAYOUT = {"half": _lib.ROPE_HALF, "interleaved": _lib.ROPE_INTERLEAVED}
 
 
@@ -688,10 +732,6 @@ def _torch_rope(s: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin
     return out.reshape(rows, N).to(dtype)
 
 
-_QKV_CACHE_ENTRY = {torch.float16: "sqllm_qkv_rope_cache_f16", torch.bfloat16: "sqllm_qkv_rope_cache_bf16"}
-_QKV_NORM_CACHE_ENTRY = {torch.float16: "sqllm_qkv_rope_norm_cache_f16", torch.bfloat16: "sqllm_qkv_rope_norm_cache_bf16"}
-_QKV_CACHE_FP8_ENTRY = {torch.float16: "sqllm_qkv_rope_cache_fp8_f16", torch.bfloat16: "sqllm_qkv_rope_cache_fp8_bf16"}
-_QKV_NORM_CACHE_FP8_ENTRY = {torch.float16: "sqllm_qkv_rope_norm_cache_fp8_f16", torch.bfloat16: "sqllm_qkv_rope_norm_cache_fp8_bf16"}
 FP8_KV_DTYPES = (torch.float8_e4m3fn, torch.uint8)  # what an fp8 KV cache may be held as: OCP e4m3fn elements, or their bytes
 FP8_KV_MAX = 448.0  # the largest finite e4m3fn value
 
@@ -871,18 +911,16 @@ class QuantQKVRopeFused(nn.Module):
     def _descriptor(self, dev: int, stream: int):
         """The sqllm_qkv_rope of (device, stream): the members' own pre-marshalled descriptors (QuantLinearLUTFused._descriptor)
         copied side by side, rebuilt when any of them is."""
-        ls = tuple(QuantLinearLUTFused._descriptor(m, dev, stream) for m in (self.q, self.k, self.v))
-        cache = self.__dict__.setdefault("_desc", {})
-        hit = cache.get((dev, stream))
-        if hit is not None and all(a is b[0] for a, b in zip(hit[0], ls)):
-            return hit[1]
+        return _composite_descriptor(self.__dict__.setdefault("_desc", {}), dev, stream, (self.q, self.k, self.v), self._build)
+
+    @staticmethod
+    def _build(entries):
+        lq, lk, lv = entries[0][0], entries[1][0], entries[2][0]
         r = _lib.SqllmQkvRope()
-        r.q, r.k, r.v = ls[0][0].op, ls[1][0].op, ls[2][0].op  # (copies)
+        r.q, r.k, r.v = lq.op, lk.op, lv.op  # (copies)
         r.q.mul = r.k.mul = r.v.mul = None
-        r.bias_q, r.bias_k, r.bias_v = ls[0][0].bias, ls[1][0].bias, ls[2][0].bias
-        entry = (r, ctypes.byref(r), ls)  # (the members' entries keep the folded CSRs alive)
-        cache[(dev, stream)] = (tuple(l[0] for l in ls), entry)
-        return entry
+        r.bias_q, r.bias_k, r.bias_v = lq.bias, lk.bias, lv.bias
+        return r
 
     def _check_cache(self, x: torch.Tensor, rows: int, k_cache, v_cache, slots, return_kv: bool) -> bool:
         """The cache arguments of forward: all three or none, and the views as the class docstring wants them."""
@@ -919,14 +957,13 @@ class QuantQKVRopeFused(nn.Module):
         k_scale, v_scale = self.__dict__.get("_fp8_scales", (None, None))  # (the module call's keyword arguments: __call__)
         q, k, v = self.q, self.k, self.v
         K, D, half = q.infeatures, self.head_dim, self.head_dim // 2
-        if x.shape[-1] != K:
-            raise ValueError(f"last dimension of x must be {K}, got {tuple(x.shape)}")
-        if norm_weight is not None:
+        x2, rows, batch = _rows_of(x, K, False)  # (the copy: behind the operand checks)
+        norm = norm_weight is not None
+        if norm:
             norm_weight = _check_norm_weight(x, norm_weight, K, norm_eps)
-        x2 = x if x.dim() == 2 else x.reshape(-1, K)
-        rows = x2.shape[0]
         cached = self._check_cache(x, rows, k_cache, v_cache, slots, return_kv)
-        fp8 = cached and k_cache.dtype in FP8_KV_DTYPES and k_cache.dtype != x.dtype
+        dtype = x.dtype
+        fp8 = cached and k_cache.dtype in FP8_KV_DTYPES and k_cache.dtype != dtype
         k_scale, v_scale = _check_fp8_scales(fp8, k_scale, v_scale)
         for name, t in (("cos", cos), ("sin", sin)):
             if t.dim() != 2 or t.shape[1] != half or t.shape[0] < 1 or t.shape != cos.shape or t.device != x.device:
@@ -935,27 +972,22 @@ class QuantQKVRopeFused(nn.Module):
             raise ValueError(f"positions must be {rows} int32 (or int64) values on {x.device}")
         lead = x.shape[:-1]
         dense_min_rows = getattr(q, "dense_min_rows", None)
-        kernel = x.dtype in _QKV_ENTRY and x.is_cuda
+        kernel = dtype in _FRONT_DTYPES and x.is_cuda
+        if kernel and not x2.is_contiguous():
+            x2 = x2.contiguous()
         if not kernel or (dense_min_rows is not None and rows >= dense_min_rows):
             pos = positions.reshape(-1)
-            if kernel:
+            if kernel:  # (fp32 from end to end, as the epilogue's dense route)
                 self.__dict__["_last_route"] = "dense"
-                if not x2.is_contiguous():
-                    x2 = x2.contiguous()
-                # fp32 from end to end, as the epilogue's dense route: the ONE rounding of the kernel is the only one here too
-                sums = []
-                xin = x2.float() if norm_weight is None else _torch_rmsnorm(x2, norm_weight, norm_eps)
-                for m in (q, k, v):
-                    s = torch.nn.functional.linear(xin, m.dequantize(torch.float32))
-                    sums.append(s if m.bias is None else s + m.bias)
+                sums = _fp32_sums((q, k, v), x2.float() if not norm else _torch_rmsnorm(x2, norm_weight, norm_eps))
             else:
                 self.__dict__["_last_route"] = "fallback"
-                xin = x2 if norm_weight is None else _torch_rmsnorm(x2, norm_weight, norm_eps)  # (fp32 sums from fp32 xn)
+                xin = x2 if not norm else _torch_rmsnorm(x2, norm_weight, norm_eps)  # (fp32 sums from fp32 xn)
                 sums = [QuantLinearLUT.forward(m, xin) for m in (q, k, v)]
-            oq = _torch_rope(sums[0], pos, cos, sin, D, self.layout, x.dtype)
+            oq = _torch_rope(sums[0], pos, cos, sin, D, self.layout, dtype)
             ok32 = _torch_rope(sums[1], pos, cos, sin, D, self.layout, torch.float32)  # (the value before its one rounding)
-            ok = ok32.to(x.dtype)
-            ov = sums[2].to(x.dtype)
+            ok = ok32.to(dtype)
+            ov = sums[2].to(dtype)
             if cached:
                 if fp8:  # (the same fp32 values, rounded once, straight to fp8)
                     _torch_cache_write_fp8(k_cache, slots, ok32, k_scale)
@@ -966,60 +998,30 @@ class QuantQKVRopeFused(nn.Module):
                 if not return_kv:
                     return oq.reshape(*lead, -1), None, None
             return oq.reshape(*lead, -1), ok.reshape(*lead, -1), ov.reshape(*lead, -1)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
         if cos.dtype != torch.float32 or sin.dtype != torch.float32 or not cos.is_contiguous() or not sin.is_contiguous():
             raise ValueError("cos and sin must be contiguous fp32 tensors")
-        pos = positions.reshape(-1)
-        if pos.dtype != torch.int32:
-            pos = pos.to(torch.int32)  # (a kernel)
-        if not pos.is_contiguous():
-            pos = pos.contiguous()
-        self.__dict__["_last_route"] = "qkv_rope" if norm_weight is None else "qkv_rope_norm"
+        pos = _int32_vector(positions)
+        self.__dict__["_last_route"] = "qkv_rope_norm" if norm else "qkv_rope"
         dev = x.get_device()
-        outs = [torch.empty((rows, m.outfeatures), dtype=x.dtype, device=x.device) if return_kv or m is q else None for m in (q, k, v)]
+        outs = [torch.empty((rows, m.outfeatures), dtype=dtype, device=x.device) if return_kv or m is q else None for m in (q, k, v)]
         stream = quant_cuda._raw_stream(dev)
         r, ref, _keep = self._descriptor(dev, stream)
-        batch = 0 if rows == 1 else rows
-        ws = _workspace_of(self.__dict__.setdefault("_ws", {}),
-                           _lib.qkv_rope_workspace_bytes(q.outfeatures, k.outfeatures, v.outfeatures, batch), q.qweight.device,
-                           self.GRAPH_WS_MAX_BYTES)
         r.q.batch = r.k.batch = r.v.batch = batch
         r.q.vec = r.k.vec = r.v.vec = x2.data_ptr()
         r.out_q, r.out_k, r.out_v = [o.data_ptr() if o is not None else None for o in outs]
         r.cos, r.sin, r.positions = cos.data_ptr(), sin.data_ptr(), pos.data_ptr()
         r.n_pos, r.head_dim, r.layout = cos.shape[0], D, _ROPE_LAYOUT[self.layout]
+        ws = _workspace_of(self, _lib.qkv_rope_workspace_bytes, (q.outfeatures, k.outfeatures, v.outfeatures, batch),
+                           q._buffers["qweight"].device, stream)
         r.workspace = ws.data_ptr()
-        nref = None if norm_weight is None else _norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps)
+        args = (ref,)
+        if norm:
+            args += (_norm_ref(self.__dict__.setdefault("_norm", {}), (dev, stream), norm_weight, norm_eps),)
         if cached:
-            sl = slots.reshape(-1)
-            if sl.dtype != torch.int32:
-                sl = sl.to(torch.int32)  # (a kernel)
-            if not sl.is_contiguous():
-                sl = sl.contiguous()
-            kcs = self.__dict__.setdefault("_kv8" if fp8 else "_kv", {})
-            hit = kcs.get((dev, stream))
-            if hit is None:
-                c = _lib.SqllmKvCacheFp8() if fp8 else _lib.SqllmKvCache()
-                hit = kcs[(dev, stream)] = (c, ctypes.byref(c))
-            c, cref = hit
-            c.k_cache, c.v_cache, c.slots = k_cache.data_ptr(), v_cache.data_ptr(), sl.data_ptr()
-            c.n_slots, c.slot_stride = k_cache.shape[0], k_cache.stride(0)
-            c.head_stride = k_cache.stride(1) if k_cache.shape[1] > 1 else D  # (one head: its stride is anything, and never used)
-            if fp8:
-                c.k_scale, c.v_scale = k_scale, v_scale
-                if nref is not None:
-                    quant_cuda._launch(quant_cuda._fn(_QKV_NORM_CACHE_FP8_ENTRY[x.dtype]), dev, (ref, nref, cref))
-                else:
-                    quant_cuda._launch(quant_cuda._fn(_QKV_CACHE_FP8_ENTRY[x.dtype]), dev, (ref, cref))
-            elif nref is not None:
-                quant_cuda._launch(quant_cuda._fn(_QKV_NORM_CACHE_ENTRY[x.dtype]), dev, (ref, nref, cref))
-            else:
-                quant_cuda._launch(quant_cuda._fn(_QKV_CACHE_ENTRY[x.dtype]), dev, (ref, cref))
-        elif nref is not None:
-            quant_cuda._launch(quant_cuda._fn(_QKV_NORM_ENTRY[x.dtype]), dev, (ref, nref))
-        else:
-            quant_cuda._launch(quant_cuda._fn(_QKV_ENTRY[x.dtype]), dev, (ref,))
+            sl = _int32_vector(slots)
+            kv = self.__dict__.setdefault("_kv8" if fp8 else "_kv", {})
+            args += (_kv_ref(kv, (dev, stream), k_cache, v_cache, sl, D, (k_scale, v_scale) if fp8 else None),)
+        quant_cuda._launch(quant_cuda._fn(_FRONT_ENTRY["qkv_rope", norm, cached, fp8, dtype]), dev, args)
         return tuple(o.reshape(*lead, -1) if o is not None else None for o in outs)
 
 
@@ -1053,15 +1055,6 @@ _ATTN_KINDS = (
     (_lib.SqllmAttnAppendFp8, {torch.float16: "sqllm_attn_append_fp8_f16", torch.bfloat16: "sqllm_attn_append_fp8_bf16"}),
 )
 _ATTN_DTYPES = (torch.float16, torch.bfloat16)
-
-
-def _int32_vector(t: torch.Tensor) -> torch.Tensor:
-    """`t` as a contiguous int32 vector; what already is one is returned as it is, so that a captured graph follows it."""
-    if t.dim() != 1:
-        t = t.reshape(-1)
-    if t.dtype != torch.int32:
-        t = t.to(torch.int32)  # (a kernel)
-    return t if t.is_contiguous() else t.contiguous()
 
 
 ATTN_PARTITION = _lib.ATTN_PARTITION  # keys per partition of the decode attention's kernel (SQLLM_ATTN_PARTITION)
@@ -1313,8 +1306,7 @@ class DecodeAttention(nn.Module):
         dev = q2.get_device()
         o = out if out is not None else torch.empty((rows, W), dtype=q2.dtype, device=q2.device)
         stream = quant_cuda._raw_stream(dev)
-        ws = _workspace_of(self.__dict__.setdefault("_ws", {}), _lib.attn_decode_workspace_bytes(rows, HQ, D, max_blocks, bs), q2.device,
-                           self.GRAPH_WS_MAX_BYTES)
+        ws = _workspace_of(self, _lib.attn_decode_workspace_bytes, (rows, HQ, D, max_blocks, bs), q2.device)
         struct, entries = _ATTN_KINDS[kind]
         descs = self.__dict__.setdefault("_desc", {})
         hit = descs.get((kind, dev, stream))
