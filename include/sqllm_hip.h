@@ -691,6 +691,51 @@ int sqllm_attn_append_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t str
 int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sliding-window decode attention: ONE new query per sequence, attending the LAST `window` keys the cache holds for that
+ * sequence (Mistral's sliding_window).  The descriptors are sqllm_attn_decode and sqllm_attn_decode_fp8, unchanged; `window`
+ * is a HOST field of the call.
+ *
+ *   - Keys.  A row of length L = seq_lens[b] with 1 <= L <= max_blocks * block_size attends the keys p in [lo, L),
+ *     lo = max(0, L - window): the query's own key included, `window` keys in all -- Hugging Face's Mistral mask
+ *     kv_idx > q_idx - sliding_window.  Addressing is sqllm_attn_decode's.
+ *   - Values.  The formulas of sqllm_attn_decode (for the byte caches: of sqllm_attn_decode_fp8) over those keys only.
+ *   - Order.  The partitions stay the ABSOLUTE key ranges [256 i, 256 i + 256); only the partitions lo / 256 ..
+ *     ceil(L / 256) - 1 take part, combined in ascending order; inside a partition the order depends on head_dim,
+ *     n_q_heads / n_kv_heads and the key's index alone, as without a window; keys below lo are left out of the first partition
+ *     the way keys at or above L are left out of the last.  Hence, bit for bit:
+ *       (a) a row with L <= window holds EXACTLY THE BITS sqllm_attn_decode_* (sqllm_attn_decode_fp8_*) gives it;
+ *       (b) where lo is a multiple of both 256 and block_size, the row holds exactly the bits the entry without a window gives
+ *           a row of length L - lo over the table row advanced by lo / block_size entries.
+ *   - What is read.  Only the table entries of blocks that hold an attended key: blocks lo / block_size ..
+ *     (L - 1) / block_size.  Entries below them may hold anything (-1, a recycled block, an id far outside the cache) and never
+ *     make a row NaN; slots of keys below lo never influence a result, whatever bits they hold.  A caller may free or reuse the
+ *     blocks behind the window; a table whose logical blocks repeat over a ring of ceil(window / block_size) + 1 physical
+ *     blocks is a rolling buffer, with no further support.
+ *   - L <= 0: the row of out is +0.  L > max_blocks * block_size: NaN.  A USED table entry outside [0, n_slots): NaN, and
+ *     nothing of the caches is read.  NaN and infinities propagate as in sqllm_attn_decode, over the attended keys only.
+ *     Capture, determinism run to run and row by row, and launch geometry from host fields only stay as they are.
+ *   - Geometry.  A window touches at most  win_parts = min(n_parts, (window - 1 + 255) / 256 + 1)  partitions (64-bit: window
+ *     may be INT32_MAX), n_parts = ceil(max_blocks * block_size / 256).  The partial launch has win_parts workgroups per
+ *     (kv head, row); workgroup x of row b serves the absolute partition lo_b / 256 + x, lo_b from seq_lens on the device.  The
+ *     workspace holds (max, sum, acc[head_dim]) in fp32 per (row, query head, RELATIVE partition):
+ *     sqllm_attn_window_workspace_bytes() = batch * n_q_heads * win_parts * (head_dim + 2) * 4 bytes, never more than
+ *     sqllm_attn_decode_workspace_bytes(); 4-byte aligned, CONTENTS IRRELEVANT.  TWO kernel nodes, ONE when win_parts == 1.
+ *
+ * Served shapes and rejections are sqllm_attn_decode's (sqllm_attn_decode_fp8's), with their codes and in their order;
+ * window < 1 counts among the counts (SQLLM_E_SHAPE), before the device is touched; the workspace that must not overlap is
+ * the windowed one.  A library without the window kernels answers hipErrorNotSupported, never with the kernels above.
+ * Not covered: a window for several new tokens per sequence (sqllm_attn_append_*; expand the rows as that block defines them
+ * and call these entries), attention sinks, soft-capping, ALiBi, a wrap-around table mode.
+ * ------------------------------------------------------------------------------------------- */
+int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int32_t head_dim, int32_t max_blocks, int32_t block_size,
+                                          int32_t window);
+int sqllm_attn_decode_window_f16(const sqllm_attn_decode* a, int32_t window, sqllm_stream_t stream);
+int sqllm_attn_decode_window_bf16(const sqllm_attn_decode* a, int32_t window, sqllm_stream_t stream);
+/* the suffix names the type of q and out */
+int sqllm_attn_decode_window_fp8_f16(const sqllm_attn_decode_fp8* a, int32_t window, sqllm_stream_t stream);
+int sqllm_attn_decode_window_fp8_bf16(const sqllm_attn_decode_fp8* a, int32_t window, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

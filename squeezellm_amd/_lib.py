@@ -233,6 +233,11 @@ SIGNATURES = {
     "sqllm_attn_append_bf16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_append_fp8_f16": [POINTER(SqllmAttnAppendFp8), P],
     "sqllm_attn_append_fp8_bf16": [POINTER(SqllmAttnAppendFp8), P],
+    "sqllm_attn_window_workspace_bytes": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32],
+    "sqllm_attn_decode_window_f16": [POINTER(SqllmAttnDecode), c_int32, P],
+    "sqllm_attn_decode_window_bf16": [POINTER(SqllmAttnDecode), c_int32, P],
+    "sqllm_attn_decode_window_fp8_f16": [POINTER(SqllmAttnDecodeFp8), c_int32, P],
+    "sqllm_attn_decode_window_fp8_bf16": [POINTER(SqllmAttnDecodeFp8), c_int32, P],
     "sqllm_abi_version": [],
     "sqllm_error_string": [c_int],
     "sqllm_set_option": [c_char_p, c_int],
@@ -282,7 +287,8 @@ def load() -> ctypes.CDLL:
         fn.restype = (c_char_p if name == "sqllm_error_string" else
                       ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes",
                                                "sqllm_select_workspace_bytes", "sqllm_gated_workspace_bytes",
-                                               "sqllm_qkv_rope_workspace_bytes", "sqllm_attn_decode_workspace_bytes") else c_int)
+                                               "sqllm_qkv_rope_workspace_bytes", "sqllm_attn_decode_workspace_bytes",
+                                               "sqllm_attn_window_workspace_bytes") else c_int)
     if lib.sqllm_abi_version() != 1:
         raise RuntimeError(f"libsqllm_hip.so ABI {lib.sqllm_abi_version()} != 1 expected by this package")
     _lib = lib
@@ -341,6 +347,11 @@ def qkv_rope_workspace_bytes(n_q: int, n_k: int, n_v: int, batch: int = 0) -> in
 def attn_decode_workspace_bytes(batch: int, n_q_heads: int, head_dim: int, max_blocks: int, block_size: int) -> int:
     """Bytes of device memory (contents irrelevant) one decode attention of these shapes needs (no GPU needed)."""
     return int(load().sqllm_attn_decode_workspace_bytes(batch, n_q_heads, head_dim, max_blocks, block_size))
+
+
+def attn_window_workspace_bytes(batch: int, n_q_heads: int, head_dim: int, max_blocks: int, block_size: int, window: int) -> int:
+    """Bytes of device memory (contents irrelevant) one sliding-window decode attention of these shapes needs (no GPU needed)."""
+    return int(load().sqllm_attn_window_workspace_bytes(batch, n_q_heads, head_dim, max_blocks, block_size, window))
 
 
 def workspace_bytes(bits: int, K: int, N: int, batch: int, nnz: int = 0, topX: int = 0, n_ops: int = 1) -> int:

@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "sqllm_nuq.hip", "sqllm_dequant.hip", "sqllm_encode.hip", "sqllm_select.hip", "sqllm_linear_bf16.hip", "sqllm_linear_gated.hip", "sqllm_linear_ep.hip", "sqllm_linear_qkv.hip",
            "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip", "sqllm_linear_qkv_cache.hip", "sqllm_linear_qkv_norm_cache.hip", "sqllm_attn_decode.hip",
            "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode_fp8.hip",
-           "sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip", "sqllm_capi.hip"]
+           "sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip", "sqllm_attn_window.hip", "sqllm_attn_window_fp8.hip", "sqllm_capi.hip"]
 # measured-and-not-adopted kernels (round 3: the streaming batch-1 kernel, the column-pair-table kernel; round 4: the
 # dependency-gated persistent pass) and the host code that routes to them: csrc/experimental/, part of the MEASUREMENT
 # library only (options "stream" / "pair4", entry points sqllm_pass_*)

@@ -1,5 +1,5 @@
-// sqllm_attn.h -- what the four decode-attention kernel files share (sqllm_attn_decode.hip, sqllm_attn_decode_fp8.hip,
-// sqllm_attn_append.hip, sqllm_attn_append_fp8.hip): the lane helpers for 16-bit elements and for byte caches, the length of an append
+// sqllm_attn.h -- what the six decode-attention kernel files share (sqllm_attn_decode.hip, sqllm_attn_decode_fp8.hip,
+// sqllm_attn_append.hip, sqllm_attn_append_fp8.hip, sqllm_attn_window.hip, sqllm_attn_window_fp8.hip): the lane helpers for 16-bit elements and for byte caches, the length of an append
 // row and phase 0 of the append kernels, and the launch ladder launch_attn<TAG>.  NOT shared: the bodies of the partial kernels
 // and of the combines, which stay copies of each other ("Not shared either").
 #pragma once
@@ -206,7 +206,7 @@ __device__ __forceinline__ bool append_phase0(const AttnAppendArgs& a, int part,
 }
 
 // ------------------------------------------------------------------------------------------------
-// The launch ladder of the four kernel files, written once (as launch_front<TAG> of sqllm_fused.h): {_Float16, __bf16} x head_dim
+// The launch ladder of the six kernel files, written once (as launch_front<TAG> of sqllm_fused.h): {_Float16, __bf16} x head_dim
 // 64 / 128 x group class 1 / 2 / 3-4 / 8 -> one instantiation of the partial kernel TAG names; with more than one partition the
 // combine behind it.  A kernel file says
 //   struct MyAttn : AttnOneQuery {   // or AttnTokens: several new tokens per sequence
@@ -239,6 +239,16 @@ struct AttnTokens {
   static dim3 grid(const Args& k, const AttnCall& c) { return dim3(k.n_parts, c.n_kv_heads, k.batch * ((k.q_len * k.group + GC - 1) / GC)); }
   static bool has_combine() { return g_launch_attn_append_combine != nullptr; }
   static hipError_t combine(const Args& k, const AttnCall& c, hipStream_t stream) { return g_launch_attn_append_combine(k, c.head_dim, c.bf16, stream); }
+};
+// one query per sequence over the last `window` keys: win_parts (k.n_parts) workgroups per (kv head, row), the window combine
+struct AttnWindowQuery {
+  typedef AttnWindowArgs Args;
+  static bool served(const AttnCall& c) { return c.window >= 1 && c.q_len == 0; }
+  static int heads(const Args& k) { return k.group; }
+  template <int GC>
+  static dim3 grid(const Args& k, const AttnCall& c) { return dim3(k.n_parts, c.n_kv_heads, c.batch); }
+  static bool has_combine() { return g_launch_attn_window_combine != nullptr; }
+  static hipError_t combine(const Args& k, const AttnCall& c, hipStream_t stream) { return g_launch_attn_window_combine(k, c.head_dim, c.bf16, c.batch, stream); }
 };
 
 template <typename TAG, int D, int GC, typename OT>

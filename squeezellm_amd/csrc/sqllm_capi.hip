@@ -20,6 +20,8 @@ FrontLauncher g_launch_front[kFrontKinds] = {};  // each slot set by its kernel 
 AttnLauncher g_launch_attn[kAttnKinds] = {};  // each slot set by its kernel file (sqllm_attn_decode.hip ... sqllm_attn_append_fp8.hip)
 hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
 hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
+AttnLauncher g_launch_attn_window[2] = {};  // [0] set by sqllm_attn_window.hip, [1] by sqllm_attn_window_fp8.hip
+hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_window.hip
 }
 
 namespace sqllm_host {
@@ -1552,17 +1554,34 @@ int64_t sqllm_attn_decode_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
   return (int64_t)batch * n_q_heads * attn_parts(max_blocks, block_size) * (head_dim + 2) * 4;
 }
 
-// The eight attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
+// The partitions a window of `window` keys can touch (sqllm_attn_decode_window_*): one more than it fills when it starts inside
+// one, never more than the table has.  64-bit: window may be INT32_MAX.
+static int64_t attn_window_parts(int32_t max_blocks, int32_t block_size, int32_t window) {
+  const int64_t n_parts = attn_parts(max_blocks, block_size);
+  const int64_t touched = ((int64_t)window - 1 + SQLLM_ATTN_PARTITION - 1) / SQLLM_ATTN_PARTITION + 1;
+  return touched < n_parts ? touched : n_parts;
+}
+
+int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int32_t head_dim, int32_t max_blocks, int32_t block_size, int32_t window) {
+  if (batch < 1 || n_q_heads < 1 || head_dim < 1 || max_blocks < 1 || block_size < 1 || window < 1) return 0;
+  // per (row, query head, RELATIVE partition): acc[head_dim], max, sum
+  return (int64_t)batch * n_q_heads * attn_window_parts(max_blocks, block_size, window) * (head_dim + 2) * 4;
+}
+
+// The twelve attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
 // follows them is passed on by each entry:
 //   `kv_scales` (the fp8 entries): {k_scale, v_scale} of the descriptor -- the caches hold 1-byte e4m3fn elements, their strides
 //     and extents count bytes and they need no alignment; the scales are judged last.  NULL: 16-bit caches.
 //   `tokens` (sqllm_attn_append_*): lead.batch counts sequences of q_len rows each, `q_lens` (or NULL) their real tokens.  NULL:
 //     the one-query entries -- so a q_len below 1 in an append descriptor is a count < 1, never the one-query call.
+//   `window` (sqllm_attn_decode_window_*): the keys [max(0, L - *window), L) of every row; a count as the others.  The launch and
+//     the workspace are sized by the partitions a window can touch, and the call goes to g_launch_attn_window.  NULL: no window.
 struct AttnTokensTail {
   const int32_t* q_lens;
   int32_t q_len;
 };
-static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, bool bf16, const float* kv_scales, const AttnTokensTail* tokens) {
+static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, bool bf16, const float* kv_scales, const AttnTokensTail* tokens,
+                       const int32_t* window = nullptr) {
   const sqllm_attn_decode* const a = &lead;
   const bool append = tokens != nullptr;
   const int32_t q_len = append ? tokens->q_len : 0;
@@ -1571,7 +1590,7 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   if (!a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || !a->workspace) return SQLLM_E_NULL;
   const int64_t D = a->head_dim;
   if (a->batch < 1 || a->n_q_heads < 1 || a->n_kv_heads < 1 || D < 1 || a->n_slots < 1 || a->block_size < 1 || a->max_blocks < 1 ||
-      a->table_stride < 1 || (append && q_len < 1))
+      a->table_stride < 1 || (append && q_len < 1) || (window && *window < 1))
     return SQLLM_E_SHAPE;
   const int64_t rows = append ? (int64_t)a->batch * q_len : a->batch;  // of q, out and the workspace
   const int64_t width = (int64_t)a->n_q_heads * D;
@@ -1589,7 +1608,8 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   const unsigned __int128 out_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->out_stride + (uint64_t)width;
   if (extent >= ((unsigned __int128)1 << 62) || q_extent >= ((unsigned __int128)1 << 62) || out_extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
   if (!__builtin_isfinite(a->scale)) return SQLLM_E_OPTION;
-  const int64_t ws_bytes = sqllm_attn_decode_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
+  const int64_t ws_bytes = window ? sqllm_attn_window_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size, *window)
+                                  : sqllm_attn_decode_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
   const void* const in[6] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens, q_lens};
   const int64_t in_bytes[6] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
                                4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch, 4 * (int64_t)a->batch};
@@ -1623,7 +1643,7 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.block_size = a->block_size;
   c.table_stride = a->table_stride;
   c.capacity = (int)attn_capacity(a->max_blocks, a->block_size);
-  c.n_parts = (int)attn_parts(a->max_blocks, a->block_size);
+  c.n_parts = (int)(window ? attn_window_parts(a->max_blocks, a->block_size, *window) : attn_parts(a->max_blocks, a->block_size));
   c.slot_stride = a->slot_stride;
   c.head_stride = a->head_stride;
   c.q_stride = a->q_stride;
@@ -1634,7 +1654,9 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.v_scale = kv_scales ? kv_scales[1] : 1.0f;
   c.q_lens = q_lens;
   c.q_len = q_len;  // (0: one query per sequence; an append call has passed q_len >= 1 above)
-  const sqllm::AttnLauncher launch = sqllm::g_launch_attn[sqllm::attn_kind(c)];
+  c.window = window ? *window : 0;
+  // (a window has a table of its own: a null slot there is an error, never the kernels without a window)
+  const sqllm::AttnLauncher launch = window ? sqllm::g_launch_attn_window[c.fp8 ? 1 : 0] : sqllm::g_launch_attn[sqllm::attn_kind(c)];
   return static_cast<int>(launch ? launch(c, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
 }
 
@@ -1663,9 +1685,9 @@ static sqllm_attn_decode attn_lead(const A* p) {
   return lead;
 }
 extern "C++" template <typename A>
-static int launch_attn_fp8(const A* p, sqllm_stream_t stream, bool bf16, const AttnTokensTail* tokens) {
+static int launch_attn_fp8(const A* p, sqllm_stream_t stream, bool bf16, const AttnTokensTail* tokens, const int32_t* window = nullptr) {
   const float kv_scales[2] = {p->k_scale, p->v_scale};
-  return launch_attn(attn_lead(p), stream, bf16, kv_scales, tokens);
+  return launch_attn(attn_lead(p), stream, bf16, kv_scales, tokens, window);
 }
 extern "C++" template <typename A>
 static AttnTokensTail attn_tokens(const A* p) { return {p->q_lens, p->q_len}; }
@@ -1681,6 +1703,18 @@ int sqllm_attn_decode_fp8_f16(const sqllm_attn_decode_fp8* a, sqllm_stream_t str
 }
 int sqllm_attn_decode_fp8_bf16(const sqllm_attn_decode_fp8* a, sqllm_stream_t stream) {
   return a ? launch_attn_fp8(a, stream, true, nullptr) : SQLLM_E_NULL;
+}
+int sqllm_attn_decode_window_f16(const sqllm_attn_decode* a, int32_t window, sqllm_stream_t stream) {
+  return a ? launch_attn(*a, stream, false, nullptr, nullptr, &window) : SQLLM_E_NULL;
+}
+int sqllm_attn_decode_window_bf16(const sqllm_attn_decode* a, int32_t window, sqllm_stream_t stream) {
+  return a ? launch_attn(*a, stream, true, nullptr, nullptr, &window) : SQLLM_E_NULL;
+}
+int sqllm_attn_decode_window_fp8_f16(const sqllm_attn_decode_fp8* a, int32_t window, sqllm_stream_t stream) {
+  return a ? launch_attn_fp8(a, stream, false, nullptr, &window) : SQLLM_E_NULL;
+}
+int sqllm_attn_decode_window_fp8_bf16(const sqllm_attn_decode_fp8* a, int32_t window, sqllm_stream_t stream) {
+  return a ? launch_attn_fp8(a, stream, true, nullptr, &window) : SQLLM_E_NULL;
 }
 static int launch_attn_append(const sqllm_attn_append* a, sqllm_stream_t stream, bool bf16) {
   if (!a) return SQLLM_E_NULL;

@@ -230,6 +230,9 @@ struct AttnCall {
   // several new tokens per sequence (sqllm_attn_append_*): `batch` counts SEQUENCES; q, out and the workspace have batch * q_len rows
   const int* q_lens;       // int32 [batch], device memory, or null: q_len real tokens everywhere
   int q_len;               // rows per sequence, 1 to 16; 0: the one-query entries
+  // a sliding window (sqllm_attn_decode_window_*): the keys [max(0, L - window), L) of a row of length L; n_parts then holds
+  // win_parts, the partitions a window can touch, and the workspace is laid out by it
+  int window;              // at least 1; 0: the entries without a window
 };
 enum AttnKind { kAttnDecode, kAttnDecodeFp8, kAttnAppend, kAttnAppendFp8, kAttnKinds };
 inline AttnKind attn_kind(const AttnCall& c) {
@@ -276,7 +279,28 @@ struct AttnAppendArgs {
   int q_len;
   float scale;
 };
+// The window kernels' argument (sqllm_attn_window.hip, sqllm_attn_window_fp8.hip): AttnArgs' fields and the window.  n_parts is
+// win_parts here: the workgroups per (kv head, row) and the partials per (row, query head), indexed RELATIVE to the row's first
+// attended partition.
+struct AttnWindowArgs {
+  const void* q;
+  void* out;
+  const void* k_cache;
+  const void* v_cache;
+  const int* block_table;
+  const int* seq_lens;
+  float* ws_acc;  // [batch, n_q_heads, n_parts, head_dim]
+  float* ws_ml;   // [batch, n_q_heads, n_parts, 2]
+  long long q_stride, out_stride;
+  unsigned slot_stride, head_stride;  // (below 2^32 wherever they are multiplied: checked by the host)
+  int n_q_heads, group, n_slots, block_size, table_stride;
+  int capacity;  // min(max_blocks * block_size, INT32_MAX)
+  int n_parts;   // win_parts
+  int window;
+  float scale;
+};
 inline void attn_token_args(AttnArgs&, const AttnCall&) {}
+inline void attn_token_args(AttnWindowArgs& k, const AttnCall& c) { k.window = c.window; }
 inline void attn_token_args(AttnAppendArgs& k, const AttnCall& c) {
   k.q_lens = c.q_lens;
   k.batch = c.batch;
@@ -313,6 +337,11 @@ inline ARGS make_attn_args(const AttnCall& c) {
 // the byte caches' partials are followed by the same kernels.
 extern hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
 extern hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream);
+// The window entries (sqllm_attn_decode_window_*): a table of their own beside g_launch_attn, [0] the 16-bit caches
+// (sqllm_attn_window.hip), [1] the byte caches (sqllm_attn_window_fp8.hip), and the window combine both reach through its hook.
+// Null until the file is linked in: hipErrorNotSupported, never the kernels without a window.
+extern AttnLauncher g_launch_attn_window[2];
+extern hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

@@ -1054,6 +1054,11 @@ _ATTN_KINDS = (
     (_lib.SqllmAttnAppend, {torch.float16: "sqllm_attn_append_f16", torch.bfloat16: "sqllm_attn_append_bf16"}),
     (_lib.SqllmAttnAppendFp8, {torch.float16: "sqllm_attn_append_fp8_f16", torch.bfloat16: "sqllm_attn_append_fp8_bf16"}),
 )
+# ... and with a sliding window (DecodeAttention(..., window=)): the one-query descriptors, kind = (fp8 cache)
+_ATTN_WINDOW_ENTRIES = (
+    {torch.float16: "sqllm_attn_decode_window_f16", torch.bfloat16: "sqllm_attn_decode_window_bf16"},
+    {torch.float16: "sqllm_attn_decode_window_fp8_f16", torch.bfloat16: "sqllm_attn_decode_window_fp8_bf16"},
+)
 _ATTN_DTYPES = (torch.float16, torch.bfloat16)
 
 
@@ -1092,12 +1097,30 @@ def static_cache_blocks(batch: int, n_kv_heads: int, device=None) -> torch.Tenso
     return (torch.arange(int(batch), dtype=torch.int32, device=device) * int(n_kv_heads)).reshape(-1, 1)
 
 
+def ring_block_table(batch: int, window: int, block_size: int, max_len: int, device=None) -> torch.Tensor:
+    """The int32 block table [batch, ceil(max_len / block_size)] of a ROLLING buffer for DecodeAttention(..., window=window):
+    logical block j of row b is physical block b * R + j % R, with R = ceil(window / block_size) + 1, so a sequence of any
+    length up to max_len lives in R blocks (batch * R blocks in all; the front writes position p of row b into slot
+    table[b, p // block_size] * block_size + p % block_size, as with any table).  Why R suffices: writing position p overwrites
+    position p - R * block_size, and R * block_size >= window + block_size, so with L = p + 1 keys that position is below
+    lo = L - window -- it has left the window, at this step and at every later one; the blocks below lo / block_size are never
+    read (include/sqllm_hip.h, sliding-window decode attention).  Without a window the table is wrong: old keys are gone."""
+    batch, window, block_size, max_len = int(batch), int(window), int(block_size), int(max_len)
+    if batch < 1 or window < 1 or block_size < 1 or max_len < 1:
+        raise ValueError(f"batch, window, block_size and max_len must be positive, got {batch}, {window}, {block_size}, {max_len}")
+    R = (window + block_size - 1) // block_size + 1
+    j = torch.arange((max_len + block_size - 1) // block_size, dtype=torch.int32, device=device)
+    b = torch.arange(batch, dtype=torch.int32, device=device)
+    return (b[:, None] * R + (j % R)[None, :]).contiguous()
+
+
 def _torch_attn_decode(q, k_cache, v_cache, block_table, seq_lens, block_size, n_heads, n_kv_heads, head_dim, scale, dtype,
-                       k_scale=None, v_scale=None):
+                       k_scale=None, v_scale=None, window=None):
     """The formulas of sqllm_attn_decode (include/sqllm_hip.h) in torch: fp32, rounded once to `dtype`; the +0 row, the NaN
     rows; unaddressed slots never enter a result.  q: [rows, n_heads * head_dim].  With `k_scale` and `v_scale` the caches
     hold e4m3fn bytes (sqllm_attn_decode_fp8): scale * k_scale is the score's scale, rounded once to fp32, and v_scale
-    multiplies the sum over the keys."""
+    multiplies the sum over the keys.  With `window` a row of length L attends the keys [max(0, L - window), L) only: table
+    entries and slots below them are never looked at."""
     rows, D, G = q.shape[0], head_dim, n_heads // n_kv_heads
     n_slots, H = k_cache.shape[0], k_cache.shape[1]
     ss, hs = k_cache.stride(0), (k_cache.stride(1) if H > 1 else D)
@@ -1109,6 +1132,8 @@ def _torch_attn_decode(q, k_cache, v_cache, block_table, seq_lens, block_size, n
     S = max(int(use.max().item()), 1)
     p = torch.arange(S, device=dev)
     valid = p[None, :] < use[:, None]  # [rows, S]
+    if window is not None:
+        valid = valid & (p[None, :] >= (use - int(window))[:, None])
     entry = block_table.long()[:, (p // block_size).clamp(max=block_table.shape[1] - 1)]  # [rows, S]
     slot = entry * int(block_size) + (p % block_size)[None, :]
     bad = (valid & ((slot < 0) | (slot >= n_slots))).any(dim=1)
@@ -1153,8 +1178,8 @@ class DecodeAttention(nn.Module):
     It reads K and V once for all the query heads of a kv group, only the keys below each row's length, and follows lengths
     and block tables in device memory -- no mask tensor, no expanded heads.
 
-    DecodeAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None); scale: 1 / sqrt(head_dim) where None.  No
-    parameters, no buffers, no state-dict keys.
+    DecodeAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None, window=None); scale: 1 / sqrt(head_dim) where
+    None.  No parameters, no buffers, no state-dict keys.
 
     forward(q, k_cache, v_cache, block_table, seq_lens, out=None, block_size=None) -> [..., n_heads * head_dim].
     `q`: [..., n_heads * head_dim] with a contiguous last dimension, one row per sequence (the front's q).  `k_cache`,
@@ -1202,12 +1227,23 @@ class DecodeAttention(nn.Module):
     expansion prepared outside the timed region, the one-query kernels are the faster ones on 313 of 384 measured points (the
     repeated rows hit the caches; the append kernels win by up to 3.0x with 32/32 heads, a 16-bit cache and 4096 keys); end to
     end, as a caller of this module pays, the append route is faster on 361 of 384, by 0.90x - 3.2x (tools/attn_append_bench.py,
-    DESIGN.md 4.4, profiles/attn_append_bench.txt).  Everything else is the torch fallback on the expansion."""
+    DESIGN.md 4.4, profiles/attn_append_bench.txt).  Everything else is the torch fallback on the expansion.
+
+    DecodeAttention(..., window=W): a SLIDING WINDOW (Mistral's `sliding_window`; an int of at least 1, anything else is a
+    ValueError; None is the module above, bit for bit and launch for launch).  A row of length L attends the keys
+    [max(0, L - W), L) -- the query's own key included, W keys in all -- through kernels of their own
+    (sqllm_attn_decode_window_f16 / _bf16 / _fp8_f16 / _fp8_bf16; include/sqllm_hip.h, sliding-window decode attention;
+    `last_route` "attn_window"): the launch, the workspace and the bytes read are sized by the window, not by the table.  Rows
+    with L <= W hold exactly the bits of the module without a window.  Table entries and slots behind the window are never
+    looked at: the caller may free or reuse those blocks, and ring_block_table is the table of a rolling buffer.  The torch
+    fallback applies the same window.  With `q_len=` a windowed module ALWAYS takes the expansion (append_as_decode_rows) on
+    the windowed one-query kernels -- row (b, t) attends [max(0, L(b,t) - W), L(b,t)) -- and `append_route` is ignored: the
+    append kernels have no window."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
     append_route = "auto"  # forward(..., q_len=): "auto" routes by measurement, "kernel" / "emulate" force one way (same bits)
 
-    def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None):
+    def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None, window=None):
         super().__init__()
         n_heads, n_kv_heads, head_dim = int(n_heads), int(n_kv_heads), int(head_dim)
         if n_heads < 1 or n_kv_heads < 1 or head_dim < 1 or n_heads % n_kv_heads:
@@ -1219,10 +1255,13 @@ class DecodeAttention(nn.Module):
             raise ValueError(f"block_size must be positive, got {block_size}")
         self.n_heads, self.n_kv_heads, self.head_dim, self.scale = n_heads, n_kv_heads, head_dim, scale
         self.block_size = None if block_size is None else int(block_size)
+        if window is not None and (isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= (1 << 31) - 1):
+            raise ValueError(f"window must be None or an int in [1, 2^31), got {window!r}")
+        self.window = window
 
     @property
     def last_route(self):
-        """"attn_decode", "attn_append" or "fallback": the way the most recent forward went (None before the first)."""
+        """"attn_decode", "attn_append", "attn_window" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def _check_cache(self, q: torch.Tensor, k_cache, v_cache) -> None:
@@ -1306,8 +1345,14 @@ class DecodeAttention(nn.Module):
         dev = q2.get_device()
         o = out if out is not None else torch.empty((rows, W), dtype=q2.dtype, device=q2.device)
         stream = quant_cuda._raw_stream(dev)
-        ws = _workspace_of(self, _lib.attn_decode_workspace_bytes, (rows, HQ, D, max_blocks, bs), q2.device)
+        window = self.window
+        if window is None:
+            ws = _workspace_of(self, _lib.attn_decode_workspace_bytes, (rows, HQ, D, max_blocks, bs), q2.device)
+        else:  # (kind 0 or 1: the one-query descriptors)
+            ws = _workspace_of(self, _lib.attn_window_workspace_bytes, (rows, HQ, D, max_blocks, bs, window), q2.device)
         struct, entries = _ATTN_KINDS[kind]
+        if window is not None:
+            entries = _ATTN_WINDOW_ENTRIES[kind]
         descs = self.__dict__.setdefault("_desc", {})
         hit = descs.get((kind, dev, stream))
         if hit is None:
@@ -1328,7 +1373,7 @@ class DecodeAttention(nn.Module):
             a.k_scale, a.v_scale = k_scale, v_scale
         if kind & 2:
             a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
-        quant_cuda._launch(quant_cuda._fn(entries[q2.dtype]), dev, (ref,))
+        quant_cuda._launch(quant_cuda._fn(entries[q2.dtype]), dev, (ref,) if window is None else (ref, window))
         return o
 
     def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
@@ -1349,7 +1394,7 @@ class DecodeAttention(nn.Module):
         if not kernel:
             self.__dict__["_last_route"] = "fallback"
             table, lens = (block_table, seq_lens) if T is None else append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
-            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
+            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale, self.window)
             if out is not None:
                 out.copy_(o)
                 return out
@@ -1360,23 +1405,25 @@ class DecodeAttention(nn.Module):
             # routed by measurement, END TO END (tools/attn_append_bench.py `route_emul` against `append`): the expansion
             # below is a dozen small kernels in every call, 24 - 34 us in a replayed graph, which the one-query kernels win back only
             # over an fp8 cache at 64 rows (by up to 10 %); everywhere else the append kernels are faster.  The same bits either way.
-            if self.append_route == "emulate" or (self.append_route == "auto" and fp8 and rows >= 64):
+            # (a window: the append kernels have none -- always the expansion, on the windowed one-query kernels)
+            if self.window is not None or self.append_route == "emulate" or (self.append_route == "auto" and fp8 and rows >= 64):
                 table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
                 o = self.forward(q2, k_cache, v_cache, table, lens, out=out, block_size=bs, k_scale=k_scale if fp8 else None,
-                                 v_scale=v_scale if fp8 else None)  # (`last_route` "attn_decode")
+                                 v_scale=v_scale if fp8 else None)  # (`last_route` "attn_decode", "attn_window" with a window)
                 return o if out is not None else o.reshape(*q.shape[:-1], W)
         bt, sl, ql = self._int32_operands(block_table, seq_lens, q_lens)
-        self.__dict__["_last_route"] = "attn_decode" if T is None else "attn_append"
+        self.__dict__["_last_route"] = "attn_append" if T is not None else "attn_decode" if self.window is None else "attn_window"
         o = self._launch(2 * (T is not None) + fp8, q2, k_cache, v_cache, bt, sl, ql, T, out, bs, k_scale, v_scale)
         return o if out is not None else o.reshape(*q.shape[:-1], W)
 
 
-def fuse_decode_attention(module: nn.Module, n_heads=None, n_kv_heads=None) -> int:
+def fuse_decode_attention(module: nn.Module, n_heads=None, n_kv_heads=None, window=None) -> int:
     """Give every submodule of `module` that carries a `qkv_rope` (fuse_qkv_rope) an attribute `attend_decode`, a
     DecodeAttention for its heads: head_dim the front's, n_heads and n_kv_heads the widths of the front's q and k over it
     (or the arguments).  Not a child, through `__dict__`: the module tree, the state dict and every `forward` stay as they
     are; an attention forward calls `self.attend_decode(q, k_cache, v_cache, block_table, seq_lens)` between `self.qkv_rope`
-    and `o_proj`.  Returns the count."""
+    and `o_proj`.  `window`: the model's sliding window (Mistral: model.config.sliding_window), passed to every
+    DecodeAttention; None: no window.  Returns the count."""
     n = 0
     for m in module.modules():
         front = m.__dict__.get("qkv_rope")
@@ -1387,7 +1434,7 @@ def fuse_decode_attention(module: nn.Module, n_heads=None, n_kv_heads=None) -> i
         hk = int(n_kv_heads) if n_kv_heads is not None else front.k.outfeatures // d
         if hq < 1 or hk < 1 or hq % hk:
             continue
-        m.__dict__["attend_decode"] = DecodeAttention(hq, hk, d)
+        m.__dict__["attend_decode"] = DecodeAttention(hq, hk, d, window=window)
         n += 1
     return n
 
