@@ -736,6 +736,49 @@ int sqllm_attn_decode_window_fp8_f16(const sqllm_attn_decode_fp8* a, int32_t win
 int sqllm_attn_decode_window_fp8_bf16(const sqllm_attn_decode_fp8* a, int32_t window, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PREFILL attention over the paged KV cache, on the matrix cores: a whole prompt (or a long chunk of one) per sequence behind a
+ * front that wrote all of its tokens -- causal, bottom-right aligned, variable length.  What the blocks above leave to the
+ * integrator (more than 16 rows per sequence, more than 64 rows per call) is served here, by entries of their own; the
+ * entries above are unchanged.  The descriptor is sqllm_attn_append, unchanged.
+ *
+ *   - Rows, tables, lengths: as sqllm_attn_append.  Row b*T + t is new token t of sequence b (T = q_len, a host field); ONE table
+ *     row per sequence; seq_lens[b] counts the new tokens; n_b = q_lens ? q_lens[b] : T; token t < n_b attends the keys below
+ *     L(b,t) = seq_lens[b] - (n_b - 1 - t).  Addressing is sqllm_attn_decode's.
+ *   - Corner rows, word for word.  +0 rows: padding t >= n_b, and L <= 0.  NaN rows: n_b > T, L > max_blocks*block_size, and a
+ *     table entry outside [0, n_slots) at key p -- a bad entry makes NaN only the tokens with L > p, and nothing of the caches is
+ *     read at or behind a bad entry.  n_b < 0 counts as 0.
+ *   - Values.  The formulas of sqllm_attn_decode for a row of length L(b,t), inside the same fp32-class error bound -- but NOT
+ *     THE BITS of the one-query entry (nor of sqllm_attn_append_*): the sums run on the matrix instructions, in another order.
+ *     The key tiles are the absolute ranges [64 i, 64 i + 64), walked in ascending order with one running (max, sum, acc) per
+ *     row; scores are v_mfma_f32_16x16x32 products of the 16-bit operands as stored, accumulated in fp32; the softmax is fp32;
+ *     the fp32 weights enter the second product as three 16-bit planes (exact for bf16; for fp16 exact above 2^-16 of the row's
+ *     largest weight), so nothing is rounded to 16 bits before the ONE rounding of the output.  Row (b,t)'s bits depend only on
+ *     its own operands, L(b,t) and the descriptor's shape fields: not on other sequences, not on batch, not on timing;
+ *     bit-identical run to run.
+ *   - NO WORKSPACE.  The descriptor's workspace field is ignored and may be NULL; the overlap and alignment rules name out only.
+ *     Always ONE kernel node; the call allocates nothing and is capturable; launch geometry comes from host fields only
+ *     (ceil(q_len * n_q_heads / n_kv_heads / 64) x n_kv_heads x batch workgroups).  Nothing but the batch*T rows of out is written.
+ *   - Isolation, and where it is WEAKER than the append entries'.  Slots not addressed by (block_table, seq_lens) never
+ *     influence a result, whatever bits they hold; nothing outside the cache extent is read; staged rows for keys at or beyond the
+ *     query tile's largest L are zeros written by the kernel and are never loaded.  A FINITE value at a key >= L(b,t) that a later
+ *     token of the same query tile attends never influences row (b,t).  But a NON-FINITE v[p,d] at such a key may make column d
+ *     NaN for every row of that query tile (64 consecutive (token, head of the kv group) pairs, tokens first): 0 * NaN inside
+ *     the matrix instruction.  A non-finite k at such a key does NOT spread: the mask is a select on the score.
+ *   - NaN among the attended elements propagates as in sqllm_attn_decode (and, by the clause above, possibly further within
+ *     the query tile for v); infinities are not pinned.
+ *
+ * Served: head_dim 64 or 128; a head ratio of 1 to 8; q_len 1 to 65536; batch 1 to 65535; 16-bit caches, fp16 and bf16.
+ * Rejections are sqllm_attn_append's, with its codes and in its order, except: q_len > 65536 or batch > 65535 stand where
+ * q_len > 16 and batch*q_len > 64 stood; there is no workspace NULL check, no workspace overlap check, no workspace alignment.
+ * A library without the prefill kernel answers hipErrorNotSupported, never with the kernels above.
+ * Out of scope: fp8 caches; a sliding window; attention sinks, ALiBi and soft-capping; splitting one long sequence's keys
+ * across workgroups (a single sequence of few heads fills few CUs); routing sqllm_attn_decode_* / sqllm_attn_append_* onto this
+ * kernel.
+ * ------------------------------------------------------------------------------------------- */
+int sqllm_attn_prefill_f16(const sqllm_attn_append* a, sqllm_stream_t stream);
+int sqllm_attn_prefill_bf16(const sqllm_attn_append* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

@@ -13,6 +13,7 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -23,7 +24,8 @@ LIB_PATH = os.path.join(HERE, LIB_NAME)
 SOURCES = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "sqllm_nuq.hip", "sqllm_dequant.hip", "sqllm_encode.hip", "sqllm_select.hip", "sqllm_linear_bf16.hip", "sqllm_linear_gated.hip", "sqllm_linear_ep.hip", "sqllm_linear_qkv.hip",
            "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip", "sqllm_linear_qkv_cache.hip", "sqllm_linear_qkv_norm_cache.hip", "sqllm_attn_decode.hip",
            "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode_fp8.hip",
-           "sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip", "sqllm_attn_window.hip", "sqllm_attn_window_fp8.hip", "sqllm_capi.hip"]
+           "sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip", "sqllm_attn_window.hip", "sqllm_attn_window_fp8.hip",
+           "sqllm_attn_prefill.hip", "sqllm_capi.hip"]
 # measured-and-not-adopted kernels (round 3: the streaming batch-1 kernel, the column-pair-table kernel; round 4: the
 # dependency-gated persistent pass) and the host code that routes to them: csrc/experimental/, part of the MEASUREMENT
 # library only (options "stream" / "pair4", entry points sqllm_pass_*)
@@ -39,6 +41,10 @@ ARCH = "gfx950"
 # mean kernel duration of the 7B batch-1 launches -2.5 %, same-box A/B profiles/r05_kernarg_preload_ab.txt
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
+# sources compiled to an object of their own WITHOUT the packed fp32 VALU instructions (plain v_mul / v_fma instead); the other
+# sources keep the code generation they were measured and pinned with (tests/test_codegen_*_cpu.py)
+NO_PACKED_FP32 = ("sqllm_attn_prefill.hip",)
+NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 class HipccMissing(RuntimeError):
@@ -82,9 +88,7 @@ def ablation_is_stale() -> bool:
 VARIANT_ENV = ("SQLLM_PAIR3", "SQLLM_HALF_STAGES", "SQLLM_PAIR3_NOCONFLICT", "SQLLM_MFMA_VAR", "SQLLM_MFMA_FAKE", "SQLLM_TOPX_ROWS", "SQLLM_CSR_CHUNK")
 
 
-def _compile(out: str, extra, verbose: bool, sources=None) -> str:
-    cmd = [hipcc(), f"--offload-arch={ARCH}", *FLAGS, *extra, "-shared", f"-I{INCLUDE}", f"-I{CSRC}", f"-I{EXPERIMENTAL}",
-           *[os.path.join(CSRC, s) for s in (sources or SOURCES)], "-o", out + ".tmp"]
+def _run(cmd, verbose: bool) -> None:
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)
@@ -92,6 +96,22 @@ def _compile(out: str, extra, verbose: bool, sources=None) -> str:
         raise BuildError(f"hipcc failed ({res.returncode}):\n{res.stdout}\n{res.stderr}")
     if verbose and res.stderr.strip():
         print(res.stderr, file=sys.stderr)
+
+
+def _compile(out: str, extra, verbose: bool, sources=None) -> str:
+    sources = list(sources or SOURCES)
+    common = [hipcc(), f"--offload-arch={ARCH}", *FLAGS, *extra, f"-I{INCLUDE}", f"-I{CSRC}", f"-I{EXPERIMENTAL}"]
+    with tempfile.TemporaryDirectory(prefix="sqllm_build_") as tmp:
+        inputs = []
+        for s in sources:
+            if s in NO_PACKED_FP32:  # a command of its own: the flag would reach every source of a shared command
+                obj = os.path.join(tmp, os.path.splitext(os.path.basename(s))[0] + ".o")
+                _run([*common, *NO_PACKED_FP32_FLAGS, "-c", os.path.join(CSRC, s), "-o", obj], verbose)
+                inputs.append(obj)
+            else:
+                inputs.append(os.path.join(CSRC, s))
+        inputs.sort(key=lambda p: not p.endswith(".o"))  # objects first: hipcc's `-x hip` holds for every input behind a source
+        _run([*common, "-shared", *inputs, "-o", out + ".tmp"], verbose)
     os.replace(out + ".tmp", out)
     return out
 

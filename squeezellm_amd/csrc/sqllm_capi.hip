@@ -22,6 +22,7 @@ hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, 
 hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
 AttnLauncher g_launch_attn_window[2] = {};  // [0] set by sqllm_attn_window.hip, [1] by sqllm_attn_window_fp8.hip
 hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_window.hip
+AttnLauncher g_launch_attn_prefill = nullptr;  // set by sqllm_attn_prefill.hip
 }
 
 namespace sqllm_host {
@@ -1568,7 +1569,7 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
   return (int64_t)batch * n_q_heads * attn_window_parts(max_blocks, block_size, window) * (head_dim + 2) * 4;
 }
 
-// The twelve attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
+// The fourteen attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
 // follows them is passed on by each entry:
 //   `kv_scales` (the fp8 entries): {k_scale, v_scale} of the descriptor -- the caches hold 1-byte e4m3fn elements, their strides
 //     and extents count bytes and they need no alignment; the scales are judged last.  NULL: 16-bit caches.
@@ -1576,18 +1577,20 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
 //     the one-query entries -- so a q_len below 1 in an append descriptor is a count < 1, never the one-query call.
 //   `window` (sqllm_attn_decode_window_*): the keys [max(0, L - *window), L) of every row; a count as the others.  The launch and
 //     the workspace are sized by the partitions a window can touch, and the call goes to g_launch_attn_window.  NULL: no window.
+//   `prefill` (sqllm_attn_prefill_*, with `tokens`): q_len up to 65536 and batch up to 65535 instead of the append entries' two
+//     limits; the workspace field is ignored (NULL allowed, no overlap or alignment rule); the call goes to g_launch_attn_prefill.
 struct AttnTokensTail {
   const int32_t* q_lens;
   int32_t q_len;
 };
 static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, bool bf16, const float* kv_scales, const AttnTokensTail* tokens,
-                       const int32_t* window = nullptr) {
+                       const int32_t* window = nullptr, bool prefill = false) {
   const sqllm_attn_decode* const a = &lead;
   const bool append = tokens != nullptr;
   const int32_t q_len = append ? tokens->q_len : 0;
   const int32_t* const q_lens = append ? tokens->q_lens : nullptr;
   const int celem = kv_scales ? 1 : 2;  // bytes per cache element
-  if (!a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || !a->workspace) return SQLLM_E_NULL;
+  if (!a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || (!prefill && !a->workspace)) return SQLLM_E_NULL;
   const int64_t D = a->head_dim;
   if (a->batch < 1 || a->n_q_heads < 1 || a->n_kv_heads < 1 || D < 1 || a->n_slots < 1 || a->block_size < 1 || a->max_blocks < 1 ||
       a->table_stride < 1 || (append && q_len < 1) || (window && *window < 1))
@@ -1597,8 +1600,8 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   if (a->slot_stride < D || a->head_stride < D || a->q_stride < width || a->out_stride < width) return SQLLM_E_SHAPE;
   if (a->max_blocks > a->table_stride) return SQLLM_E_SHAPE;
   // what the kernel serves
-  if ((D != 64 && D != 128) || a->n_q_heads % a->n_kv_heads || a->n_q_heads / a->n_kv_heads > 8 || rows > 64 || a->n_q_heads > 65535 ||
-      (append && q_len > 16))
+  if ((D != 64 && D != 128) || a->n_q_heads % a->n_kv_heads || a->n_q_heads / a->n_kv_heads > 8 || a->n_q_heads > 65535 ||
+      (prefill ? (q_len > 65536 || a->batch > 65535) : (rows > 64 || (append && q_len > 16))))
     return SQLLM_E_SHAPE;
   // as for sqllm_kv_cache: 32 x 32 -> 64-bit products, and extents that do not wrap
   const int64_t H = a->n_kv_heads;
@@ -1608,18 +1611,19 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   const unsigned __int128 out_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->out_stride + (uint64_t)width;
   if (extent >= ((unsigned __int128)1 << 62) || q_extent >= ((unsigned __int128)1 << 62) || out_extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
   if (!__builtin_isfinite(a->scale)) return SQLLM_E_OPTION;
-  const int64_t ws_bytes = window ? sqllm_attn_window_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size, *window)
+  const int64_t ws_bytes = prefill ? 0
+                           : window ? sqllm_attn_window_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size, *window)
                                   : sqllm_attn_decode_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
   const void* const in[6] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens, q_lens};
   const int64_t in_bytes[6] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
                                4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch, 4 * (int64_t)a->batch};
   for (int i = 0; i < (q_lens ? 6 : 5); ++i)
-    if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i]))
+    if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || (!prefill && ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i])))
       return SQLLM_E_SHAPE;
-  if (ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
+  if (!prefill && ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
   if (((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->out)) & 1u) != 0 ||
       (!kv_scales && ((reinterpret_cast<uintptr_t>(a->k_cache) | reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0) ||
-      (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0)
+      (!prefill && (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0))
     return SQLLM_E_ALIGN;
   float scale = a->scale;
   if (kv_scales) {
@@ -1634,7 +1638,7 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.v_cache = a->v_cache;
   c.block_table = a->block_table;
   c.seq_lens = a->seq_lens;
-  c.workspace = a->workspace;
+  c.workspace = prefill ? nullptr : a->workspace;
   c.batch = a->batch;
   c.n_q_heads = a->n_q_heads;
   c.n_kv_heads = a->n_kv_heads;
@@ -1643,7 +1647,7 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.block_size = a->block_size;
   c.table_stride = a->table_stride;
   c.capacity = (int)attn_capacity(a->max_blocks, a->block_size);
-  c.n_parts = (int)(window ? attn_window_parts(a->max_blocks, a->block_size, *window) : attn_parts(a->max_blocks, a->block_size));
+  c.n_parts = prefill ? 1 : (int)(window ? attn_window_parts(a->max_blocks, a->block_size, *window) : attn_parts(a->max_blocks, a->block_size));
   c.slot_stride = a->slot_stride;
   c.head_stride = a->head_stride;
   c.q_stride = a->q_stride;
@@ -1656,7 +1660,8 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.q_len = q_len;  // (0: one query per sequence; an append call has passed q_len >= 1 above)
   c.window = window ? *window : 0;
   // (a window has a table of its own: a null slot there is an error, never the kernels without a window)
-  const sqllm::AttnLauncher launch = window ? sqllm::g_launch_attn_window[c.fp8 ? 1 : 0] : sqllm::g_launch_attn[sqllm::attn_kind(c)];
+  const sqllm::AttnLauncher launch = prefill ? sqllm::g_launch_attn_prefill
+                                     : window ? sqllm::g_launch_attn_window[c.fp8 ? 1 : 0] : sqllm::g_launch_attn[sqllm::attn_kind(c)];
   return static_cast<int>(launch ? launch(c, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
 }
 
@@ -1730,6 +1735,13 @@ int sqllm_attn_append_f16(const sqllm_attn_append* a, sqllm_stream_t stream) { r
 int sqllm_attn_append_bf16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_append(a, stream, true); }
 int sqllm_attn_append_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, false); }
 int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, true); }
+static int launch_attn_prefill(const sqllm_attn_append* a, sqllm_stream_t stream, bool bf16) {
+  if (!a) return SQLLM_E_NULL;
+  const AttnTokensTail t = attn_tokens(a);
+  return launch_attn(attn_lead(a), stream, bf16, nullptr, &t, nullptr, true);
+}
+int sqllm_attn_prefill_f16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_prefill(a, stream, false); }
+int sqllm_attn_prefill_bf16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_prefill(a, stream, true); }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

@@ -342,6 +342,10 @@ extern hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int h
 // Null until the file is linked in: hipErrorNotSupported, never the kernels without a window.
 extern AttnLauncher g_launch_attn_window[2];
 extern hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
+// The prefill entries (sqllm_attn_prefill_*, sqllm_attn_prefill.hip): a slot of its own, NOT a kind of g_launch_attn -- the call
+// carries q_len up to 65536 and no workspace (AttnCall::workspace is null, n_parts 1).  Null until the file is linked in:
+// hipErrorNotSupported, never the append kernels.
+extern AttnLauncher g_launch_attn_prefill;
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

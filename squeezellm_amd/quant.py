@@ -1439,6 +1439,118 @@ def fuse_decode_attention(module: nn.Module, n_heads=None, n_kv_heads=None, wind
     return n
 
 
+ATTN_PREFILL_MAX_Q_LEN = 65536  # new tokens per sequence the prefill kernel serves
+ATTN_PREFILL_MAX_BATCH = 65535  # ... and sequences per call
+_ATTN_PREFILL_ENTRIES = {torch.float16: "sqllm_attn_prefill_f16", torch.bfloat16: "sqllm_attn_prefill_bf16"}
+
+
+class PrefillAttention(DecodeAttention):
+    """PREFILL attention -- a whole prompt, or a long chunk of one, per sequence -- over the KV cache QuantQKVRopeFused writes, as
+    ONE HIP kernel on the matrix cores (sqllm_attn_prefill_f16 / _bf16; include/sqllm_hip.h, prefill attention): causal,
+    bottom-right aligned, variable length, K and V read once per 64 (token, query head of a kv group) pairs, the causal triangle
+    skipped, no mask tensor, no gathered cache, no expanded heads, no workspace.  Opt-in, beside DecodeAttention, which is unchanged
+    (its q_len = 17 stays its fallback); the operand rules, the checks and their helpers are DecodeAttention's.
+
+    PrefillAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None).  No window, no fp8 scales.
+
+    forward(q, k_cache, v_cache, block_table, seq_lens, q_len, q_lens=None, out=None, block_size=None) -> q's shape.  `q`:
+    [batch * q_len, W] or [batch, q_len, W], row b * q_len + t new token t of sequence b; `block_table` [batch, max_blocks] and
+    `seq_lens` [batch] per SEQUENCE, seq_lens counting the new tokens (no prior context: seq_lens = q_lens); `q_lens`: int32
+    [batch] or None, the real tokens n_b of each sequence -- rows t >= n_b are padding and +0, n_b > q_len makes the sequence's
+    rows NaN.  Token t attends the keys below seq_lens[b] - (n_b - 1 - t).  Tables and lengths are used without a copy: a captured
+    graph (one kernel node) follows them updated in place.
+
+    The values are the formulas of sqllm_attn_decode inside its fp32-class bound, NOT the bits of DecodeAttention: other sums,
+    other order.  Isolation is weaker in one clause: a NON-FINITE v at a key that a later token of the same 64-row query tile
+    attends may make that column NaN for the tile's earlier rows too (0 * NaN in the matrix instruction); finite values never
+    leak, unaddressed slots never matter.
+
+    fp16 / bf16 GPU tensors with head_dim 64 or 128, n_heads / n_kv_heads of 1 to 8, q_len up to 65536 and up to 65535 sequences
+    over a 16-bit cache take the kernel (`last_route` "attn_prefill").  Everything else -- CPU tensors, other dtypes and shapes,
+    fp8 caches (forward(..., k_scale=, v_scale=)) -- computes the same formulas in torch through append_as_decode_rows and the
+    fallback of DecodeAttention (`last_route` "fallback"): correct, and as slow as that sounds.
+
+    Speed, graph-replayed on an MI355X (tools/attn_prefill_bench.py, DESIGN.md 4.4, profiles/attn_prefill_bench.txt; 32/32 and 32/8
+    heads of 128, 1 / 4 sequences, 128 / 512 / 2048 new tokens behind 0 / 2048 keys, fp16 / bf16, paged: 48 points): 16 - 1722 us per
+    call; 2.9x - 19.7x faster than a loop of DecodeAttention(q_len=16) calls on all points; 0.90x - 2.98x against torch SDPA on K / V
+    gathered from the pages (NOT faster on 4 points, fp16 at 2048 tokens), 0.74x - 1.88x when the gather is not counted (NOT faster
+    on 18)."""
+
+    def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None):
+        super().__init__(n_heads, n_kv_heads, head_dim, scale=scale, block_size=block_size)
+
+    @property
+    def last_route(self):
+        """"attn_prefill" or "fallback": the way the most recent forward went (None before the first)."""
+        return self.__dict__.get("_last_route")
+
+    def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
+                q_len: int, q_lens=None, out=None, block_size=None, k_scale=None, v_scale=None) -> torch.Tensor:
+        D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
+        W = HQ * D
+        T = int(q_len)
+        if T < 1:
+            raise ValueError(f"q_len must be positive, got {q_len}")
+        q2, rows, bs, fp8, k_scale, v_scale = self._check_operands(q, k_cache, v_cache, block_table, seq_lens, out, block_size,
+                                                                   k_scale, v_scale, T, q_lens)
+        batch = rows // T
+        kernel = (q.dtype in _ATTN_DTYPES and q.is_cuda and not fp8 and D in (64, 128) and HQ // H <= 8 and HQ <= 65535
+                  and T <= ATTN_PREFILL_MAX_Q_LEN and batch <= ATTN_PREFILL_MAX_BATCH)
+        if not kernel:
+            self.__dict__["_last_route"] = "fallback"
+            table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
+            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
+            if out is not None:
+                out.copy_(o)
+                return out
+            return o.reshape(*q.shape[:-1], W)
+        bt, sl, ql = self._int32_operands(block_table, seq_lens, q_lens)
+        self.__dict__["_last_route"] = "attn_prefill"
+        max_blocks = bt.shape[1]
+        dev = q2.get_device()
+        o = out if out is not None else torch.empty((rows, W), dtype=q2.dtype, device=q2.device)
+        stream = quant_cuda._raw_stream(dev)
+        descs = self.__dict__.setdefault("_desc", {})
+        hit = descs.get(("prefill", dev, stream))
+        if hit is None:
+            a = _lib.SqllmAttnAppend()
+            hit = descs[("prefill", dev, stream)] = (a, ctypes.byref(a))
+        a, ref = hit
+        a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+        a.block_table, a.seq_lens = bt.data_ptr(), sl.data_ptr()
+        a.batch, a.n_q_heads, a.n_kv_heads, a.head_dim = batch, HQ, H, D
+        a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, max_blocks
+        a.table_stride = bt.stride(0) if batch > 1 else max_blocks
+        a.slot_stride = k_cache.stride(0)
+        a.head_stride = k_cache.stride(1) if H > 1 else D
+        a.q_stride = q2.stride(0) if rows > 1 else W
+        a.out_stride = o.stride(0) if rows > 1 else W
+        a.scale, a.workspace = self.scale, None  # (no workspace: the field is ignored)
+        a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
+        quant_cuda._launch(quant_cuda._fn(_ATTN_PREFILL_ENTRIES[q2.dtype]), dev, (ref,))
+        return o if out is not None else o.reshape(*q.shape[:-1], W)
+
+
+def fuse_prefill_attention(module: nn.Module, n_heads=None, n_kv_heads=None) -> int:
+    """Give every submodule of `module` that carries a `qkv_rope` (fuse_qkv_rope) an attribute `attend_prefill`, a
+    PrefillAttention for its heads, the way fuse_decode_attention gives it `attend_decode`: through `__dict__`, not a child -- the
+    module tree, the state dict and every `forward` stay as they are.  An attention forward calls
+    `self.attend_prefill(q, k_cache, v_cache, block_table, seq_lens, q_len)` when q_len > 1.  Returns the count."""
+    n = 0
+    for m in module.modules():
+        front = m.__dict__.get("qkv_rope")
+        if not isinstance(front, QuantQKVRopeFused):
+            continue
+        d = front.head_dim
+        hq = int(n_heads) if n_heads is not None else front.q.outfeatures // d
+        hk = int(n_kv_heads) if n_kv_heads is not None else front.k.outfeatures // d
+        if hq < 1 or hk < 1 or hq % hk:
+            continue
+        m.__dict__["attend_prefill"] = PrefillAttention(hq, hk, d)
+        n += 1
+    return n
+
+
 def _norm_of(m):
     """(weight, eps) of an RMSNorm-like module: a `weight` and a `variance_epsilon` (or `eps`); None for anything else."""
     w = getattr(m, "weight", None)

@@ -1,0 +1,130 @@
+"""Prefill attention over the paged KV cache: quant.PrefillAttention (one kernel node on the matrix cores) against what the library
+offered before it and against torch, graph-replayed ALTERNATELY in one process, timed by device events around the replays.
+
+    python tools/attn_prefill_bench.py [--heads 32/32,32/8] [--seqs 1,4] [--q-lens 128,512,2048] [--ctx 0,2048]
+                                       [--dtypes fp16,bf16] [--reps 7] [--replays 50] > profiles/attn_prefill_bench.txt
+
+Workload per point: `seqs` sequences of T new tokens behind `ctx` prior keys each, head_dim 128, a paged cache of blocks of 16 with
+a shuffled table, the new tokens' keys already written (what the attention front leaves).  The contenders:
+  prefill      one PrefillAttention call
+  loop16       (a) what the library offered before: a loop of T / 16 DecodeAttention(q_len=16) calls over the same cache, chunk c
+               with seq_lens = ctx + 16 (c + 1) -- K and V re-read once per 16 tokens, two kernel nodes per chunk
+  sdpa         (b) torch scaled_dot_product_attention with the bottom-right causal mask on K / V gathered from the pages to
+               contiguous [B, HQ, n, D] tensors (grouped heads expanded), timed WITH the gather and WITHOUT it (sdpa_only)
+prefill is checked against loop16 (largest absolute difference printed, at most 2^-6) before anything is timed.  Each contender
+is captured once after an eager warm-up; --reps rounds, each replaying every contender --replays times between two events, in
+turn.  One JSON line per point: median us and spread (max - min over the rounds) per contender, the causal-trimmed operation count
+from the shapes -- 4 * head_dim * (T * ctx + T (T + 1) / 2) per (sequence, query head) -- and prefill's FLOP/s over it.
+Needs a GPU: there is no CPU timing."""
+import argparse, json, os, statistics, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+D, BLOCK = 128, 16
+ap = argparse.ArgumentParser()
+ap.add_argument("--heads", default="32/32,32/8")
+ap.add_argument("--seqs", default="1,4")
+ap.add_argument("--q-lens", default="128,512,2048")
+ap.add_argument("--ctx", default="0,2048")
+ap.add_argument("--dtypes", default="fp16,bf16")
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--replays", type=int, default=50)
+args = ap.parse_args()
+
+import torch  # noqa: E402
+if not torch.cuda.is_available():
+    sys.exit("attn_prefill_bench: no GPU is visible; there is nothing to measure on a CPU")
+from squeezellm_amd import quant  # noqa: E402
+
+dev = torch.device("cuda:0")
+
+
+def capture(fn):
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side): fn()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr): fn()
+    return gr
+
+
+def replay_us(gr, n):
+    beg, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    beg.record()
+    for _ in range(n): gr.replay()
+    end.record()
+    end.synchronize()
+    return beg.elapsed_time(end) * 1e3 / n
+
+
+print(json.dumps(dict(tool="attn_prefill_bench", torch=torch.__version__, device=torch.cuda.get_device_name(0), head_dim=D, block=BLOCK,
+                      reps=args.reps, replays=args.replays)), flush=True)
+for heads in args.heads.split(","):
+    HQ, H = map(int, heads.split("/"))
+    G = HQ // H
+    for B in map(int, args.seqs.split(",")):
+        for dname in args.dtypes.split(","):
+            dt = {"fp16": torch.float16, "bf16": torch.bfloat16}[dname]
+            for ctx in map(int, args.ctx.split(",")):
+                for T in map(int, args.q_lens.split(",")):
+                    n = ctx + T
+                    n_blocks = (n + BLOCK - 1) // BLOCK
+                    torch.manual_seed(T + ctx)
+                    table = torch.randperm(B * n_blocks, device=dev).reshape(B, n_blocks).to(torch.int32)
+                    k_cache, v_cache = (torch.randn((B * n_blocks * BLOCK, H, D), device=dev).to(dt) for _ in "kv")
+                    q = torch.randn((B * T, HQ * D), device=dev).to(dt)
+                    seq = torch.full((B,), n, dtype=torch.int32, device=dev)
+                    pre, dec = quant.PrefillAttention(HQ, H, D, block_size=BLOCK), quant.DecodeAttention(HQ, H, D, block_size=BLOCK)
+                    dec.append_route = "kernel"
+                    out_p, out_l = torch.empty_like(q), torch.empty_like(q)
+                    # loop16: chunk c holds rows [16 c, 16 c + 16) of every sequence, gathered to [B * 16, W] outside the timed region
+                    chunks = T // 16
+                    q_c = [q.view(B, T, -1)[:, 16 * c:16 * c + 16].reshape(B * 16, -1).contiguous() for c in range(chunks)]
+                    seq_c = [torch.full((B,), ctx + 16 * (c + 1), dtype=torch.int32, device=dev) for c in range(chunks)]
+                    out_c = out_l.view(B, T, -1)
+                    tmp = [torch.empty_like(q_c[0]) for _ in range(chunks)]
+
+                    def run_prefill():
+                        pre(q, k_cache, v_cache, table, seq, T, out=out_p)
+
+                    def run_loop16():
+                        for c in range(chunks):
+                            dec(q_c[c], k_cache, v_cache, table, seq_c[c], out=tmp[c], q_len=16)
+
+                    slot = (table.long()[:, :, None] * BLOCK + torch.arange(BLOCK, device=dev)[None, None, :]).reshape(B, -1)[:, :n]
+                    mask = torch.ones((T, n), dtype=torch.bool, device=dev).tril(diagonal=ctx)
+                    q4 = q.view(B, T, HQ, D).transpose(1, 2)
+                    kv = {}
+
+                    def gather():
+                        for name, cache in (("k", k_cache), ("v", v_cache)):
+                            kv[name] = cache[slot].permute(0, 2, 1, 3).repeat_interleave(G, dim=1) if G > 1 else cache[slot].permute(0, 2, 1, 3).contiguous()
+
+                    def run_sdpa_only():
+                        return torch.nn.functional.scaled_dot_product_attention(q4, kv["k"], kv["v"], attn_mask=mask)
+
+                    def run_sdpa():
+                        gather()
+                        return run_sdpa_only()
+
+                    run_prefill(); run_loop16(); gather()
+                    assert pre.last_route == "attn_prefill" and dec.last_route == "attn_append"
+                    for c in range(chunks):
+                        out_c[:, 16 * c:16 * c + 16] = tmp[c].view(B, 16, -1)
+                    diff = float((out_p.float() - out_l.float()).abs().max())
+                    assert diff <= 2.0 ** -6, diff
+                    graphs = {"prefill": capture(run_prefill), "loop16": capture(run_loop16), "sdpa": capture(run_sdpa), "sdpa_only": capture(run_sdpa_only)}
+                    for gr in graphs.values(): replay_us(gr, 2)  # warm-up of the replays themselves
+                    times = {name: [] for name in graphs}
+                    for _ in range(args.reps):
+                        for name, gr in graphs.items():  # alternately
+                            times[name].append(replay_us(gr, args.replays))
+                    flops = 4.0 * D * (T * ctx + T * (T + 1) / 2) * B * HQ
+                    rec = dict(heads=heads, seqs=B, dtype=dname, ctx=ctx, T=T, max_abs_diff_vs_loop16=diff, flops=flops)
+                    for name, ts in times.items():
+                        rec[name + "_us"], rec[name + "_spread_us"] = round(statistics.median(ts), 1), round(max(ts) - min(ts), 1)
+                    rec["prefill_tflops"] = round(flops / (rec["prefill_us"] * 1e-6) / 1e12, 2)
+                    rec["prefill_faster_than"] = [name for name in ("loop16", "sdpa", "sdpa_only") if rec["prefill_us"] < rec[name + "_us"]]
+                    print(json.dumps(rec), flush=True)
+                    del graphs, k_cache, v_cache, kv
