@@ -771,12 +771,47 @@ int sqllm_attn_decode_window_fp8_bf16(const sqllm_attn_decode_fp8* a, int32_t wi
  * Rejections are sqllm_attn_append's, with its codes and in its order, except: q_len > 65536 or batch > 65535 stand where
  * q_len > 16 and batch*q_len > 64 stood; there is no workspace NULL check, no workspace overlap check, no workspace alignment.
  * A library without the prefill kernel answers hipErrorNotSupported, never with the kernels above.
- * Out of scope: fp8 caches; a sliding window; attention sinks, ALiBi and soft-capping; splitting one long sequence's keys
+ * Out of scope: fp8 caches (the entries below); a sliding window; attention sinks, ALiBi and soft-capping; splitting one long sequence's keys
  * across workgroups (a single sequence of few heads fills few CUs); routing sqllm_attn_decode_* / sqllm_attn_append_* onto this
  * kernel.
  * ------------------------------------------------------------------------------------------- */
 int sqllm_attn_prefill_f16(const sqllm_attn_append* a, sqllm_stream_t stream);
 int sqllm_attn_prefill_bf16(const sqllm_attn_append* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * PREFILL attention over the fp8 KV cache, on the matrix cores: the two entries above for caches of 1-byte OCP e4m3fn elements,
+ * as sqllm_qkv_rope_cache_fp8_* writes them and sqllm_attn_decode_fp8_* / sqllm_attn_append_fp8_* read them.  The descriptor is
+ * sqllm_attn_append_fp8, unchanged: slot_stride and head_stride count BYTES, the caches need no alignment, k_scale and v_scale
+ * are the cache's.  Kernels of their own; every entry above is unchanged.
+ *
+ *   - Values.  float(k) = k_scale * f32(byte) and float(v) = v_scale * f32(byte) in the formulas of the block above, as
+ *     sqllm_attn_decode_fp8 defines them: the score's scale is scale * k_scale, rounded once to fp32 on the host; v_scale
+ *     multiplies the finished element (sum over the keys / sum of the weights) once, in fp32, before the ONE rounding of the
+ *     output.  Inside the fp32-class error bound of sqllm_attn_decode_fp8 over the dequantised bytes; NOT THE BITS of
+ *     sqllm_attn_decode_fp8_* or sqllm_attn_append_fp8_*.
+ *   - The bytes are converted to the type of q ONCE per element, exactly (e4m3fn is a subset of fp16 and of bf16: three mantissa
+ *     bits, the smallest subnormal 2^-9 a normal number in both; the bytes 0x7f and 0xff are NaN), and the matrix instructions
+ *     run on the bytes' own values: every product with a weight plane is exact.  Key tiles, order, the three planes of the
+ *     weights and the fp32 softmax are the block's above.  Row (b,t)'s bits depend only on its own operands, L(b,t), the two
+ *     scales and the descriptor's shape fields; bit-identical run to run.
+ *   - Rows, tables, lengths, the corner rows (+0: padding, L <= 0; NaN: n_b > T, L > max_blocks*block_size, a table entry outside
+ *     [0, n_slots) at a key below L), NO WORKSPACE (the field is ignored and may be NULL), ONE kernel node, launch geometry from
+ *     host fields only, and isolation with its one WEAKER clause -- here for a NaN BYTE of v at a key a later token of the same
+ *     query tile attends -- are the block's above, word for word.  Unaddressed bytes never influence a result; staged rows for
+ *     keys at or beyond the query tile's largest L are zeros written by the kernel and are never loaded.
+ *
+ * Served: head_dim 64 or 128; a head ratio of 1 to 8; q_len 1 to 65536; batch 1 to 65535; q and out fp16 or bf16 (the suffix).
+ * Rejections are sqllm_attn_append_fp8's, with its codes and in its order -- NULL, counts and shapes, the finite scale, the
+ * overlap of out with an input (cache extents in bytes), the alignment of q and out (none for the caches), the two scales
+ * LAST (SQLLM_E_OPTION) -- except, as above: q_len > 65536 or batch > 65535 stand where q_len > 16 and batch*q_len > 64 stood,
+ * and there is no workspace NULL check, overlap check or alignment.  A library without this kernel answers
+ * hipErrorNotSupported, never with the 16-bit kernel and never with the append kernels.
+ * Out of scope: a sliding window; per-head or per-token scales; e5m2, int8 and 4-bit caches; computing the scales; splitting one
+ * long sequence's keys across workgroups; routing sqllm_attn_decode_fp8_* / sqllm_attn_append_fp8_* onto this kernel.
+ * ------------------------------------------------------------------------------------------- */
+/* the suffix names the type of q and out */
+int sqllm_attn_prefill_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream);
+int sqllm_attn_prefill_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The reference operator names.

@@ -346,6 +346,9 @@ extern hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int h
 // carries q_len up to 65536 and no workspace (AttnCall::workspace is null, n_parts 1).  Null until the file is linked in:
 // hipErrorNotSupported, never the append kernels.
 extern AttnLauncher g_launch_attn_prefill;
+// ... and over caches of e4m3fn bytes (sqllm_attn_prefill_fp8_*, sqllm_attn_prefill_fp8.hip): a second slot beside it, for the calls
+// with AttnCall::fp8.  Null until that file is linked in: hipErrorNotSupported, never the 16-bit kernel and never the append kernels.
+extern AttnLauncher g_launch_attn_prefill_fp8;
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

@@ -1442,6 +1442,7 @@ def fuse_decode_attention(module: nn.Module, n_heads=None, n_kv_heads=None, wind
 ATTN_PREFILL_MAX_Q_LEN = 65536  # new tokens per sequence the prefill kernel serves
 ATTN_PREFILL_MAX_BATCH = 65535  # ... and sequences per call
 _ATTN_PREFILL_ENTRIES = {torch.float16: "sqllm_attn_prefill_f16", torch.bfloat16: "sqllm_attn_prefill_bf16"}
+_ATTN_PREFILL_FP8_ENTRIES = {torch.float16: "sqllm_attn_prefill_fp8_f16", torch.bfloat16: "sqllm_attn_prefill_fp8_bf16"}
 
 
 class PrefillAttention(DecodeAttention):
@@ -1451,9 +1452,10 @@ class PrefillAttention(DecodeAttention):
     skipped, no mask tensor, no gathered cache, no expanded heads, no workspace.  Opt-in, beside DecodeAttention, which is unchanged
     (its q_len = 17 stays its fallback); the operand rules, the checks and their helpers are DecodeAttention's.
 
-    PrefillAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None).  No window, no fp8 scales.
+    PrefillAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None).  No window.
 
-    forward(q, k_cache, v_cache, block_table, seq_lens, q_len, q_lens=None, out=None, block_size=None) -> q's shape.  `q`:
+    forward(q, k_cache, v_cache, block_table, seq_lens, q_len, q_lens=None, out=None, block_size=None, k_scale=None,
+    v_scale=None) -> q's shape.  `q`:
     [batch * q_len, W] or [batch, q_len, W], row b * q_len + t new token t of sequence b; `block_table` [batch, max_blocks] and
     `seq_lens` [batch] per SEQUENCE, seq_lens counting the new tokens (no prior context: seq_lens = q_lens); `q_lens`: int32
     [batch] or None, the real tokens n_b of each sequence -- rows t >= n_b are padding and +0, n_b > q_len makes the sequence's
@@ -1465,10 +1467,19 @@ class PrefillAttention(DecodeAttention):
     attends may make that column NaN for the tile's earlier rows too (0 * NaN in the matrix instruction); finite values never
     leak, unaddressed slots never matter.
 
+    forward(..., k_scale=, v_scale=).  Caches of torch.float8_e4m3fn (or uint8), as QuantQKVRopeFused writes them with the same two
+    scales, take a kernel of their own (sqllm_attn_prefill_fp8_f16 / _bf16; include/sqllm_hip.h, prefill attention over the fp8 KV
+    cache): float(k) = k_scale * f32(byte), float(v) = v_scale * f32(byte), the bytes converted exactly to q's type on their way
+    into LDS, half the cache bytes read.  Both scales are required then, as for DecodeAttention.  The same contract, the same
+    weaker clause (for a NaN byte of v); not the bits of DecodeAttention over the fp8 cache.  Speed on the 48 points below
+    (tools/attn_prefill_bench.py --cache fp8, profiles/attn_prefill_fp8_bench.txt): 0.92x - 1.115x of the 16-bit
+    kernel's time -- the kernel is bound by the matrix instructions, not by the cache bytes: NOT faster on 27 of 48 points (21 of
+    the 24 bf16 ones) --, and 47x - 151x faster than the torch route it replaces on the four smallest points.
+
     fp16 / bf16 GPU tensors with head_dim 64 or 128, n_heads / n_kv_heads of 1 to 8, q_len up to 65536 and up to 65535 sequences
-    over a 16-bit cache take the kernel (`last_route` "attn_prefill").  Everything else -- CPU tensors, other dtypes and shapes,
-    fp8 caches (forward(..., k_scale=, v_scale=)) -- computes the same formulas in torch through append_as_decode_rows and the
-    fallback of DecodeAttention (`last_route` "fallback"): correct, and as slow as that sounds.
+    over a 16-bit or an fp8 cache take the kernels (`last_route` "attn_prefill").  Everything else -- CPU tensors, other dtypes
+    and shapes -- computes the same formulas in torch through append_as_decode_rows and the fallback of DecodeAttention
+    (`last_route` "fallback"): correct, and as slow as that sounds.
 
     Speed, graph-replayed on an MI355X (tools/attn_prefill_bench.py, DESIGN.md 4.4, profiles/attn_prefill_bench.txt; 32/32 and 32/8
     heads of 128, 1 / 4 sequences, 128 / 512 / 2048 new tokens behind 0 / 2048 keys, fp16 / bf16, paged: 48 points): 16 - 1722 us per
@@ -1494,7 +1505,7 @@ class PrefillAttention(DecodeAttention):
         q2, rows, bs, fp8, k_scale, v_scale = self._check_operands(q, k_cache, v_cache, block_table, seq_lens, out, block_size,
                                                                    k_scale, v_scale, T, q_lens)
         batch = rows // T
-        kernel = (q.dtype in _ATTN_DTYPES and q.is_cuda and not fp8 and D in (64, 128) and HQ // H <= 8 and HQ <= 65535
+        kernel = (q.dtype in _ATTN_DTYPES and q.is_cuda and D in (64, 128) and HQ // H <= 8 and HQ <= 65535
                   and T <= ATTN_PREFILL_MAX_Q_LEN and batch <= ATTN_PREFILL_MAX_BATCH)
         if not kernel:
             self.__dict__["_last_route"] = "fallback"
@@ -1511,23 +1522,26 @@ class PrefillAttention(DecodeAttention):
         o = out if out is not None else torch.empty((rows, W), dtype=q2.dtype, device=q2.device)
         stream = quant_cuda._raw_stream(dev)
         descs = self.__dict__.setdefault("_desc", {})
-        hit = descs.get(("prefill", dev, stream))
+        key = ("prefill_fp8" if fp8 else "prefill", dev, stream)  # (a descriptor per cache type: the structs differ)
+        hit = descs.get(key)
         if hit is None:
-            a = _lib.SqllmAttnAppend()
-            hit = descs[("prefill", dev, stream)] = (a, ctypes.byref(a))
+            a = _lib.SqllmAttnAppendFp8() if fp8 else _lib.SqllmAttnAppend()
+            hit = descs[key] = (a, ctypes.byref(a))
         a, ref = hit
         a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
         a.block_table, a.seq_lens = bt.data_ptr(), sl.data_ptr()
         a.batch, a.n_q_heads, a.n_kv_heads, a.head_dim = batch, HQ, H, D
         a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, max_blocks
         a.table_stride = bt.stride(0) if batch > 1 else max_blocks
-        a.slot_stride = k_cache.stride(0)
+        a.slot_stride = k_cache.stride(0)  # (an fp8 cache has 1-byte elements: its strides count bytes)
         a.head_stride = k_cache.stride(1) if H > 1 else D
         a.q_stride = q2.stride(0) if rows > 1 else W
         a.out_stride = o.stride(0) if rows > 1 else W
         a.scale, a.workspace = self.scale, None  # (no workspace: the field is ignored)
         a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
-        quant_cuda._launch(quant_cuda._fn(_ATTN_PREFILL_ENTRIES[q2.dtype]), dev, (ref,))
+        if fp8:
+            a.k_scale, a.v_scale = k_scale, v_scale
+        quant_cuda._launch(quant_cuda._fn((_ATTN_PREFILL_FP8_ENTRIES if fp8 else _ATTN_PREFILL_ENTRIES)[q2.dtype]), dev, (ref,))
         return o if out is not None else o.reshape(*q.shape[:-1], W)
 
 

@@ -11,6 +11,12 @@ a shuffled table, the new tokens' keys already written (what the attention front
                with seq_lens = ctx + 16 (c + 1) -- K and V re-read once per 16 tokens, two kernel nodes per chunk
   sdpa         (b) torch scaled_dot_product_attention with the bottom-right causal mask on K / V gathered from the pages to
                contiguous [B, HQ, n, D] tensors (grouped heads expanded), timed WITH the gather and WITHOUT it (sdpa_only)
+With --cache fp8 (> profiles/attn_prefill_fp8_bench.txt) the same points compare the two prefill kernels of this library:
+  prefill_fp8  one PrefillAttention call over the cache quantised to e4m3fn bytes with k_scale = v_scale = 2^-6
+  prefill16    one PrefillAttention call over the DEQUANTISED cache in q's type (exact for a power-of-two scale: the same values)
+  fallback     what an fp8 cache took before the kernel: the torch route (append_as_decode_rows and the fallback of DecodeAttention),
+               eager, on the smallest points only (the fewest tokens, keys and sequences: it gathers [rows, keys, H, D] in fp32)
+prefill_fp8 is checked against prefill16 (at most 2^-6) before anything is timed.
 prefill is checked against loop16 (largest absolute difference printed, at most 2^-6) before anything is timed.  Each contender
 is captured once after an eager warm-up; --reps rounds, each replaying every contender --replays times between two events, in
 turn.  One JSON line per point: median us and spread (max - min over the rounds) per contender, the causal-trimmed operation count
@@ -28,6 +34,7 @@ ap.add_argument("--ctx", default="0,2048")
 ap.add_argument("--dtypes", default="fp16,bf16")
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--replays", type=int, default=50)
+ap.add_argument("--cache", default="16bit", choices=("16bit", "fp8"))
 args = ap.parse_args()
 
 import torch  # noqa: E402
@@ -58,7 +65,43 @@ def replay_us(gr, n):
     return beg.elapsed_time(end) * 1e3 / n
 
 
-print(json.dumps(dict(tool="attn_prefill_bench", torch=torch.__version__, device=torch.cuda.get_device_name(0), head_dim=D, block=BLOCK,
+def fp8_point(rec, q, k_cache, v_cache, table, seq, T, HQ, H, smallest):
+    """the --cache fp8 contenders of one point -> rec"""
+    S = 2.0 ** -6  # randn reaches about +-4.5: 288 in units of the scale, inside +-448
+    k8, v8 = (quant._fp8_bytes(c.float(), S).view(torch.float8_e4m3fn) for c in (k_cache, v_cache))
+    k16, v16 = ((c.float() * S).to(q.dtype) for c in (k8, v8))
+    att8, att16 = (quant.PrefillAttention(HQ, H, D, block_size=BLOCK) for _ in range(2))
+    out_8, out_16 = torch.empty_like(q), torch.empty_like(q)
+    runs = {"prefill_fp8": lambda: att8(q, k8, v8, table, seq, T, out=out_8, k_scale=S, v_scale=S),
+            "prefill16": lambda: att16(q, k16, v16, table, seq, T, out=out_16)}
+    for run in runs.values(): run()
+    assert att8.last_route == "attn_prefill" and att16.last_route == "attn_prefill"
+    rec["max_abs_diff_vs_prefill16"] = diff = float((out_8.float() - out_16.float()).abs().max())
+    assert diff <= 2.0 ** -6, diff
+    graphs = {name: capture(run) for name, run in runs.items()}
+    for gr in graphs.values(): replay_us(gr, 2)  # warm-up of the replays themselves
+    times = {name: [] for name in graphs}
+    for _ in range(args.reps):
+        for name, gr in graphs.items():  # alternately
+            times[name].append(replay_us(gr, args.replays))
+    if smallest:  # today's route for an fp8 cache, eager (it synchronises), after one warm-up call
+        def fallback():
+            tb, ln = quant.append_as_decode_rows(table, seq, T, None, BLOCK)
+            return quant._torch_attn_decode(q, k8, v8, tb, ln, BLOCK, HQ, H, D, D ** -0.5, q.dtype, S, S)
+        assert float((fallback().float() - out_8.float()).abs().max()) <= 2.0 ** -6
+        times["fallback"] = []
+        for _ in range(3):
+            beg, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            beg.record(); fallback(); end.record(); end.synchronize()
+            times["fallback"].append(beg.elapsed_time(end) * 1e3)
+    for name, ts in times.items():
+        rec[name + "_us"], rec[name + "_spread_us"] = round(statistics.median(ts), 1), round(max(ts) - min(ts), 1)
+    rec["prefill_fp8_tflops"] = round(rec["flops"] / (rec["prefill_fp8_us"] * 1e-6) / 1e12, 2)
+    rec["fp8_over_16bit"] = round(rec["prefill_fp8_us"] / rec["prefill16_us"], 3)
+    rec["prefill_fp8_faster_than"] = [name for name in times if name != "prefill_fp8" and rec["prefill_fp8_us"] < rec[name + "_us"]]
+
+
+print(json.dumps(dict(tool="attn_prefill_bench", cache=args.cache, torch=torch.__version__, device=torch.cuda.get_device_name(0), head_dim=D, block=BLOCK,
                       reps=args.reps, replays=args.replays)), flush=True)
 for heads in args.heads.split(","):
     HQ, H = map(int, heads.split("/"))
@@ -75,6 +118,13 @@ for heads in args.heads.split(","):
                     k_cache, v_cache = (torch.randn((B * n_blocks * BLOCK, H, D), device=dev).to(dt) for _ in "kv")
                     q = torch.randn((B * T, HQ * D), device=dev).to(dt)
                     seq = torch.full((B,), n, dtype=torch.int32, device=dev)
+                    if args.cache == "fp8":
+                        rec = dict(heads=heads, seqs=B, dtype=dname, ctx=ctx, T=T, flops=4.0 * D * (T * ctx + T * (T + 1) / 2) * B * HQ)
+                        fp8_point(rec, q, k_cache, v_cache, table, seq, T, HQ, H,
+                                  (T, ctx, B) == tuple(min(map(int, getattr(args, a).split(","))) for a in ("q_lens", "ctx", "seqs")))
+                        print(json.dumps(rec), flush=True)
+                        del k_cache, v_cache
+                        continue
                     pre, dec = quant.PrefillAttention(HQ, H, D, block_size=BLOCK), quant.DecodeAttention(HQ, H, D, block_size=BLOCK)
                     dec.append_route = "kernel"
                     out_p, out_l = torch.empty_like(q), torch.empty_like(q)
