@@ -814,6 +814,52 @@ int sqllm_attn_prefill_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t st
 int sqllm_attn_prefill_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SLIDING-WINDOW prefill attention, on the matrix cores: the four prefill entries above for a model with a sliding window
+ * (Mistral's sliding_window).  The descriptors are sqllm_attn_append and sqllm_attn_append_fp8, unchanged; `window` is a HOST
+ * field of the call.  Kernels of their own; every entry above is unchanged.
+ *
+ *   - Keys.  Token t of sequence b, with L = L(b,t) as the prefill block defines it, attends the keys p in [lo, L),
+ *     lo = max(0, L - window): the query's own key included, `window` keys in all -- Hugging Face's Mistral mask
+ *     kv_idx > q_idx - sliding_window.  window may be INT32_MAX.
+ *   - Values, order.  The formulas of sqllm_attn_prefill_* (for the byte caches: of sqllm_attn_prefill_fp8_*, scales included)
+ *     over [lo, L) only, inside the same fp32-class error bound: the same absolute key tiles [64 i, 64 i + 64) in ascending
+ *     order, the same order inside a tile, the same three planes of the weights; keys below lo are left out of a row's first
+ *     tile the way keys at or above L are left out of its last.  Hence, BIT FOR BIT on finite caches:
+ *       (a) a row with L(b,t) <= window holds EXACTLY THE BITS the entry without a window gives it;
+ *       (b) a row whose lo is a multiple of both 64 and block_size holds exactly the bits the entry without a window gives that
+ *           query in a call with q_len = 1 and seq_lens = L - lo over the table row advanced by lo / block_size entries.
+ *     A row's bits depend only on its own operands, L, window, the scales and the shape fields; bit-identical run to run.
+ *   - What is read.  A query tile (64 consecutive (token, head of the kv group) pairs) with lo_min the least lo and lmax the
+ *     largest L of its rows reads the table entries of the keys lo_min <= p < lmax only: entries of blocks wholly below
+ *     lo_min / block_size are NEVER READ and may hold anything; slots of keys below lo_min are never loaded (the staged rows of
+ *     such keys are zeros written by the kernel, like those at or beyond lmax).  A caller may free or reuse the blocks behind
+ *     the earliest window of a call; a ring of ceil((window + q_len - 1) / block_size) + 1 physical blocks is a rolling buffer
+ *     for chunks of q_len tokens.
+ *   - Corner rows.  +0 rows: padding t >= n_b, and L <= 0.  NaN rows: n_b > T, L > max_blocks*block_size, and a table entry
+ *     outside [0, n_slots) at key p -- which makes NaN EXACTLY the rows with lo(b,t) <= p < L(b,t), and leaves alone the rows of
+ *     the same query tile whose window has passed p; nothing of the caches is read at a bad entry (the walk goes on behind it).
+ *   - Isolation.  Entries of blocks wholly below a row's lo, and slots of keys below it, never influence that row when they hold
+ *     finite values or are not read; keys below lo_min never matter, whatever bits they hold.  The one WEAKER clause of the
+ *     prefill entries carries over and widens: a NON-FINITE v (a NaN BYTE for the byte caches) at a key inside the query tile's
+ *     range [64 * (lo_min / 64), lmax) that some row of the tile attends but this row does not may make that column NaN for this
+ *     row too.  A non-finite k there does not spread: the mask is a select on the score.
+ *   - NO WORKSPACE (the field is ignored and may be NULL), ONE kernel node, capturable; launch geometry from host fields only,
+ *     the grid of the prefill entries; the tiles a workgroup walks, lo_min / 64 .. ceil(lmax / 64) - 1, follow seq_lens and q_lens
+ *     on the device.
+ *
+ * Served shapes and rejections are those of the prefill entry for the same cache type, with its codes and in its order;
+ * window < 1 stands among the counts (SQLLM_E_SHAPE), before the device is touched.  A library without these kernels answers
+ * hipErrorNotSupported, never with another kernel.
+ * Out of scope: attention sinks, ALiBi and soft-capping; a wrap-around table mode; splitting one long sequence's keys across
+ * workgroups; routing sqllm_attn_decode_window_* onto these kernels.
+ * ------------------------------------------------------------------------------------------- */
+int sqllm_attn_prefill_window_f16(const sqllm_attn_append* a, int32_t window, sqllm_stream_t stream);
+int sqllm_attn_prefill_window_bf16(const sqllm_attn_append* a, int32_t window, sqllm_stream_t stream);
+/* the suffix names the type of q and out */
+int sqllm_attn_prefill_window_fp8_f16(const sqllm_attn_append_fp8* a, int32_t window, sqllm_stream_t stream);
+int sqllm_attn_prefill_window_fp8_bf16(const sqllm_attn_append_fp8* a, int32_t window, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The reference operator names.
  * height/width = mat.size(0)/mat.size(1) of the qweight tensor (quant_cuda_kernel.cu:138-139).
  * ------------------------------------------------------------------------------------------- */

@@ -237,6 +237,10 @@ SIGNATURES = {
     "sqllm_attn_prefill_bf16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_prefill_fp8_f16": [POINTER(SqllmAttnAppendFp8), P],
     "sqllm_attn_prefill_fp8_bf16": [POINTER(SqllmAttnAppendFp8), P],
+    "sqllm_attn_prefill_window_f16": [POINTER(SqllmAttnAppend), c_int32, P],
+    "sqllm_attn_prefill_window_bf16": [POINTER(SqllmAttnAppend), c_int32, P],
+    "sqllm_attn_prefill_window_fp8_f16": [POINTER(SqllmAttnAppendFp8), c_int32, P],
+    "sqllm_attn_prefill_window_fp8_bf16": [POINTER(SqllmAttnAppendFp8), c_int32, P],
     "sqllm_attn_window_workspace_bytes": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32],
     "sqllm_attn_decode_window_f16": [POINTER(SqllmAttnDecode), c_int32, P],
     "sqllm_attn_decode_window_bf16": [POINTER(SqllmAttnDecode), c_int32, P],

@@ -25,7 +25,8 @@ SOURCES = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "
            "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip", "sqllm_linear_qkv_cache.hip", "sqllm_linear_qkv_norm_cache.hip", "sqllm_attn_decode.hip",
            "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode_fp8.hip",
            "sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip", "sqllm_attn_window.hip", "sqllm_attn_window_fp8.hip",
-           "sqllm_attn_prefill.hip", "sqllm_attn_prefill_fp8.hip", "sqllm_capi.hip"]
+           "sqllm_attn_prefill.hip", "sqllm_attn_prefill_fp8.hip", "sqllm_attn_prefill_window.hip", "sqllm_attn_prefill_window_fp8.hip",
+           "sqllm_capi.hip"]
 # measured-and-not-adopted kernels (round 3: the streaming batch-1 kernel, the column-pair-table kernel; round 4: the
 # dependency-gated persistent pass) and the host code that routes to them: csrc/experimental/, part of the MEASUREMENT
 # library only (options "stream" / "pair4", entry points sqllm_pass_*)
@@ -43,7 +44,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc", "-
          "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 # sources compiled to an object of their own WITHOUT the packed fp32 VALU instructions (plain v_mul / v_fma instead); the other
 # sources keep the code generation they were measured and pinned with (tests/test_codegen_*_cpu.py)
-NO_PACKED_FP32 = ("sqllm_attn_prefill.hip", "sqllm_attn_prefill_fp8.hip")
+NO_PACKED_FP32 = ("sqllm_attn_prefill.hip", "sqllm_attn_prefill_fp8.hip", "sqllm_attn_prefill_window.hip", "sqllm_attn_prefill_window_fp8.hip")
 NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

@@ -66,6 +66,36 @@ inline AttnPrefillArgs make_prefill_args(const AttnCall& c) {
   return k;
 }
 
+// The sliding-window prefill kernels (sqllm_attn_prefill_window.hip, sqllm_attn_prefill_window_fp8.hip): the same argument and
+// the window behind it, 1 .. INT32_MAX.  Row (b, t) attends the keys [lo, L), lo = L > window ? L - window : 0.
+struct AttnPrefillWindowArgs : AttnPrefillArgs {
+  int window;
+};
+
+// what the window entries serve: the shapes of prefill_served and a window of at least one key
+inline bool prefill_window_served(const AttnCall& c) {
+  AttnCall plain = c;
+  plain.window = 0;
+  return c.window >= 1 && prefill_served(plain);
+}
+
+inline AttnPrefillWindowArgs make_prefill_window_args(const AttnCall& c) {
+  AttnPrefillWindowArgs k;
+  static_cast<AttnPrefillArgs&>(k) = make_prefill_args(c);
+  k.window = c.window;
+  return k;
+}
+
+// the keys [lo, len) of a row inside the key tile [key0, key0 + 64) as a 64-bit mask, bit i for key key0 + i (0 <= lo <= len or
+// len <= 0; no sum that could leave int)
+__device__ __forceinline__ unsigned long long window_tile_bits(int lo, int len, int key0) {
+  const int first = lo > key0 ? lo - key0 : 0;
+  const int end = len > key0 ? (len - key0 < 64 ? len - key0 : 64) : 0;
+  if (end <= first) return 0ull;
+  const unsigned long long below_end = end == 64 ? ~0ull : (1ull << end) - 1ull;
+  return below_end & ~((1ull << first) - 1ull);  // (first < end <= 64)
+}
+
 // 8 bytes of 16-bit elements that are aligned to their elements only
 struct __attribute__((packed, aligned(2))) Packed4 {
   uint32_t w[2];

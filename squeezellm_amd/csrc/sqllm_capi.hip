@@ -24,6 +24,7 @@ AttnLauncher g_launch_attn_window[2] = {};  // [0] set by sqllm_attn_window.hip,
 hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_window.hip
 AttnLauncher g_launch_attn_prefill = nullptr;  // set by sqllm_attn_prefill.hip
 AttnLauncher g_launch_attn_prefill_fp8 = nullptr;  // set by sqllm_attn_prefill_fp8.hip
+AttnLauncher g_launch_attn_prefill_window[2] = {};  // [0] set by sqllm_attn_prefill_window.hip, [1] by sqllm_attn_prefill_window_fp8.hip
 }
 
 namespace sqllm_host {
@@ -1570,7 +1571,7 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
   return (int64_t)batch * n_q_heads * attn_window_parts(max_blocks, block_size, window) * (head_dim + 2) * 4;
 }
 
-// The sixteen attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
+// The twenty attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
 // follows them is passed on by each entry:
 //   `kv_scales` (the fp8 entries): {k_scale, v_scale} of the descriptor -- the caches hold 1-byte e4m3fn elements, their strides
 //     and extents count bytes and they need no alignment; the scales are judged last.  NULL: 16-bit caches.
@@ -1581,6 +1582,8 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
 //   `prefill` (sqllm_attn_prefill_*, with `tokens`): q_len up to 65536 and batch up to 65535 instead of the append entries' two
 //     limits; the workspace field is ignored (NULL allowed, no overlap or alignment rule); the call goes to g_launch_attn_prefill,
 //     with `kv_scales` (sqllm_attn_prefill_fp8_*) to g_launch_attn_prefill_fp8.
+//   `prefill` with `window` (sqllm_attn_prefill_window_*): the prefill call with the count `window`; no workspace and no
+//     partitions either; the call goes to g_launch_attn_prefill_window, a table of its own.
 struct AttnTokensTail {
   const int32_t* q_lens;
   int32_t q_len;
@@ -1662,8 +1665,10 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.q_len = q_len;  // (0: one query per sequence; an append call has passed q_len >= 1 above)
   c.window = window ? *window : 0;
   // (a window has a table of its own: a null slot there is an error, never the kernels without a window)
-  const sqllm::AttnLauncher launch = prefill ? (c.fp8 ? sqllm::g_launch_attn_prefill_fp8 : sqllm::g_launch_attn_prefill)
-                                     : window ? sqllm::g_launch_attn_window[c.fp8 ? 1 : 0] : sqllm::g_launch_attn[sqllm::attn_kind(c)];
+  const sqllm::AttnLauncher launch = prefill && window ? sqllm::g_launch_attn_prefill_window[c.fp8 ? 1 : 0]
+                                     : prefill         ? (c.fp8 ? sqllm::g_launch_attn_prefill_fp8 : sqllm::g_launch_attn_prefill)
+                                     : window          ? sqllm::g_launch_attn_window[c.fp8 ? 1 : 0]
+                                                       : sqllm::g_launch_attn[sqllm::attn_kind(c)];
   return static_cast<int>(launch ? launch(c, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
 }
 
@@ -1738,20 +1743,28 @@ int sqllm_attn_append_f16(const sqllm_attn_append* a, sqllm_stream_t stream) { r
 int sqllm_attn_append_bf16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_append(a, stream, true); }
 int sqllm_attn_append_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, false); }
 int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, true); }
-static int launch_attn_prefill(const sqllm_attn_append* a, sqllm_stream_t stream, bool bf16) {
+static int launch_attn_prefill(const sqllm_attn_append* a, sqllm_stream_t stream, bool bf16, const int32_t* window = nullptr) {
   if (!a) return SQLLM_E_NULL;
   const AttnTokensTail t = attn_tokens(a);
-  return launch_attn(attn_lead(a), stream, bf16, nullptr, &t, nullptr, true);
+  return launch_attn(attn_lead(a), stream, bf16, nullptr, &t, window, true);
 }
 int sqllm_attn_prefill_f16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_prefill(a, stream, false); }
 int sqllm_attn_prefill_bf16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_prefill(a, stream, true); }
-static int launch_attn_prefill_fp8(const sqllm_attn_append_fp8* a, sqllm_stream_t stream, bool bf16) {
+static int launch_attn_prefill_fp8(const sqllm_attn_append_fp8* a, sqllm_stream_t stream, bool bf16, const int32_t* window = nullptr) {
   if (!a) return SQLLM_E_NULL;
   const AttnTokensTail t = attn_tokens(a);
-  return launch_attn_fp8(a, stream, bf16, &t, nullptr, true);
+  return launch_attn_fp8(a, stream, bf16, &t, window, true);
 }
 int sqllm_attn_prefill_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_prefill_fp8(a, stream, false); }
 int sqllm_attn_prefill_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_prefill_fp8(a, stream, true); }
+int sqllm_attn_prefill_window_f16(const sqllm_attn_append* a, int32_t window, sqllm_stream_t stream) { return launch_attn_prefill(a, stream, false, &window); }
+int sqllm_attn_prefill_window_bf16(const sqllm_attn_append* a, int32_t window, sqllm_stream_t stream) { return launch_attn_prefill(a, stream, true, &window); }
+int sqllm_attn_prefill_window_fp8_f16(const sqllm_attn_append_fp8* a, int32_t window, sqllm_stream_t stream) {
+  return launch_attn_prefill_fp8(a, stream, false, &window);
+}
+int sqllm_attn_prefill_window_fp8_bf16(const sqllm_attn_append_fp8* a, int32_t window, sqllm_stream_t stream) {
+  return launch_attn_prefill_fp8(a, stream, true, &window);
+}
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {
   return launch_group_with_events(op, 1, stream, nullptr, nullptr);

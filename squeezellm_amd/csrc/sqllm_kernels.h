@@ -349,6 +349,10 @@ extern AttnLauncher g_launch_attn_prefill;
 // ... and over caches of e4m3fn bytes (sqllm_attn_prefill_fp8_*, sqllm_attn_prefill_fp8.hip): a second slot beside it, for the calls
 // with AttnCall::fp8.  Null until that file is linked in: hipErrorNotSupported, never the 16-bit kernel and never the append kernels.
 extern AttnLauncher g_launch_attn_prefill_fp8;
+// The sliding-window prefill entries (sqllm_attn_prefill_window_*): a table of their own beside g_launch_attn_prefill, [0] the
+// 16-bit caches (sqllm_attn_prefill_window.hip), [1] the byte caches (sqllm_attn_prefill_window_fp8.hip); the call carries
+// AttnCall::window >= 1.  Null until the file is linked in: hipErrorNotSupported, never the prefill kernels without a window.
+extern AttnLauncher g_launch_attn_prefill_window[2];
 hipError_t launch_batched_mfma(int bits, const LaunchArgs& a, hipStream_t stream);        // fp32 matrix instructions
 hipError_t launch_batched_mfma_split(int bits, const LaunchArgs& a, hipStream_t stream);  // bf16 matrix instructions on exactly split operands (sqllm_mfma_split.hip)
 hipError_t launch_batched_mfma_split_all(int bits, const LaunchArgs& a, hipStream_t stream);  // ... tile form, the op's sparse terms in the same grid

@@ -1097,18 +1097,23 @@ def static_cache_blocks(batch: int, n_kv_heads: int, device=None) -> torch.Tenso
     return (torch.arange(int(batch), dtype=torch.int32, device=device) * int(n_kv_heads)).reshape(-1, 1)
 
 
-def ring_block_table(batch: int, window: int, block_size: int, max_len: int, device=None) -> torch.Tensor:
+def ring_block_table(batch: int, window: int, block_size: int, max_len: int, device=None, q_len: int = 1) -> torch.Tensor:
     """The int32 block table [batch, ceil(max_len / block_size)] of a ROLLING buffer for DecodeAttention(..., window=window):
     logical block j of row b is physical block b * R + j % R, with R = ceil(window / block_size) + 1, so a sequence of any
     length up to max_len lives in R blocks (batch * R blocks in all; the front writes position p of row b into slot
     table[b, p // block_size] * block_size + p % block_size, as with any table).  Why R suffices: writing position p overwrites
     position p - R * block_size, and R * block_size >= window + block_size, so with L = p + 1 keys that position is below
     lo = L - window -- it has left the window, at this step and at every later one; the blocks below lo / block_size are never
-    read (include/sqllm_hip.h, sliding-window decode attention).  Without a window the table is wrong: old keys are gone."""
-    batch, window, block_size, max_len = int(batch), int(window), int(block_size), int(max_len)
-    if batch < 1 or window < 1 or block_size < 1 or max_len < 1:
-        raise ValueError(f"batch, window, block_size and max_len must be positive, got {batch}, {window}, {block_size}, {max_len}")
-    R = (window + block_size - 1) // block_size + 1
+    read (include/sqllm_hip.h, sliding-window decode attention).  Without a window the table is wrong: old keys are gone.
+
+    `q_len`: the new tokens per step (PrefillAttention(..., window=window) over chunks of q_len tokens; 1 is the table above).
+    R = ceil((window + q_len - 1) / block_size) + 1.  The argument in one line: a step whose last token has length L needs the
+    keys [L - q_len + 1 - window, L) at once, window + q_len - 1 keys, and the latest write, position L - 1, overwrites position
+    L - 1 - R * block_size <= L - q_len - window - block_size, below the first of them."""
+    batch, window, block_size, max_len, q_len = int(batch), int(window), int(block_size), int(max_len), int(q_len)
+    if batch < 1 or window < 1 or block_size < 1 or max_len < 1 or q_len < 1:
+        raise ValueError(f"batch, window, block_size, max_len and q_len must be positive, got {batch}, {window}, {block_size}, {max_len}, {q_len}")
+    R = (window + q_len - 1 + block_size - 1) // block_size + 1
     j = torch.arange((max_len + block_size - 1) // block_size, dtype=torch.int32, device=device)
     b = torch.arange(batch, dtype=torch.int32, device=device)
     return (b[:, None] * R + (j % R)[None, :]).contiguous()
@@ -1443,6 +1448,8 @@ ATTN_PREFILL_MAX_Q_LEN = 65536  # new tokens per sequence the prefill kernel ser
 ATTN_PREFILL_MAX_BATCH = 65535  # ... and sequences per call
 _ATTN_PREFILL_ENTRIES = {torch.float16: "sqllm_attn_prefill_f16", torch.bfloat16: "sqllm_attn_prefill_bf16"}
 _ATTN_PREFILL_FP8_ENTRIES = {torch.float16: "sqllm_attn_prefill_fp8_f16", torch.bfloat16: "sqllm_attn_prefill_fp8_bf16"}
+_ATTN_PREFILL_WINDOW_ENTRIES = {torch.float16: "sqllm_attn_prefill_window_f16", torch.bfloat16: "sqllm_attn_prefill_window_bf16"}
+_ATTN_PREFILL_WINDOW_FP8_ENTRIES = {torch.float16: "sqllm_attn_prefill_window_fp8_f16", torch.bfloat16: "sqllm_attn_prefill_window_fp8_bf16"}
 
 
 class PrefillAttention(DecodeAttention):
@@ -1452,7 +1459,8 @@ class PrefillAttention(DecodeAttention):
     skipped, no mask tensor, no gathered cache, no expanded heads, no workspace.  Opt-in, beside DecodeAttention, which is unchanged
     (its q_len = 17 stays its fallback); the operand rules, the checks and their helpers are DecodeAttention's.
 
-    PrefillAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None).  No window.
+    PrefillAttention(n_heads, n_kv_heads, head_dim, scale=None, block_size=None, window=None).  window=None: no window, the
+    module below, bit for bit and launch for launch; window=W: the paragraph at the end.
 
     forward(q, k_cache, v_cache, block_table, seq_lens, q_len, q_lens=None, out=None, block_size=None, k_scale=None,
     v_scale=None) -> q's shape.  `q`:
@@ -1485,14 +1493,25 @@ class PrefillAttention(DecodeAttention):
     heads of 128, 1 / 4 sequences, 128 / 512 / 2048 new tokens behind 0 / 2048 keys, fp16 / bf16, paged: 48 points): 16 - 1722 us per
     call; 2.9x - 19.7x faster than a loop of DecodeAttention(q_len=16) calls on all points; 0.90x - 2.98x against torch SDPA on K / V
     gathered from the pages (NOT faster on 4 points, fp16 at 2048 tokens), 0.74x - 1.88x when the gather is not counted (NOT faster
-    on 18)."""
+    on 18).
 
-    def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None):
-        super().__init__(n_heads, n_kv_heads, head_dim, scale=scale, block_size=block_size)
+    PrefillAttention(..., window=W): a SLIDING WINDOW (Mistral's `sliding_window`; validated as DecodeAttention validates it).
+    Token t attends the keys [max(0, L - W), L), L = seq_lens[b] - (n_b - 1 - t): the query's own key included, W keys in all.
+    The served shapes take kernels of their own (sqllm_attn_prefill_window_f16 / _bf16 / _fp8_f16 / _fp8_bf16; include/sqllm_hip.h,
+    sliding-window prefill attention; `last_route` "attn_prefill_window"): one kernel node, no workspace, and a query tile walks
+    only the key tiles between its earliest window and its longest row -- about W / 64 + 2 of them, however long the context.
+    Rows with L <= W hold exactly the bits of the module without a window.  Table entries of blocks wholly below a query tile's
+    earliest window are never read and the slots of those keys never loaded: the caller may free or reuse them, and
+    ring_block_table(..., q_len=T) is the table of a rolling buffer for chunks of T tokens.  A table entry outside the cache
+    makes NaN exactly the tokens that attend its keys.  Everything else takes the torch fallback with the same window.  Speed:
+    tools/attn_prefill_bench.py --window, DESIGN.md 4.4."""
+
+    def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None, window=None):
+        super().__init__(n_heads, n_kv_heads, head_dim, scale=scale, block_size=block_size, window=window)
 
     @property
     def last_route(self):
-        """"attn_prefill" or "fallback": the way the most recent forward went (None before the first)."""
+        """"attn_prefill", "attn_prefill_window" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
@@ -1510,13 +1529,14 @@ class PrefillAttention(DecodeAttention):
         if not kernel:
             self.__dict__["_last_route"] = "fallback"
             table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
-            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
+            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale, self.window)
             if out is not None:
                 out.copy_(o)
                 return out
             return o.reshape(*q.shape[:-1], W)
         bt, sl, ql = self._int32_operands(block_table, seq_lens, q_lens)
-        self.__dict__["_last_route"] = "attn_prefill"
+        window = self.window
+        self.__dict__["_last_route"] = "attn_prefill" if window is None else "attn_prefill_window"
         max_blocks = bt.shape[1]
         dev = q2.get_device()
         o = out if out is not None else torch.empty((rows, W), dtype=q2.dtype, device=q2.device)
@@ -1541,15 +1561,19 @@ class PrefillAttention(DecodeAttention):
         a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
         if fp8:
             a.k_scale, a.v_scale = k_scale, v_scale
-        quant_cuda._launch(quant_cuda._fn((_ATTN_PREFILL_FP8_ENTRIES if fp8 else _ATTN_PREFILL_ENTRIES)[q2.dtype]), dev, (ref,))
+        if window is None:
+            quant_cuda._launch(quant_cuda._fn((_ATTN_PREFILL_FP8_ENTRIES if fp8 else _ATTN_PREFILL_ENTRIES)[q2.dtype]), dev, (ref,))
+        else:  # (kernels of their own: a missing one is an error, never the kernels without a window)
+            quant_cuda._launch(quant_cuda._fn((_ATTN_PREFILL_WINDOW_FP8_ENTRIES if fp8 else _ATTN_PREFILL_WINDOW_ENTRIES)[q2.dtype]), dev, (ref, window))
         return o if out is not None else o.reshape(*q.shape[:-1], W)
 
 
-def fuse_prefill_attention(module: nn.Module, n_heads=None, n_kv_heads=None) -> int:
+def fuse_prefill_attention(module: nn.Module, n_heads=None, n_kv_heads=None, window=None) -> int:
     """Give every submodule of `module` that carries a `qkv_rope` (fuse_qkv_rope) an attribute `attend_prefill`, a
     PrefillAttention for its heads, the way fuse_decode_attention gives it `attend_decode`: through `__dict__`, not a child -- the
     module tree, the state dict and every `forward` stay as they are.  An attention forward calls
-    `self.attend_prefill(q, k_cache, v_cache, block_table, seq_lens, q_len)` when q_len > 1.  Returns the count."""
+    `self.attend_prefill(q, k_cache, v_cache, block_table, seq_lens, q_len)` when q_len > 1.  `window`: the model's
+    sliding window (Mistral: model.config.sliding_window), passed to every PrefillAttention; None: no window.  Returns the count."""
     n = 0
     for m in module.modules():
         front = m.__dict__.get("qkv_rope")
@@ -1560,7 +1584,7 @@ def fuse_prefill_attention(module: nn.Module, n_heads=None, n_kv_heads=None) -> 
         hk = int(n_kv_heads) if n_kv_heads is not None else front.k.outfeatures // d
         if hq < 1 or hk < 1 or hq % hk:
             continue
-        m.__dict__["attend_prefill"] = PrefillAttention(hq, hk, d)
+        m.__dict__["attend_prefill"] = PrefillAttention(hq, hk, d, window=window)
         n += 1
     return n
 

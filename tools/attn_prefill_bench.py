@@ -17,6 +17,15 @@ With --cache fp8 (> profiles/attn_prefill_fp8_bench.txt) the same points compare
   fallback     what an fp8 cache took before the kernel: the torch route (append_as_decode_rows and the fallback of DecodeAttention),
                eager, on the smallest points only (the fewest tokens, keys and sequences: it gathers [rows, keys, H, D] in fp32)
 prefill_fp8 is checked against prefill16 (at most 2^-6) before anything is timed.
+With --window W (> profiles/attn_prefill_window_bench.txt; with either --cache) the points compare, on the same operands:
+  window       one PrefillAttention(window=W) call: token t attends the last W keys below its length
+  full         the prefill kernel WITHOUT a window: beyond W keys it computes another function -- the time yardstick only
+  sdpa         torch scaled_dot_product_attention with a BAND mask on K / V gathered from the pages (an fp8 cache: dequantised in the
+               gather), timed with the gather; only where seqs * T * (ctx + T) <= --sdpa-cap (the mask and the scores are dense: the
+               larger points would take most of a run), otherwise NOT MEASURED (null)
+window is checked against sdpa where that runs (at most 2^-6), and against full on the rows with L <= W (equal bits).  A contender
+whose single replay takes long is replayed fewer times per round (at least 3; "replays" in the record); `tiles_ratio` is the
+windowed walk's share of the full one by the tile count, min(1, (W + 64 / group) / (ctx + T / 2)).
 prefill is checked against loop16 (largest absolute difference printed, at most 2^-6) before anything is timed.  Each contender
 is captured once after an eager warm-up; --reps rounds, each replaying every contender --replays times between two events, in
 turn.  One JSON line per point: median us and spread (max - min over the rounds) per contender, the causal-trimmed operation count
@@ -35,6 +44,9 @@ ap.add_argument("--dtypes", default="fp16,bf16")
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--replays", type=int, default=50)
 ap.add_argument("--cache", default="16bit", choices=("16bit", "fp8"))
+ap.add_argument("--window", type=int, default=None)
+ap.add_argument("--sdpa-cap", type=float, default=4 * 2048 * 6144.0)
+ap.add_argument("--round-us", type=float, default=60000.0, help="--window: the time one contender may take per round")
 args = ap.parse_args()
 
 import torch  # noqa: E402
@@ -101,7 +113,50 @@ def fp8_point(rec, q, k_cache, v_cache, table, seq, T, HQ, H, smallest):
     rec["prefill_fp8_faster_than"] = [name for name in times if name != "prefill_fp8" and rec["prefill_fp8_us"] < rec[name + "_us"]]
 
 
-print(json.dumps(dict(tool="attn_prefill_bench", cache=args.cache, torch=torch.__version__, device=torch.cuda.get_device_name(0), head_dim=D, block=BLOCK,
+def window_point(rec, q, k_cache, v_cache, table, seq, T, HQ, H, ctx, Wn):
+    """the --window contenders of one point -> rec"""
+    B, G, n, S = seq.numel(), HQ // H, ctx + T, 2.0 ** -6
+    kw = {}
+    if args.cache == "fp8":
+        k_cache, v_cache = (quant._fp8_bytes(c.float(), S).view(torch.float8_e4m3fn) for c in (k_cache, v_cache))
+        kw = dict(k_scale=S, v_scale=S)
+    att_w, att_f = quant.PrefillAttention(HQ, H, D, block_size=BLOCK, window=Wn), quant.PrefillAttention(HQ, H, D, block_size=BLOCK)
+    out_w, out_f = torch.empty_like(q), torch.empty_like(q)
+    runs = {"window": lambda: att_w(q, k_cache, v_cache, table, seq, T, out=out_w, **kw),
+            "full": lambda: att_f(q, k_cache, v_cache, table, seq, T, out=out_f, **kw)}
+    for run in runs.values(): run()
+    assert att_w.last_route == "attn_prefill_window" and att_f.last_route == "attn_prefill"
+    inside = max(0, min(T, Wn - ctx))  # the tokens with L <= W: the first `inside` of every sequence
+    if inside:
+        assert torch.equal(out_w.view(B, T, -1)[:, :inside].view(torch.int16), out_f.view(B, T, -1)[:, :inside].view(torch.int16))
+    if B * T * n <= args.sdpa_cap:
+        slot = (table.long()[:, :, None] * BLOCK + torch.arange(BLOCK, device=dev)[None, None, :]).reshape(B, -1)[:, :n]
+        mask = torch.ones((T, n), dtype=torch.bool, device=dev).tril(diagonal=ctx).triu(diagonal=ctx - Wn + 1)
+        q4 = q.view(B, T, HQ, D).transpose(1, 2)
+
+        def run_sdpa():
+            k, v = (((c.view(torch.float8_e4m3fn)[slot].float() * S).to(q.dtype) if kw else c[slot]).permute(0, 2, 1, 3) for c in (k_cache, v_cache))
+            if G > 1: k, v = k.repeat_interleave(G, dim=1), v.repeat_interleave(G, dim=1)
+            return torch.nn.functional.scaled_dot_product_attention(q4, k, v, attn_mask=mask)
+        rec["max_abs_diff_vs_sdpa"] = diff = float((run_sdpa().transpose(1, 2).reshape(B * T, -1).float() - out_w.float()).abs().max())
+        assert diff <= 2.0 ** -6, diff
+        runs["sdpa"] = run_sdpa
+    graphs = {name: capture(run) for name, run in runs.items()}
+    replays = {name: int(max(3, min(args.replays, args.round_us / max(replay_us(gr, 2), 1.0)))) for name, gr in graphs.items()}  # (and the warm-up)
+    times = {name: [] for name in graphs}
+    for _ in range(args.reps):
+        for name, gr in graphs.items():  # alternately
+            times[name].append(replay_us(gr, replays[name]))
+    rec["replays"] = replays
+    for name in ("window", "full", "sdpa"):
+        ts = times.get(name)
+        rec[name + "_us"], rec[name + "_spread_us"] = (round(statistics.median(ts), 1), round(max(ts) - min(ts), 1)) if ts else (None, None)
+    rec["tiles_ratio"] = round(min(1.0, (Wn + 64.0 / G) / (ctx + T / 2.0)), 3)
+    rec["window_over_full"] = round(rec["window_us"] / rec["full_us"], 3)
+    rec["window_faster_than"] = [name for name in ("full", "sdpa") if rec[name + "_us"] is not None and rec["window_us"] < rec[name + "_us"]]
+
+
+print(json.dumps(dict(tool="attn_prefill_bench", cache=args.cache, window=args.window, torch=torch.__version__, device=torch.cuda.get_device_name(0), head_dim=D, block=BLOCK,
                       reps=args.reps, replays=args.replays)), flush=True)
 for heads in args.heads.split(","):
     HQ, H = map(int, heads.split("/"))
@@ -118,6 +173,12 @@ for heads in args.heads.split(","):
                     k_cache, v_cache = (torch.randn((B * n_blocks * BLOCK, H, D), device=dev).to(dt) for _ in "kv")
                     q = torch.randn((B * T, HQ * D), device=dev).to(dt)
                     seq = torch.full((B,), n, dtype=torch.int32, device=dev)
+                    if args.window is not None:
+                        rec = dict(heads=heads, seqs=B, dtype=dname, ctx=ctx, T=T, window=args.window)
+                        window_point(rec, q, k_cache, v_cache, table, seq, T, HQ, H, ctx, args.window)
+                        print(json.dumps(rec), flush=True)
+                        del k_cache, v_cache
+                        continue
                     if args.cache == "fp8":
                         rec = dict(heads=heads, seqs=B, dtype=dname, ctx=ctx, T=T, flops=4.0 * D * (T * ctx + T * (T + 1) / 2) * B * HQ)
                         fp8_point(rec, q, k_cache, v_cache, table, seq, T, HQ, H,
