@@ -691,6 +691,87 @@ int sqllm_attn_append_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t str
 int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Tree-masked decode attention: the new tokens of a sequence form a TREE of draft tokens (Medusa, EAGLE, SpecInfer), verified in
+ * one read of K and V.  sqllm_attn_tree is the fields of sqllm_attn_append, in the same order, followed by tree_mask and
+ * mask_stride; sqllm_attn_tree_fp8 is the fields of sqllm_attn_append_fp8 followed by the same two.
+ *
+ *   - Nodes.  Rows, tables, q_lens and seq_lens as sqllm_attn_append: n_b = q_lens ? q_lens[b] : q_len real new tokens ("nodes"),
+ *     seq_lens[b] counts them too.  C_b = seq_lens[b] - n_b is the context length; node j is the key at position C_b + j.
+ *   - Mask.  tree_mask: int32 [batch, mask_stride] in DEVICE memory, used without a copy; a captured graph follows it updated
+ *     in place.  m(b,t) = tree_mask[b * mask_stride + t] & ((1 << n_b) - 1): bits at and above n_b are ignored.
+ *   - Attended keys.  Row (b, t) with t < n_b attends the keys [0, C_b) and node j for every set bit j of m(b,t).  Any bit
+ *     pattern is legal: j > t is allowed, a missing own bit is allowed.  The kernel does not interpret the tree, it applies the
+ *     mask.  Leff(b,t) = C_b + 1 + (index of the highest set bit of m), or C_b when m == 0, is the row's effective length.
+ *   - Values.  The formulas, the fp32 arithmetic, the one rounding, the partitions of SQLLM_ATTN_PARTITION absolute keys and the
+ *     ascending combine of sqllm_attn_decode, over the attended keys.  Partials exist for the partitions below Leff, and none
+ *     of them is empty of attended keys: the nodes span at most 16 keys, so they touch at most two partitions; a partition that
+ *     begins below C_b holds context keys, which every row attends; one that begins at or behind C_b lies within 15 keys of
+ *     it, so it holds the whole rest of the nodes, the row's highest attended node (the one that puts the partition below Leff)
+ *     among them.  The first of two node partitions is empty of context only when C_b lies on its edge -- and then it holds
+ *     all the nodes and there is no second.
+ *   - Chain identity.  With m(b,t) = (2 << t) - 1 every row holds EXACTLY THE BITS of sqllm_attn_append_* (of
+ *     sqllm_attn_append_fp8_* for the byte caches) on the same operands wherever C_b >= 0, hence of the one-query entry.  An
+ *     excluded key's score is -inf, its softmax weight is +0 and is added to the sum; in the sum over v it is left out by a
+ *     select, never by a factor 0.
+ *   - Corner rows, judged in this order.  n_b > q_len: the sequence's q_len rows are NaN.  n_b <= 0: they are +0.
+ *     seq_lens[b] < n_b (a negative context): they are NaN.  t >= n_b: padding, +0.  A row with no attended key (C_b == 0 and
+ *     m == 0) is +0.  Leff > max_blocks * block_size: NaN for that row.  A table entry outside [0, n_slots) that covers any key
+ *     below Leff(b,t), attended or not, makes that row NaN; rows that end below it are exact.  Nothing outside the cache is read.
+ *   - Isolation.  A NaN or inf in k or v at a node the row does not attend leaves the row's bits unchanged.  Unaddressed
+ *     slots never matter.  A row's bits do not depend on the other sequences, the batch size or timing.
+ *   - Launch.  The workspace is sqllm_attn_decode_workspace_bytes(batch*q_len, ...), CONTENTS IRRELEVANT.  TWO kernel nodes, ONE
+ *     when max_blocks * block_size <= SQLLM_ATTN_PARTITION.  No allocation, capturable, geometry from host fields only.
+ *
+ * Served as sqllm_attn_append: head_dim 64 or 128; a head ratio of 1 to 8; q_len 1 to 16; batch*q_len <= 64; fp16 / bf16 over a
+ * 16-bit or e4m3fn cache.  Rejections are sqllm_attn_append's (sqllm_attn_append_fp8's), with their codes and in their order,
+ * plus: a NULL tree_mask among the NULLs (SQLLM_E_NULL); mask_stride < q_len among the strides (SQLLM_E_SHAPE); out or the
+ * workspace overlapping the mask among the overlaps (SQLLM_E_SHAPE); a mask not aligned to 4 bytes among the alignments
+ * (SQLLM_E_ALIGN).  A library without the tree kernels answers hipErrorNotSupported, never with the append kernels.
+ * Not covered: more than 16 nodes per sequence or 64 rows, a sliding window together with a tree, tree masks on the prefill
+ * entries, accepting a path and compacting the cache afterwards (the caller's).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_attn_tree {
+  const void* q;            /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride q_stride elements */
+  void* out;                /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride out_stride; OVERWRITTEN */
+  const void* k_cache;      /* as sqllm_kv_cache */
+  const void* v_cache;
+  const int32_t* block_table; /* int32 [batch, table_stride], DEVICE memory: one row per sequence */
+  const int32_t* seq_lens;    /* int32 [batch], DEVICE memory: the keys of sequence b, its new tokens included */
+  int32_t batch, n_q_heads, n_kv_heads, head_dim;   /* batch: sequences */
+  int32_t n_slots, block_size, max_blocks, table_stride;   /* max_blocks <= table_stride */
+  int64_t slot_stride, head_stride, q_stride, out_stride;
+  float scale;              /* the caller's, usually 1/sqrt(head_dim); finite */
+  void* workspace;          /* sqllm_attn_decode_workspace_bytes(batch * q_len, ...); contents irrelevant */
+  const int32_t* q_lens;    /* int32 [batch], DEVICE memory, or NULL: q_len real tokens in every sequence */
+  int32_t q_len;            /* rows per sequence, 1 to 16 */
+  const int32_t* tree_mask; /* int32 [batch, mask_stride], DEVICE memory: word (b, t), bit j = row (b, t) attends node j */
+  int64_t mask_stride;      /* words between the sequences' rows of tree_mask, >= q_len */
+} sqllm_attn_tree;
+int sqllm_attn_tree_f16(const sqllm_attn_tree* a, sqllm_stream_t stream);
+int sqllm_attn_tree_bf16(const sqllm_attn_tree* a, sqllm_stream_t stream);
+typedef struct sqllm_attn_tree_fp8 {
+  const void* q;            /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride q_stride elements */
+  void* out;                /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride out_stride; OVERWRITTEN */
+  const void* k_cache;      /* as sqllm_kv_cache_fp8 */
+  const void* v_cache;
+  const int32_t* block_table; /* int32 [batch, table_stride], DEVICE memory: one row per sequence */
+  const int32_t* seq_lens;    /* int32 [batch], DEVICE memory: the keys of sequence b, its new tokens included */
+  int32_t batch, n_q_heads, n_kv_heads, head_dim;   /* batch: sequences */
+  int32_t n_slots, block_size, max_blocks, table_stride;   /* max_blocks <= table_stride */
+  int64_t slot_stride, head_stride, q_stride, out_stride;  /* the first two in bytes, the last two in 16-bit elements */
+  float scale;              /* the caller's, usually 1/sqrt(head_dim); finite */
+  void* workspace;          /* sqllm_attn_decode_workspace_bytes(batch * q_len, ...); contents irrelevant */
+  float k_scale, v_scale;   /* the cache's, as the front was given them */
+  const int32_t* q_lens;    /* int32 [batch], DEVICE memory, or NULL */
+  int32_t q_len;            /* rows per sequence, 1 to 16 */
+  const int32_t* tree_mask; /* as sqllm_attn_tree */
+  int64_t mask_stride;
+} sqllm_attn_tree_fp8;
+/* the suffix names the type of q and out */
+int sqllm_attn_tree_fp8_f16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
+int sqllm_attn_tree_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sliding-window decode attention: ONE new query per sequence, attending the LAST `window` keys the cache holds for that
  * sequence (Mistral's sliding_window).  The descriptors are sqllm_attn_decode and sqllm_attn_decode_fp8, unchanged; `window`
  * is a HOST field of the call.

@@ -120,6 +120,19 @@ class SqllmAttnAppendFp8(ctypes.Structure):
     _fields_ = SqllmAttnDecodeFp8._fields_ + [("q_lens", c_void_p), ("q_len", c_int32)]
 
 
+class SqllmAttnTree(ctypes.Structure):
+    """struct sqllm_attn_tree (include/sqllm_hip.h): sqllm_attn_append followed by the tree mask -- one int32 word per row, bit j:
+    the row attends new token j of its sequence -- and the words between the sequences' rows of it."""
+
+    _fields_ = SqllmAttnAppend._fields_ + [("tree_mask", c_void_p), ("mask_stride", ctypes.c_int64)]
+
+
+class SqllmAttnTreeFp8(ctypes.Structure):
+    """struct sqllm_attn_tree_fp8 (include/sqllm_hip.h): sqllm_attn_append_fp8 followed by the same two fields."""
+
+    _fields_ = SqllmAttnAppendFp8._fields_ + [("tree_mask", c_void_p), ("mask_stride", ctypes.c_int64)]
+
+
 class SqllmQkvRope(ctypes.Structure):
     """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
 
@@ -233,6 +246,10 @@ SIGNATURES = {
     "sqllm_attn_append_bf16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_append_fp8_f16": [POINTER(SqllmAttnAppendFp8), P],
     "sqllm_attn_append_fp8_bf16": [POINTER(SqllmAttnAppendFp8), P],
+    "sqllm_attn_tree_f16": [POINTER(SqllmAttnTree), P],
+    "sqllm_attn_tree_bf16": [POINTER(SqllmAttnTree), P],
+    "sqllm_attn_tree_fp8_f16": [POINTER(SqllmAttnTreeFp8), P],
+    "sqllm_attn_tree_fp8_bf16": [POINTER(SqllmAttnTreeFp8), P],
     "sqllm_attn_prefill_f16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_prefill_bf16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_prefill_fp8_f16": [POINTER(SqllmAttnAppendFp8), P],

@@ -25,6 +25,7 @@ SOURCES = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "
            "sqllm_linear_gated_norm.hip", "sqllm_linear_qkv_norm.hip", "sqllm_linear_qkv_cache.hip", "sqllm_linear_qkv_norm_cache.hip", "sqllm_attn_decode.hip",
            "sqllm_linear_qkv_cache_fp8.hip", "sqllm_linear_qkv_norm_cache_fp8.hip", "sqllm_attn_decode_fp8.hip",
            "sqllm_attn_append.hip", "sqllm_attn_append_fp8.hip", "sqllm_attn_window.hip", "sqllm_attn_window_fp8.hip",
+           "sqllm_attn_tree.hip", "sqllm_attn_tree_fp8.hip",
            "sqllm_attn_prefill.hip", "sqllm_attn_prefill_fp8.hip", "sqllm_attn_prefill_window.hip", "sqllm_attn_prefill_window_fp8.hip",
            "sqllm_capi.hip"]
 # measured-and-not-adopted kernels (round 3: the streaming batch-1 kernel, the column-pair-table kernel; round 4: the

@@ -1,7 +1,8 @@
 // sqllm_attn.h -- what the six decode-attention kernel files share (sqllm_attn_decode.hip, sqllm_attn_decode_fp8.hip,
 // sqllm_attn_append.hip, sqllm_attn_append_fp8.hip, sqllm_attn_window.hip, sqllm_attn_window_fp8.hip): the lane helpers for 16-bit elements and for byte caches, the length of an append
 // row and phase 0 of the append kernels, and the launch ladder launch_attn<TAG>.  NOT shared: the bodies of the partial kernels
-// and of the combines, which stay copies of each other ("Not shared either").
+// and of the combines, which stay copies of each other ("Not shared either").  The two tree files
+// (sqllm_attn_tree.hip, sqllm_attn_tree_fp8.hip) take the helpers, the ladder and a phase 0 of their own from here as well.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -206,6 +207,132 @@ __device__ __forceinline__ bool append_phase0(const AttnAppendArgs& a, int part,
 }
 
 // ------------------------------------------------------------------------------------------------
+// a token tree over the new tokens (sqllm_attn_tree.hip, sqllm_attn_tree_fp8.hip)
+// ------------------------------------------------------------------------------------------------
+// Leff(b, t) of include/sqllm_hip.h (sqllm_attn_tree): the context C = seq - n and the nodes up to the highest set bit of the row's
+// word, in [1, capacity]; 0 for a row that is +0 (no real tokens, padding, nothing attended); -1 for a row that is NaN (n > q_len,
+// a negative context, Leff > capacity).  64-bit: seq is any int32.
+__device__ __forceinline__ int tree_row_len(int n, int seq, int t, int q_len, int capacity, int word) {
+  if (n > q_len) return -1;
+  if (n <= 0) return 0;
+  if (seq < n) return -1;
+  if (t >= n) return 0;
+  const unsigned m = (unsigned)word & ((1u << n) - 1u);  // (1 <= n <= q_len <= 16)
+  const long long len = (long long)seq - n + (m ? 32 - __builtin_clz(m) : 0);
+  if (len == 0) return 0;
+  if (len > capacity) return -1;
+  return (int)len;
+}
+
+// Key kl of a partition whose first `ctx` keys are context: every head's below ctx, behind it the head's own by bit kl - ctx of its
+// word `w` (the row's mask shifted to the partition's origin: tree_phase0).
+__device__ __forceinline__ bool tree_key(unsigned w, int kl, int ctx) {
+  const unsigned j = (unsigned)(kl - ctx);
+  return kl < ctx || (j < 16u && (w >> j & 1u));
+}
+
+// Phase 0 of a tree workgroup: append_phase0 with two differences.  nv[h] comes from Leff, and with it the head's mask word, shifted
+// so that bit i is key ctx + i of THIS partition, goes to LDS (mwl[h], beside nvl[h]).  And what the heads share is not the
+// shortest head's end but the CONTEXT's end inside the partition, ctx = clamp(C - 256 * part, 0, 256): one scalar per workgroup,
+// per sequence and not per head.  The keys below it are every head's; the at most 16 keys behind it are the nodes.  ctx <= n_max
+// wherever true is returned: a served head ends at or behind the context.
+template <int D, int GC, typename OT>
+__device__ __forceinline__ bool tree_phase0(const AttnTreeArgs& a, int part, int hk, int b, int chunk, int* slots, int* first_bad, int* nvl,
+                                            unsigned* mwl, int (&nv)[GC], int& n_max, int& ctx) {
+  constexpr int P = kAttnPartition;
+  const int tid = threadIdx.x, g = a.group, p0 = part * P;
+  const bool single = a.n_parts == 1;
+  OT* const out = reinterpret_cast<OT*>(a.out);
+  const int n = a.q_lens ? a.q_lens[b] : a.q_len, seq = a.seq_lens[b];
+  const int* const words = a.tree_mask + (long long)b * a.mask_stride;
+  const long long far = (long long)seq - n - p0;  // the context's end from the partition's origin
+  const int rel = far < -16 ? -16 : far > P ? P : (int)far;
+  ctx = rel < 0 ? 0 : rel;
+  const unsigned real = n >= 1 && n <= 16 ? (1u << n) - 1u : 0u;
+  int t = __builtin_amdgcn_readfirstlane(chunk * GC / g), hh = chunk * GC - t * g;  // (a uniform quotient: back to a scalar)
+  n_max = 0;
+#pragma unroll
+  for (int h = 0; h < GC; ++h) {
+    nv[h] = 0;
+    unsigned w = 0;
+    if (t < a.q_len) {
+      const int word = words[t];
+      const int len = tree_row_len(n, seq, t, a.q_len, a.capacity, word);
+      if (len > p0) nv[h] = len - p0 < P ? len - p0 : P;
+      w = (unsigned)word & real;
+      w = rel < 0 ? w >> -rel : w;
+    }
+    if (tid == h) mwl[h] = w;
+    n_max = nv[h] > n_max ? nv[h] : n_max;
+    if (++hh == g) {
+      hh = 0;
+      ++t;
+    }
+  }
+  if (single) {  // this launch is the whole call: the +0 and the NaN rows (otherwise the combine writes them); a loop that stays a loop
+#pragma unroll 1
+    for (int h = 0; h < GC; ++h) {
+      const int vh = chunk * GC + h, tok = __builtin_amdgcn_readfirstlane(vh / g);
+      if (tok >= a.q_len) break;
+      const int len = tree_row_len(n, seq, tok, a.q_len, a.capacity, words[tok]);
+      if (len > 0) continue;
+      const OT c = len == 0 ? (OT)0.0f : (OT)__builtin_nanf("");
+      OT* const o = out + (long long)(b * a.q_len + tok) * a.out_stride + (long long)(hk * g + vh - tok * g) * D;
+      for (int i = tid; i < D; i += kAttnThreads) o[i] = c;
+    }
+  }
+  if (n_max == 0) return false;
+
+  const unsigned p = tid < n_max ? p0 + tid : p0;
+  const unsigned blk = p / (unsigned)a.block_size, off = p - blk * (unsigned)a.block_size;
+  const long long s = (long long)a.block_table[(long long)b * a.table_stride + blk] * a.block_size + off;
+  const bool bad = s < 0 || s >= a.n_slots;
+  slots[tid] = (int)s;
+  int fb = P;  // the lowest key of the partition with a bad entry
+  if (__syncthreads_or(bad)) {
+    if (tid == 0) *first_bad = P;
+    __syncthreads();
+    if (bad) atomicMin(first_bad, tid < n_max ? tid : 0);
+    __syncthreads();
+    fb = __builtin_amdgcn_readfirstlane(*first_bad);
+  }
+  n_max = 0;
+  unsigned nan_heads = 0;  // the heads whose Leff lies behind the bad entry: NaN, and nothing of the caches is read for them
+#pragma unroll
+  for (int h = 0; h < GC; ++h) {
+    if (nv[h] > fb) {
+      nan_heads |= 1u << h;
+      nv[h] = 0;
+    }
+    n_max = nv[h] > n_max ? nv[h] : n_max;
+    if (tid == h) nvl[h] = nv[h];
+  }
+#pragma unroll 1
+  for (int h = 0; nan_heads >> h; ++h) {  // (a loop that stays a loop, as above)
+    if (!(nan_heads >> h & 1)) continue;
+    const float nan = __builtin_nanf("");
+    const AppendHead v = append_head(a, hk, b, chunk * GC + h);
+    if (single) {
+      OT* const o = out + (long long)v.row * a.out_stride + (long long)v.head * D;
+      for (int i = tid; i < D; i += kAttnThreads) o[i] = (OT)nan;
+    } else {
+      const long long at = ((long long)v.row * a.n_q_heads + v.head) * a.n_parts + part;
+      for (int i = tid; i < D; i += kAttnThreads) {
+        a.ws_acc[at * D + i] = nan;
+        if (i == 0) {
+          a.ws_ml[at * 2] = 0.0f;
+          a.ws_ml[at * 2 + 1] = nan;
+        }
+      }
+    }
+  }
+  if (n_max == 0) return false;
+  if (tid >= n_max) slots[tid] = slots[0];  // (n_max <= fb: key 0 of the partition is a good one)
+  __syncthreads();
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The launch ladder of the six kernel files, written once (as launch_front<TAG> of sqllm_fused.h): {_Float16, __bf16} x head_dim
 // 64 / 128 x group class 1 / 2 / 3-4 / 8 -> one instantiation of the partial kernel TAG names; with more than one partition the
 // combine behind it.  A kernel file says
@@ -239,6 +366,13 @@ struct AttnTokens {
   static dim3 grid(const Args& k, const AttnCall& c) { return dim3(k.n_parts, c.n_kv_heads, k.batch * ((k.q_len * k.group + GC - 1) / GC)); }
   static bool has_combine() { return g_launch_attn_append_combine != nullptr; }
   static hipError_t combine(const Args& k, const AttnCall& c, hipStream_t stream) { return g_launch_attn_append_combine(k, c.head_dim, c.bf16, stream); }
+};
+// several new tokens per sequence under a tree mask: the grid and the virtual heads of AttnTokens, the tree combine
+struct AttnTreeTokens : AttnTokens {
+  typedef AttnTreeArgs Args;
+  static bool served(const AttnCall& c) { return AttnTokens::served(c) && c.tree_mask != nullptr; }
+  static bool has_combine() { return g_launch_attn_tree_combine != nullptr; }
+  static hipError_t combine(const Args& k, const AttnCall& c, hipStream_t stream) { return g_launch_attn_tree_combine(k, c.head_dim, c.bf16, stream); }
 };
 // one query per sequence over the last `window` keys: win_parts (k.n_parts) workgroups per (kv head, row), the window combine
 struct AttnWindowQuery {

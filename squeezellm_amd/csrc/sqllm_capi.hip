@@ -20,6 +20,8 @@ FrontLauncher g_launch_front[kFrontKinds] = {};  // each slot set by its kernel 
 AttnLauncher g_launch_attn[kAttnKinds] = {};  // each slot set by its kernel file (sqllm_attn_decode.hip ... sqllm_attn_append_fp8.hip)
 hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_decode.hip
 hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
+AttnLauncher g_launch_attn_tree[2] = {};  // [0] set by sqllm_attn_tree.hip, [1] by sqllm_attn_tree_fp8.hip
+hipError_t (*g_launch_attn_tree_combine)(const AttnTreeArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_tree.hip
 AttnLauncher g_launch_attn_window[2] = {};  // [0] set by sqllm_attn_window.hip, [1] by sqllm_attn_window_fp8.hip
 hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_window.hip
 AttnLauncher g_launch_attn_prefill = nullptr;  // set by sqllm_attn_prefill.hip
@@ -1571,7 +1573,7 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
   return (int64_t)batch * n_q_heads * attn_window_parts(max_blocks, block_size, window) * (head_dim + 2) * 4;
 }
 
-// The twenty attention entries.  The four descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
+// The twenty-four attention entries.  The six descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
 // follows them is passed on by each entry:
 //   `kv_scales` (the fp8 entries): {k_scale, v_scale} of the descriptor -- the caches hold 1-byte e4m3fn elements, their strides
 //     and extents count bytes and they need no alignment; the scales are judged last.  NULL: 16-bit caches.
@@ -1584,25 +1586,35 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
 //     with `kv_scales` (sqllm_attn_prefill_fp8_*) to g_launch_attn_prefill_fp8.
 //   `prefill` with `window` (sqllm_attn_prefill_window_*): the prefill call with the count `window`; no workspace and no
 //     partitions either; the call goes to g_launch_attn_prefill_window, a table of its own.
+//   `tree` (sqllm_attn_tree_*, with `tokens`): the append call with one mask word per row; NULL among the NULLs, its stride among
+//     the strides, the mask among the tensors out and the workspace must not overlap, its alignment among the alignments; the call
+//     goes to g_launch_attn_tree, a table of its own.
 struct AttnTokensTail {
   const int32_t* q_lens;
   int32_t q_len;
 };
+struct AttnTreeTail {
+  const int32_t* tree_mask;
+  int64_t mask_stride;
+};
 static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, bool bf16, const float* kv_scales, const AttnTokensTail* tokens,
-                       const int32_t* window = nullptr, bool prefill = false) {
+                       const int32_t* window = nullptr, bool prefill = false, const AttnTreeTail* tree = nullptr) {
   const sqllm_attn_decode* const a = &lead;
   const bool append = tokens != nullptr;
   const int32_t q_len = append ? tokens->q_len : 0;
   const int32_t* const q_lens = append ? tokens->q_lens : nullptr;
   const int celem = kv_scales ? 1 : 2;  // bytes per cache element
-  if (!a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || (!prefill && !a->workspace)) return SQLLM_E_NULL;
+  if (!a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || (!prefill && !a->workspace) ||
+      (tree && !tree->tree_mask))
+    return SQLLM_E_NULL;
   const int64_t D = a->head_dim;
   if (a->batch < 1 || a->n_q_heads < 1 || a->n_kv_heads < 1 || D < 1 || a->n_slots < 1 || a->block_size < 1 || a->max_blocks < 1 ||
       a->table_stride < 1 || (append && q_len < 1) || (window && *window < 1))
     return SQLLM_E_SHAPE;
   const int64_t rows = append ? (int64_t)a->batch * q_len : a->batch;  // of q, out and the workspace
   const int64_t width = (int64_t)a->n_q_heads * D;
-  if (a->slot_stride < D || a->head_stride < D || a->q_stride < width || a->out_stride < width) return SQLLM_E_SHAPE;
+  if (a->slot_stride < D || a->head_stride < D || a->q_stride < width || a->out_stride < width || (tree && tree->mask_stride < q_len))
+    return SQLLM_E_SHAPE;
   if (a->max_blocks > a->table_stride) return SQLLM_E_SHAPE;
   // what the kernel serves
   if ((D != 64 && D != 128) || a->n_q_heads % a->n_kv_heads || a->n_q_heads / a->n_kv_heads > 8 || a->n_q_heads > 65535 ||
@@ -1615,20 +1627,24 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   const unsigned __int128 q_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->q_stride + (uint64_t)width;
   const unsigned __int128 out_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->out_stride + (uint64_t)width;
   if (extent >= ((unsigned __int128)1 << 62) || q_extent >= ((unsigned __int128)1 << 62) || out_extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
+  const unsigned __int128 mask_extent = tree ? (unsigned __int128)(a->batch - 1) * (uint64_t)tree->mask_stride + (uint64_t)q_len : 0;  // words
+  if (mask_extent >= ((unsigned __int128)1 << 60)) return SQLLM_E_SHAPE;
   if (!__builtin_isfinite(a->scale)) return SQLLM_E_OPTION;
   const int64_t ws_bytes = prefill ? 0
                            : window ? sqllm_attn_window_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size, *window)
                                   : sqllm_attn_decode_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
-  const void* const in[6] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens, q_lens};
-  const int64_t in_bytes[6] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
-                               4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch, 4 * (int64_t)a->batch};
-  for (int i = 0; i < (q_lens ? 6 : 5); ++i)
-    if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || (!prefill && ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i])))
+  const void* const in[7] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens, q_lens, tree ? tree->tree_mask : nullptr};
+  const int64_t in_bytes[7] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
+                               4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch, 4 * (int64_t)a->batch,
+                               4 * (int64_t)mask_extent};
+  for (int i = 0; i < 7; ++i)
+    if (in[i] == nullptr) continue;  // (no q_lens, no tree)
+    else if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || (!prefill && ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i])))
       return SQLLM_E_SHAPE;
   if (!prefill && ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
   if (((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->out)) & 1u) != 0 ||
       (!kv_scales && ((reinterpret_cast<uintptr_t>(a->k_cache) | reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0) ||
-      (!prefill && (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0))
+      (!prefill && (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0) || (tree && (reinterpret_cast<uintptr_t>(tree->tree_mask) & 3u) != 0))
     return SQLLM_E_ALIGN;
   float scale = a->scale;
   if (kv_scales) {
@@ -1664,10 +1680,13 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.q_lens = q_lens;
   c.q_len = q_len;  // (0: one query per sequence; an append call has passed q_len >= 1 above)
   c.window = window ? *window : 0;
+  c.tree_mask = tree ? tree->tree_mask : nullptr;
+  c.mask_stride = tree ? tree->mask_stride : 0;
   // (a window has a table of its own: a null slot there is an error, never the kernels without a window)
   const sqllm::AttnLauncher launch = prefill && window ? sqllm::g_launch_attn_prefill_window[c.fp8 ? 1 : 0]
                                      : prefill         ? (c.fp8 ? sqllm::g_launch_attn_prefill_fp8 : sqllm::g_launch_attn_prefill)
                                      : window          ? sqllm::g_launch_attn_window[c.fp8 ? 1 : 0]
+                                     : tree            ? sqllm::g_launch_attn_tree[c.fp8 ? 1 : 0]
                                                        : sqllm::g_launch_attn[sqllm::attn_kind(c)];
   return static_cast<int>(launch ? launch(c, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
 }
@@ -1686,6 +1705,8 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
 SQLLM_ATTN_LEAD(sqllm_attn_decode_fp8);
 SQLLM_ATTN_LEAD(sqllm_attn_append);
 SQLLM_ATTN_LEAD(sqllm_attn_append_fp8);
+SQLLM_ATTN_LEAD(sqllm_attn_tree);
+SQLLM_ATTN_LEAD(sqllm_attn_tree_fp8);
 #undef SQLLM_ATTN_LEAD
 #undef SQLLM_ATTN_LEAD_AT
 
@@ -1698,9 +1719,9 @@ static sqllm_attn_decode attn_lead(const A* p) {
 }
 extern "C++" template <typename A>
 static int launch_attn_fp8(const A* p, sqllm_stream_t stream, bool bf16, const AttnTokensTail* tokens, const int32_t* window = nullptr,
-                           bool prefill = false) {
+                           bool prefill = false, const AttnTreeTail* tree = nullptr) {
   const float kv_scales[2] = {p->k_scale, p->v_scale};
-  return launch_attn(attn_lead(p), stream, bf16, kv_scales, tokens, window, prefill);
+  return launch_attn(attn_lead(p), stream, bf16, kv_scales, tokens, window, prefill, tree);
 }
 extern "C++" template <typename A>
 static AttnTokensTail attn_tokens(const A* p) { return {p->q_lens, p->q_len}; }
@@ -1743,6 +1764,22 @@ int sqllm_attn_append_f16(const sqllm_attn_append* a, sqllm_stream_t stream) { r
 int sqllm_attn_append_bf16(const sqllm_attn_append* a, sqllm_stream_t stream) { return launch_attn_append(a, stream, true); }
 int sqllm_attn_append_fp8_f16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, false); }
 int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t stream) { return launch_attn_append_fp8(a, stream, true); }
+static int launch_attn_tree(const sqllm_attn_tree* a, sqllm_stream_t stream, bool bf16) {
+  if (!a) return SQLLM_E_NULL;
+  const AttnTokensTail t = attn_tokens(a);
+  const AttnTreeTail m = {a->tree_mask, a->mask_stride};
+  return launch_attn(attn_lead(a), stream, bf16, nullptr, &t, nullptr, false, &m);
+}
+static int launch_attn_tree_fp8(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream, bool bf16) {
+  if (!a) return SQLLM_E_NULL;
+  const AttnTokensTail t = attn_tokens(a);
+  const AttnTreeTail m = {a->tree_mask, a->mask_stride};
+  return launch_attn_fp8(a, stream, bf16, &t, nullptr, false, &m);
+}
+int sqllm_attn_tree_f16(const sqllm_attn_tree* a, sqllm_stream_t stream) { return launch_attn_tree(a, stream, false); }
+int sqllm_attn_tree_bf16(const sqllm_attn_tree* a, sqllm_stream_t stream) { return launch_attn_tree(a, stream, true); }
+int sqllm_attn_tree_fp8_f16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream) { return launch_attn_tree_fp8(a, stream, false); }
+int sqllm_attn_tree_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream) { return launch_attn_tree_fp8(a, stream, true); }
 static int launch_attn_prefill(const sqllm_attn_append* a, sqllm_stream_t stream, bool bf16, const int32_t* window = nullptr) {
   if (!a) return SQLLM_E_NULL;
   const AttnTokensTail t = attn_tokens(a);

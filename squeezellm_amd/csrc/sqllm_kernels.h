@@ -233,6 +233,9 @@ struct AttnCall {
   // a sliding window (sqllm_attn_decode_window_*): the keys [max(0, L - window), L) of a row of length L; n_parts then holds
   // win_parts, the partitions a window can touch, and the workspace is laid out by it
   int window;              // at least 1; 0: the entries without a window
+  // a token tree (sqllm_attn_tree_*, with q_len >= 1): one int32 word per row, bit j = "attends new token j of its sequence"
+  const int* tree_mask = nullptr;  // int32 [batch, mask_stride], device memory; null: the entries without a tree
+  long long mask_stride = 0;       // words between the sequences' rows of it, at least q_len
 };
 enum AttnKind { kAttnDecode, kAttnDecodeFp8, kAttnAppend, kAttnAppendFp8, kAttnKinds };
 inline AttnKind attn_kind(const AttnCall& c) {
@@ -279,6 +282,12 @@ struct AttnAppendArgs {
   int q_len;
   float scale;
 };
+// The tree kernels' argument (sqllm_attn_tree.hip, sqllm_attn_tree_fp8.hip): the append kernels' argument, so that what reads one
+// (append_head, AttnTokens::grid) reads this one too, followed by the mask.
+struct AttnTreeArgs : AttnAppendArgs {
+  const int* tree_mask;  // [batch, mask_stride]: word (b, t), bit j = row (b, t) attends new token j of sequence b
+  long long mask_stride;
+};
 // The window kernels' argument (sqllm_attn_window.hip, sqllm_attn_window_fp8.hip): AttnArgs' fields and the window.  n_parts is
 // win_parts here: the workgroups per (kv head, row) and the partials per (row, query head), indexed RELATIVE to the row's first
 // attended partition.
@@ -305,6 +314,11 @@ inline void attn_token_args(AttnAppendArgs& k, const AttnCall& c) {
   k.q_lens = c.q_lens;
   k.batch = c.batch;
   k.q_len = c.q_len;
+}
+inline void attn_token_args(AttnTreeArgs& k, const AttnCall& c) {
+  attn_token_args(static_cast<AttnAppendArgs&>(k), c);
+  k.tree_mask = c.tree_mask;
+  k.mask_stride = c.mask_stride;
 }
 template <typename ARGS>
 inline ARGS make_attn_args(const AttnCall& c) {
@@ -342,6 +356,11 @@ extern hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int h
 // Null until the file is linked in: hipErrorNotSupported, never the kernels without a window.
 extern AttnLauncher g_launch_attn_window[2];
 extern hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream);
+// The tree entries (sqllm_attn_tree_*): a table of their own beside g_launch_attn, [0] the 16-bit caches (sqllm_attn_tree.hip),
+// [1] the byte caches (sqllm_attn_tree_fp8.hip), and the tree combine both reach through its hook.  Null until the file is
+// linked in: hipErrorNotSupported, never the append kernels (they would compute the chain).
+extern AttnLauncher g_launch_attn_tree[2];
+extern hipError_t (*g_launch_attn_tree_combine)(const AttnTreeArgs& k, int head_dim, bool bf16, hipStream_t stream);
 // The prefill entries (sqllm_attn_prefill_*, sqllm_attn_prefill.hip): a slot of its own, NOT a kind of g_launch_attn -- the call
 // carries q_len up to 65536 and no workspace (AttnCall::workspace is null, n_parts 1).  Null until the file is linked in:
 // hipErrorNotSupported, never the append kernels.

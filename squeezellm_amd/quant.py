@@ -1053,6 +1053,9 @@ _ATTN_KINDS = (
     (_lib.SqllmAttnDecodeFp8, {torch.float16: "sqllm_attn_decode_fp8_f16", torch.bfloat16: "sqllm_attn_decode_fp8_bf16"}),
     (_lib.SqllmAttnAppend, {torch.float16: "sqllm_attn_append_f16", torch.bfloat16: "sqllm_attn_append_bf16"}),
     (_lib.SqllmAttnAppendFp8, {torch.float16: "sqllm_attn_append_fp8_f16", torch.bfloat16: "sqllm_attn_append_fp8_bf16"}),
+    # ... and kind = 4 + (fp8 cache): the new tokens under a tree mask (forward(..., tree_mask=))
+    (_lib.SqllmAttnTree, {torch.float16: "sqllm_attn_tree_f16", torch.bfloat16: "sqllm_attn_tree_bf16"}),
+    (_lib.SqllmAttnTreeFp8, {torch.float16: "sqllm_attn_tree_fp8_f16", torch.bfloat16: "sqllm_attn_tree_fp8_bf16"}),
 )
 # ... and with a sliding window (DecodeAttention(..., window=)): the one-query descriptors, kind = (fp8 cache)
 _ATTN_WINDOW_ENTRIES = (
@@ -1088,6 +1091,78 @@ def append_as_decode_rows(block_table: torch.Tensor, seq_lens: torch.Tensor, q_l
     lens = torch.where(over, torch.full_like(lens, nan_len), lens)
     table = block_table[:, None, :].expand(B, T, block_table.shape[1]).reshape(B * T, block_table.shape[1])
     return table, lens.reshape(-1).to(seq_lens.dtype)
+
+
+def tree_masks(parents, q_lens=None):
+    """(mask, depth), both int32 [batch, T] on the device of `parents`, for DecodeAttention(..., q_len=T, tree_mask=mask):
+    `parents` is [batch, T] (a tensor, or nested lists) with the index of each node's parent among the sequence's new tokens and
+    -1 for a root; a parent stands in front of its children (parents[b, t] < t: the order every drafter emits), T <= 16.
+    mask[b, t] is the ancestor closure of node t, its own bit included -- bit j set: row (b, t) attends new token j.  depth[b, t]
+    counts the node's ancestors, so that the caller's rotary positions are C_b + depth and its cache slots those of the keys
+    C_b + t (C_b: the context length).  `q_lens` ([batch], or None: T everywhere): nodes t >= q_lens[b] are padding, mask and
+    depth 0; their parent entries are not looked at.  A ValueError for anything else."""
+    par = torch.as_tensor(parents)
+    if par.dim() != 2 or par.dtype not in (torch.int32, torch.int64) or not 1 <= par.shape[1] <= ATTN_APPEND_MAX_Q_LEN:
+        raise ValueError(f"parents must be int32 (or int64) [batch, T] with T in [1, {ATTN_APPEND_MAX_Q_LEN}], got {tuple(par.shape)} {par.dtype}")
+    B, T = par.shape
+    par = par.long()
+    t = torch.arange(T, device=par.device)
+    real = torch.ones((B, T), dtype=torch.bool, device=par.device)
+    if q_lens is not None:
+        n = torch.as_tensor(q_lens, device=par.device).reshape(-1).long()
+        if n.numel() != B:
+            raise ValueError(f"q_lens must hold {B} values, got {n.numel()}")
+        real = t[None, :] < n[:, None]
+    if bool((real & ((par < -1) | (par >= t[None, :]))).any()):
+        raise ValueError("parents[b, t] must be -1 (a root) or the index of an earlier node, below t")
+    mask = torch.zeros((B, T), dtype=torch.int64, device=par.device)
+    depth = torch.zeros((B, T), dtype=torch.int64, device=par.device)
+    for i in range(T):  # (a parent's closure is complete before its children ask for it)
+        at = par[:, i].clamp(min=0)[:, None]
+        root = par[:, i] < 0
+        up = torch.where(root, torch.zeros_like(root, dtype=torch.int64), mask.gather(1, at)[:, 0])
+        mask[:, i] = torch.where(real[:, i], up | (1 << i), torch.zeros_like(up))
+        depth[:, i] = torch.where(real[:, i] & ~root, depth.gather(1, at)[:, 0] + 1, torch.zeros_like(up))
+    return mask.to(torch.int32), depth.to(torch.int32)
+
+
+def tree_as_decode_rows(block_table: torch.Tensor, seq_lens: torch.Tensor, q_len: int, q_lens, tree_mask: torch.Tensor, block_size: int,
+                        n_slots: int):
+    """The one-query call that sqllm_attn_tree (include/sqllm_hip.h) is defined by, through a boolean mask over the keys:
+    (table [batch * q_len, S], lengths [batch * q_len]) for DecodeAttention without q_len at BLOCK SIZE 1 -- row b * q_len + t
+    carries the slots of the keys row (b, t) attends, ascending, and their number.  The +0 rows become length 0; the NaN rows (the
+    contract's, a table entry outside [0, n_slots) below Leff among them) length S + 1.  The torch fallback of
+    DecodeAttention(..., tree_mask=) runs on it: correct, slow, and the kernels' reference."""
+    T, (B, max_blocks) = int(q_len), block_table.shape
+    bs, dev = int(block_size), seq_lens.device
+    seq = seq_lens.reshape(-1).long()
+    n = torch.full_like(seq, T) if q_lens is None else q_lens.reshape(-1).long()
+    ctx = seq - n
+    t = torch.arange(T, device=dev)[None, :]
+    j = torch.arange(16, device=dev)
+    word = tree_mask[:, :T].long() & ((1 << n.clamp(min=0, max=16)) - 1)[:, None]
+    bits = ((word[:, :, None] >> j) & 1).bool()  # [B, T, 16]
+    leff = ctx[:, None] + (bits * (j + 1)).amax(dim=2)
+    cap = max_blocks * bs
+    seq_nan = (n > T) | ((n > 0) & (seq < n))
+    zero = (n <= 0)[:, None] | (t >= n[:, None]) | (leff == 0)
+    live = ~seq_nan[:, None] & ~zero & (leff <= cap)
+    S = max(int(torch.where(live, leff, torch.zeros_like(leff)).max().item()), 1)
+    p = torch.arange(S, device=dev)
+    node = p[None, :] - ctx[:, None]  # [B, S]: the key as a node of its sequence
+    is_node = (node >= 0) & (node < 16)
+    attend = (p[None, None, :] < ctx[:, None, None]) | (is_node[:, None, :] & bits.gather(2, node.clamp(0, 15)[:, None, :].expand(B, T, S)))
+    below = p[None, None, :] < leff[:, :, None]
+    attend = attend & below & live[:, :, None]
+    slot = block_table.long()[:, (p // bs).clamp(max=max_blocks - 1)] * bs + (p % bs)[None, :]  # [B, S]
+    bad = (below & live[:, :, None] & ((slot < 0) | (slot >= int(n_slots)))[:, None, :]).any(dim=2)
+    order = torch.argsort((~attend).to(torch.int8), dim=2, stable=True)  # the attended keys first, ascending
+    count = attend.sum(dim=2)
+    table = slot[:, None, :].expand(B, T, S).gather(2, order)
+    table = torch.where(p[None, None, :] < count[:, :, None], table, torch.zeros_like(table))
+    lens = torch.where(live & ~bad, count, torch.full_like(count, S + 1))
+    lens = torch.where(zero & ~seq_nan[:, None], torch.zeros_like(lens), lens)
+    return table.reshape(B * T, S), lens.reshape(-1).to(seq_lens.dtype)
 
 
 def static_cache_blocks(batch: int, n_kv_heads: int, device=None) -> torch.Tensor:
@@ -1243,7 +1318,27 @@ class DecodeAttention(nn.Module):
     looked at: the caller may free or reuse those blocks, and ring_block_table is the table of a rolling buffer.  The torch
     fallback applies the same window.  With `q_len=` a windowed module ALWAYS takes the expansion (append_as_decode_rows) on
     the windowed one-query kernels -- row (b, t) attends [max(0, L(b,t) - W), L(b,t)) -- and `append_route` is ignored: the
-    append kernels have no window."""
+    append kernels have no window.
+
+    forward(..., q_len=T, q_lens=None, tree_mask=None).  The new tokens form a TREE of draft tokens (Medusa, EAGLE, SpecInfer:
+    several continuations share a prefix) and are verified in one read of K and V (sqllm_attn_tree_f16 / _bf16 / _fp8_f16 /
+    _fp8_bf16; include/sqllm_hip.h, sqllm_attn_tree; `last_route` "attn_tree").  `tree_mask`: int32 [batch, T] on q's device
+    (used without a copy where its rows are at least T apart, so a captured graph follows it; int64 is converted), word (b, t)
+    bit j: row (b, t) attends new token j of sequence b, the key at C_b + j with C_b = seq_lens[b] - n_b the context.  Every row
+    attends the context and the nodes of its word, nothing else; any bit pattern is legal, bits at and above n_b are ignored;
+    tree_masks builds the ancestor masks and the depths from parent indices.  With the chain's words (2 << t) - 1 the rows hold
+    exactly the bits of the call without `tree_mask`.  A row without any attended key is +0; a negative context
+    (seq_lens[b] < n_b) makes the sequence's rows NaN; the other corner rows are the append call's, with
+    Leff = C_b + 1 + (highest set bit) for the length.  A NaN at a node a row does not attend leaves that row's bits alone.
+    `tree_mask` requires q_len with T <= 16, and a module without `window=`: anything else is a ValueError.  `append_route` does
+    not apply (there is no one-query expansion of a tree); shapes the kernels do not serve, CPU tensors and other dtypes compute
+    the same function in torch with a boolean mask over the keys (tree_as_decode_rows), in fp32 with one rounding.  Speed,
+    graph-replayed on an MI355X (tools/attn_tree_bench.py, DESIGN.md 4.4, profiles/attn_tree_bench.txt; fp16, 32/32 and 32/8
+    heads of 128, 1 / 4 sequences, 16-bit and fp8 caches, 128 / 1024 / 4096 context keys, a wide and a deep tree of 8 and 16
+    nodes, 96 points): 19.8 - 224 us per call; 1.03x - 1.19x of the append call on a chain of the same T and context (the floor:
+    the same bytes), ABOVE its run-to-run spread on all 96 points, most at 4 sequences of 16 nodes behind 128 keys; against one
+    append call per root-to-leaf path 1.12x - 8.5x faster on all 96 (1.12x - 1.78x for the deep tree's two paths, 2.2x - 8.5x
+    for the wide tree's 6 and 12); against the torch fallback 25x - 100x.  bf16 and head_dim 64 were not measured."""
 
     GRAPH_WS_MAX_BYTES = QuantLinearLUTFused.GRAPH_WS_MAX_BYTES
     append_route = "auto"  # forward(..., q_len=): "auto" routes by measurement, "kernel" / "emulate" force one way (same bits)
@@ -1266,7 +1361,7 @@ class DecodeAttention(nn.Module):
 
     @property
     def last_route(self):
-        """"attn_decode", "attn_append", "attn_window" or "fallback": the way the most recent forward went (None before the first)."""
+        """"attn_decode", "attn_append", "attn_tree", "attn_window" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def _check_cache(self, q: torch.Tensor, k_cache, v_cache) -> None:
@@ -1341,7 +1436,7 @@ class DecodeAttention(nn.Module):
             bt = bt.contiguous()
         return bt, _int32_vector(seq_lens), (None if q_lens is None else _int32_vector(q_lens))
 
-    def _launch(self, kind: int, q2, k_cache, v_cache, bt, sl, ql, T, out, bs, k_scale, v_scale) -> torch.Tensor:
+    def _launch(self, kind: int, q2, k_cache, v_cache, bt, sl, ql, T, out, bs, k_scale, v_scale, tm=None) -> torch.Tensor:
         """Kind `kind` of _ATTN_KINDS on the current stream: the workspace, the kind's descriptor of this (device, stream), the
         entry.  bt has one row per sequence.  -> out, or a new [rows, W]."""
         D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
@@ -1376,13 +1471,15 @@ class DecodeAttention(nn.Module):
         a.scale, a.workspace = self.scale, ws.data_ptr()
         if kind & 1:
             a.k_scale, a.v_scale = k_scale, v_scale
-        if kind & 2:
+        if T is not None:
             a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
+        if tm is not None:
+            a.tree_mask, a.mask_stride = tm.data_ptr(), (tm.stride(0) if batch > 1 else T)
         quant_cuda._launch(quant_cuda._fn(entries[q2.dtype]), dev, (ref,) if window is None else (ref, window))
         return o
 
     def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
-                out=None, block_size=None, k_scale=None, v_scale=None, q_len=None, q_lens=None) -> torch.Tensor:
+                out=None, block_size=None, k_scale=None, v_scale=None, q_len=None, q_lens=None, tree_mask=None) -> torch.Tensor:
         D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
         W = HQ * D
         T = None  # one query per sequence; forward(..., q_len=T, q_lens=None): T new tokens per sequence (sqllm_attn_append_*)
@@ -1394,16 +1491,36 @@ class DecodeAttention(nn.Module):
                 raise ValueError(f"q_len must be positive, got {q_len}")
         q2, rows, bs, fp8, k_scale, v_scale = self._check_operands(q, k_cache, v_cache, block_table, seq_lens, out, block_size,
                                                                    k_scale, v_scale, T, q_lens)
+        if tree_mask is not None:
+            if T is None or T > ATTN_APPEND_MAX_Q_LEN:
+                raise ValueError(f"tree_mask needs q_len, at most {ATTN_APPEND_MAX_Q_LEN} rows per sequence, got {q_len}")
+            if self.window is not None:
+                raise ValueError("tree_mask with a sliding window is not defined")
+            if (not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype not in (torch.int32, torch.int64) or tree_mask.device != q.device
+                    or tree_mask.shape != (rows // T, T)):
+                raise ValueError(f"tree_mask must be int32 (or int64) [{rows // T}, {T}] on {q.device}")
         kernel = (q.dtype in _ATTN_DTYPES and q.is_cuda and D in (64, 128) and HQ // H <= 8 and rows <= 64
                   and (T is None or T <= ATTN_APPEND_MAX_Q_LEN))
         if not kernel:
             self.__dict__["_last_route"] = "fallback"
-            table, lens = (block_table, seq_lens) if T is None else append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
-            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale, self.window)
+            if tree_mask is not None:  # (block size 1: the table rows are the attended slots themselves)
+                table, lens = tree_as_decode_rows(block_table, seq_lens, T, q_lens, tree_mask, bs, k_cache.shape[0])
+                o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, 1, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
+            else:
+                table, lens = (block_table, seq_lens) if T is None else append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
+                o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale, self.window)
             if out is not None:
                 out.copy_(o)
                 return out
             return o.reshape(*q.shape[:-1], W)
+        if tree_mask is not None:  # (no one-query expansion of a tree: `append_route` does not apply)
+            bt, sl, ql = self._int32_operands(block_table, seq_lens, q_lens)
+            tm = tree_mask if tree_mask.dtype == torch.int32 else tree_mask.to(torch.int32)
+            if tm.stride(1) != 1 or (tm.shape[0] > 1 and tm.stride(0) < T):
+                tm = tm.contiguous()
+            self.__dict__["_last_route"] = "attn_tree"
+            o = self._launch(4 + fp8, q2, k_cache, v_cache, bt, sl, ql, T, out, bs, k_scale, v_scale, tm)
+            return o if out is not None else o.reshape(*q.shape[:-1], W)
         if T is not None:
             if self.append_route not in ("auto", "kernel", "emulate"):
                 raise ValueError(f"append_route must be 'auto', 'kernel' or 'emulate', got {self.append_route!r}")
