@@ -727,8 +727,8 @@ int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t st
  * plus: a NULL tree_mask among the NULLs (SQLLM_E_NULL); mask_stride < q_len among the strides (SQLLM_E_SHAPE); out or the
  * workspace overlapping the mask among the overlaps (SQLLM_E_SHAPE); a mask not aligned to 4 bytes among the alignments
  * (SQLLM_E_ALIGN).  A library without the tree kernels answers hipErrorNotSupported, never with the append kernels.
- * Not covered: more than 16 nodes per sequence or 64 rows, a sliding window together with a tree, tree masks on the prefill
- * entries, accepting a path and compacting the cache afterwards (the caller's).
+ * Not covered: more than 16 nodes per sequence or 64 rows (sqllm_attn_tree64_*, below, serves up to 64 nodes and any number of
+ * rows), a sliding window together with a tree, accepting a path and compacting the cache afterwards (the caller's).
  * ------------------------------------------------------------------------------------------- */
 typedef struct sqllm_attn_tree {
   const void* q;            /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride q_stride elements */
@@ -770,6 +770,56 @@ typedef struct sqllm_attn_tree_fp8 {
 /* the suffix names the type of q and out */
 int sqllm_attn_tree_fp8_f16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
 int sqllm_attn_tree_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Tree verification up to 64 nodes on the matrix cores, the keys split across workgroups: the trees EAGLE-2 (about 60 nodes) and
+ * Medusa (64) draft by default.  The semantics are sqllm_attn_tree's with 64-bit masks; the descriptors are sqllm_attn_tree and
+ * sqllm_attn_tree_fp8, UNCHANGED -- tree_mask then points at int32 PAIRS and mask_stride counts int32 words.
+ *
+ *   - Nodes, context and keys as sqllm_attn_tree: n_b = q_lens ? q_lens[b] : q_len nodes, C_b = seq_lens[b] - n_b, node j is the key
+ *     at C_b + j.  q_len is 1 to 64.
+ *   - Mask.  One 64-bit word per row, stored as two int32 words, the LOW word first: row (b, t)'s are
+ *     tree_mask[b * mask_stride + 2 t] and [... + 2 t + 1].  DEVICE memory, used without a copy; a captured graph follows it updated
+ *     in place.  m(b,t) is the word with the bits at and above n_b ignored.  Row (b, t) attends [0, C_b) and node j for every set
+ *     bit j; any bit pattern is legal.  Leff(b,t) = C_b + 1 + (index of the highest set bit), or C_b for m == 0.
+ *   - Values.  The formulas of sqllm_attn_decode over the attended keys.  Scores and PV run on the matrix instructions as in the
+ *     prefill entries: fp32 online softmax, the fp32 weights as three 16-bit planes, one rounding at the end.  The results lie
+ *     inside the tree entries' fp32-class bound; they are NOT the bits of the tree, append or prefill entries.
+ *   - Key split.  Partitions are the fixed ABSOLUTE key ranges [P i, P i + P), P = SQLLM_ATTN_TREE64_PARTITION.  Every (query tile of
+ *     64 (token, head of a kv group) rows, kv head, sequence, partition) workgroup whose partition begins below its tile's largest
+ *     Leff writes per-row fp32 partials (max, sum, acc[head_dim]) to the workspace; a second kernel node combines the partials of
+ *     the partitions below the row's own Leff in ascending order and rounds once.  A partition in which a row attends nothing --
+ *     with 64 nodes across a partition edge a row may attend only nodes of the second partition, or none of it -- contributes
+ *     nothing to that row (its maximum is -inf and it is skipped; no inf - inf anywhere).  A row's bits depend on its own operands,
+ *     its mask word, its lengths and the shape fields only: not on the batch, the other sequences or timing.
+ *   - Launch.  ONE kernel node when max_blocks * block_size <= SQLLM_ATTN_TREE64_PARTITION (the partial kernel finishes the rows
+ *     itself), TWO otherwise.  The workspace is sqllm_attn_tree64_workspace_bytes(), CONTENTS IRRELEVANT.  Geometry comes from host
+ *     fields only; no allocation; capturable.
+ *   - Corner rows, those of sqllm_attn_tree, judged in the same order.  n_b > q_len: NaN.  n_b <= 0: +0.  seq_lens[b] < n_b (a
+ *     negative context): NaN.  t >= n_b: padding, +0.  A row with no attended key: +0.  Leff > max_blocks * block_size: NaN.  A table
+ *     entry outside [0, n_slots) that covers a key below Leff(b,t) makes that row NaN.  Nothing outside the cache is read.
+ *   - Isolation is WEAKER than the vector tree entries', as for the prefill entries.  A non-finite k at a key a row does not attend
+ *     never reaches that row: score and weight are selected by bit, before the exponent.  A non-finite v at a key that is staged
+ *     for the row's query tile -- any key below the tile's largest Leff -- may make that column NaN for every row of the tile (0 x
+ *     NaN in the matrix instruction).  Finite values never leak.  Unaddressed slots never matter.
+ *
+ * Served: head_dim 64 or 128; a head ratio of 1 to 8; q_len 1 to 64; batch 1 to 65535; fp16 / bf16 over a 16-bit or an e4m3fn cache
+ * (k_scale and v_scale as in the fp8 prefill entries: k_scale folded into the score scale on the host, v_scale once per output
+ * element before the rounding).  A window together with a tree is not defined.  Rejections are the tree entries', with their codes
+ * and in their order, with these differences: q_len > 64 or batch > 65535 among the shapes that are not served (no limit on
+ * batch * q_len); mask_stride < 2 * q_len among the strides; the mask's extent is (batch - 1) * mask_stride + 2 * q_len words; a
+ * workspace of 2^62 bytes or more is SQLLM_E_SHAPE, in front of the overlaps; the mask must be aligned to 8 bytes (SQLLM_E_ALIGN).
+ * A library without these kernels answers hipErrorNotSupported, never with the 16-node tree kernels or the prefill kernels.
+ * Not covered: more than 64 nodes per sequence, a sliding window together with a tree, accepting a path and compacting the cache
+ * afterwards (the caller's).
+ * ------------------------------------------------------------------------------------------- */
+#define SQLLM_ATTN_TREE64_PARTITION 256 /* keys per partition of the wide-tree entries: a multiple of 64 */
+int64_t sqllm_attn_tree64_workspace_bytes(int32_t batch, int32_t q_len, int32_t n_q_heads, int32_t head_dim, int32_t max_blocks, int32_t block_size);
+int sqllm_attn_tree64_f16(const sqllm_attn_tree* a, sqllm_stream_t stream);
+int sqllm_attn_tree64_bf16(const sqllm_attn_tree* a, sqllm_stream_t stream);
+/* the suffix names the type of q and out */
+int sqllm_attn_tree64_fp8_f16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
+int sqllm_attn_tree64_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sliding-window decode attention: ONE new query per sequence, attending the LAST `window` keys the cache holds for that

@@ -80,6 +80,7 @@ class SqllmKvCache(ctypes.Structure):
 
 
 ATTN_PARTITION = 256  # SQLLM_ATTN_PARTITION: keys per partition of the decode attention
+ATTN_TREE64_PARTITION = 256  # SQLLM_ATTN_TREE64_PARTITION: keys per partition of the wide-tree attention
 
 
 class SqllmAttnDecode(ctypes.Structure):
@@ -250,6 +251,11 @@ SIGNATURES = {
     "sqllm_attn_tree_bf16": [POINTER(SqllmAttnTree), P],
     "sqllm_attn_tree_fp8_f16": [POINTER(SqllmAttnTreeFp8), P],
     "sqllm_attn_tree_fp8_bf16": [POINTER(SqllmAttnTreeFp8), P],
+    "sqllm_attn_tree64_workspace_bytes": [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32],
+    "sqllm_attn_tree64_f16": [POINTER(SqllmAttnTree), P],
+    "sqllm_attn_tree64_bf16": [POINTER(SqllmAttnTree), P],
+    "sqllm_attn_tree64_fp8_f16": [POINTER(SqllmAttnTreeFp8), P],
+    "sqllm_attn_tree64_fp8_bf16": [POINTER(SqllmAttnTreeFp8), P],
     "sqllm_attn_prefill_f16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_prefill_bf16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_prefill_fp8_f16": [POINTER(SqllmAttnAppendFp8), P],
@@ -313,7 +319,7 @@ def load() -> ctypes.CDLL:
                       ctypes.c_int64 if name in ("sqllm_linear_workspace_bytes", "sqllm_workspace_bytes", "sqllm_nuq_workspace_bytes",
                                                "sqllm_select_workspace_bytes", "sqllm_gated_workspace_bytes",
                                                "sqllm_qkv_rope_workspace_bytes", "sqllm_attn_decode_workspace_bytes",
-                                               "sqllm_attn_window_workspace_bytes") else c_int)
+                                               "sqllm_attn_window_workspace_bytes", "sqllm_attn_tree64_workspace_bytes") else c_int)
     if lib.sqllm_abi_version() != 1:
         raise RuntimeError(f"libsqllm_hip.so ABI {lib.sqllm_abi_version()} != 1 expected by this package")
     _lib = lib
@@ -377,6 +383,11 @@ def attn_decode_workspace_bytes(batch: int, n_q_heads: int, head_dim: int, max_b
 def attn_window_workspace_bytes(batch: int, n_q_heads: int, head_dim: int, max_blocks: int, block_size: int, window: int) -> int:
     """Bytes of device memory (contents irrelevant) one sliding-window decode attention of these shapes needs (no GPU needed)."""
     return int(load().sqllm_attn_window_workspace_bytes(batch, n_q_heads, head_dim, max_blocks, block_size, window))
+
+
+def attn_tree64_workspace_bytes(batch: int, q_len: int, n_q_heads: int, head_dim: int, max_blocks: int, block_size: int) -> int:
+    """Bytes of device memory (contents irrelevant) one wide-tree attention (sqllm_attn_tree64_*) of these shapes needs (no GPU needed)."""
+    return int(load().sqllm_attn_tree64_workspace_bytes(batch, q_len, n_q_heads, head_dim, max_blocks, block_size))
 
 
 def workspace_bytes(bits: int, K: int, N: int, batch: int, nnz: int = 0, topX: int = 0, n_ops: int = 1) -> int:

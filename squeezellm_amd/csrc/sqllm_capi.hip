@@ -22,6 +22,8 @@ hipError_t (*g_launch_attn_combine)(const AttnArgs& k, int head_dim, bool bf16, 
 hipError_t (*g_launch_attn_append_combine)(const AttnAppendArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_append.hip
 AttnLauncher g_launch_attn_tree[2] = {};  // [0] set by sqllm_attn_tree.hip, [1] by sqllm_attn_tree_fp8.hip
 hipError_t (*g_launch_attn_tree_combine)(const AttnTreeArgs& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_tree.hip
+AttnLauncher g_launch_attn_tree64[2] = {};  // [0] set by sqllm_attn_tree64.hip, [1] by sqllm_attn_tree64_fp8.hip
+hipError_t (*g_launch_attn_tree64_combine)(const AttnTree64Args& k, int head_dim, bool bf16, hipStream_t stream) = nullptr;  // set by sqllm_attn_tree64.hip
 AttnLauncher g_launch_attn_window[2] = {};  // [0] set by sqllm_attn_window.hip, [1] by sqllm_attn_window_fp8.hip
 hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim, bool bf16, int batch, hipStream_t stream) = nullptr;  // set by sqllm_attn_window.hip
 AttnLauncher g_launch_attn_prefill = nullptr;  // set by sqllm_attn_prefill.hip
@@ -1573,7 +1575,23 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
   return (int64_t)batch * n_q_heads * attn_window_parts(max_blocks, block_size, window) * (head_dim + 2) * 4;
 }
 
-// The twenty-four attention entries.  The six descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
+// The wide-tree entries (sqllm_attn_tree64_*): partitions of SQLLM_ATTN_TREE64_PARTITION keys, a size of their own.
+static int64_t attn_tree64_parts(int32_t max_blocks, int32_t block_size) {
+  return (attn_capacity(max_blocks, block_size) + SQLLM_ATTN_TREE64_PARTITION - 1) / SQLLM_ATTN_TREE64_PARTITION;
+}
+static_assert(SQLLM_ATTN_TREE64_PARTITION == sqllm::kTree64Partition && SQLLM_ATTN_TREE64_PARTITION % 64 == 0, "the header documents the kernel's partition");
+
+int64_t sqllm_attn_tree64_workspace_bytes(int32_t batch, int32_t q_len, int32_t n_q_heads, int32_t head_dim, int32_t max_blocks, int32_t block_size) {
+  if (batch < 1 || q_len < 1 || n_q_heads < 1 || head_dim < 1 || max_blocks < 1 || block_size < 1) return 0;
+  // per (row, query head, partition): acc[head_dim], max, sum -- asked for with one partition too, where nothing is written
+  // (saturates at INT64_MAX, in two steps that cannot wrap: no such workspace exists, and the entries reject the call)
+  const unsigned __int128 partials = (unsigned __int128)((uint64_t)batch * (uint64_t)q_len) * (uint64_t)n_q_heads * (uint64_t)attn_tree64_parts(max_blocks, block_size);
+  if (partials > (unsigned __int128)INT64_MAX) return INT64_MAX;
+  const unsigned __int128 bytes = partials * (((uint64_t)head_dim + 2) * 4);
+  return bytes > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)bytes;
+}
+
+// The twenty-eight attention entries.  The six descriptors begin with the fields of sqllm_attn_decode (`lead`, checked below); what
 // follows them is passed on by each entry:
 //   `kv_scales` (the fp8 entries): {k_scale, v_scale} of the descriptor -- the caches hold 1-byte e4m3fn elements, their strides
 //     and extents count bytes and they need no alignment; the scales are judged last.  NULL: 16-bit caches.
@@ -1589,6 +1607,10 @@ int64_t sqllm_attn_window_workspace_bytes(int32_t batch, int32_t n_q_heads, int3
 //   `tree` (sqllm_attn_tree_*, with `tokens`): the append call with one mask word per row; NULL among the NULLs, its stride among
 //     the strides, the mask among the tensors out and the workspace must not overlap, its alignment among the alignments; the call
 //     goes to g_launch_attn_tree, a table of its own.
+//   `tree` with `wide` (sqllm_attn_tree64_*): the tree call with one int32 PAIR per row -- mask_stride at least 2 q_len words, the
+//     mask's extent and its 8-byte alignment follow --, the prefill entries' two limits with q_len up to 64 instead of the append
+//     entries', partitions of SQLLM_ATTN_TREE64_PARTITION keys and the workspace of sqllm_attn_tree64_workspace_bytes(); the call
+//     goes to g_launch_attn_tree64, a table of its own.
 struct AttnTokensTail {
   const int32_t* q_lens;
   int32_t q_len;
@@ -1596,6 +1618,7 @@ struct AttnTokensTail {
 struct AttnTreeTail {
   const int32_t* tree_mask;
   int64_t mask_stride;
+  bool wide;  // one int32 pair per row (sqllm_attn_tree64_*)
 };
 static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, bool bf16, const float* kv_scales, const AttnTokensTail* tokens,
                        const int32_t* window = nullptr, bool prefill = false, const AttnTreeTail* tree = nullptr) {
@@ -1604,6 +1627,8 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   const int32_t q_len = append ? tokens->q_len : 0;
   const int32_t* const q_lens = append ? tokens->q_lens : nullptr;
   const int celem = kv_scales ? 1 : 2;  // bytes per cache element
+  const bool wide = tree && tree->wide;
+  const int64_t row_words = wide ? 2 * (int64_t)q_len : q_len;  // of the mask, per sequence
   if (!a->q || !a->out || !a->k_cache || !a->v_cache || !a->block_table || !a->seq_lens || (!prefill && !a->workspace) ||
       (tree && !tree->tree_mask))
     return SQLLM_E_NULL;
@@ -1613,12 +1638,12 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
     return SQLLM_E_SHAPE;
   const int64_t rows = append ? (int64_t)a->batch * q_len : a->batch;  // of q, out and the workspace
   const int64_t width = (int64_t)a->n_q_heads * D;
-  if (a->slot_stride < D || a->head_stride < D || a->q_stride < width || a->out_stride < width || (tree && tree->mask_stride < q_len))
+  if (a->slot_stride < D || a->head_stride < D || a->q_stride < width || a->out_stride < width || (tree && tree->mask_stride < row_words))
     return SQLLM_E_SHAPE;
   if (a->max_blocks > a->table_stride) return SQLLM_E_SHAPE;
   // what the kernel serves
   if ((D != 64 && D != 128) || a->n_q_heads % a->n_kv_heads || a->n_q_heads / a->n_kv_heads > 8 || a->n_q_heads > 65535 ||
-      (prefill ? (q_len > 65536 || a->batch > 65535) : (rows > 64 || (append && q_len > 16))))
+      (prefill ? (q_len > 65536 || a->batch > 65535) : wide ? (q_len > 64 || a->batch > 65535) : (rows > 64 || (append && q_len > 16))))
     return SQLLM_E_SHAPE;
   // as for sqllm_kv_cache: 32 x 32 -> 64-bit products, and extents that do not wrap
   const int64_t H = a->n_kv_heads;
@@ -1627,16 +1652,18 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   const unsigned __int128 q_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->q_stride + (uint64_t)width;
   const unsigned __int128 out_extent = (unsigned __int128)(rows - 1) * (uint64_t)a->out_stride + (uint64_t)width;
   if (extent >= ((unsigned __int128)1 << 62) || q_extent >= ((unsigned __int128)1 << 62) || out_extent >= ((unsigned __int128)1 << 62)) return SQLLM_E_SHAPE;
-  const unsigned __int128 mask_extent = tree ? (unsigned __int128)(a->batch - 1) * (uint64_t)tree->mask_stride + (uint64_t)q_len : 0;  // words
+  const unsigned __int128 mask_extent = tree ? (unsigned __int128)(a->batch - 1) * (uint64_t)tree->mask_stride + (uint64_t)row_words : 0;  // words
   if (mask_extent >= ((unsigned __int128)1 << 60)) return SQLLM_E_SHAPE;
   if (!__builtin_isfinite(a->scale)) return SQLLM_E_OPTION;
   const int64_t ws_bytes = prefill ? 0
+                           : wide ? sqllm_attn_tree64_workspace_bytes(a->batch, q_len, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size)
                            : window ? sqllm_attn_window_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size, *window)
                                   : sqllm_attn_decode_workspace_bytes((int32_t)rows, a->n_q_heads, a->head_dim, a->max_blocks, a->block_size);
   const void* const in[7] = {a->q, a->k_cache, a->v_cache, a->block_table, a->seq_lens, q_lens, tree ? tree->tree_mask : nullptr};
   const int64_t in_bytes[7] = {2 * (int64_t)q_extent, celem * (int64_t)extent, celem * (int64_t)extent,
                                4 * ((int64_t)(a->batch - 1) * a->table_stride + a->max_blocks), 4 * (int64_t)a->batch, 4 * (int64_t)a->batch,
                                4 * (int64_t)mask_extent};
+  if (ws_bytes >= (1ll << 62)) return SQLLM_E_SHAPE;  // (the wide tree's, with the prefill entries' limits: no such workspace)
   for (int i = 0; i < 7; ++i)
     if (in[i] == nullptr) continue;  // (no q_lens, no tree)
     else if (ranges_overlap(a->out, 2 * (int64_t)out_extent, in[i], in_bytes[i]) || (!prefill && ranges_overlap(a->workspace, ws_bytes, in[i], in_bytes[i])))
@@ -1644,7 +1671,7 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   if (!prefill && ranges_overlap(a->out, 2 * (int64_t)out_extent, a->workspace, ws_bytes)) return SQLLM_E_SHAPE;
   if (((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->out)) & 1u) != 0 ||
       (!kv_scales && ((reinterpret_cast<uintptr_t>(a->k_cache) | reinterpret_cast<uintptr_t>(a->v_cache)) & 1u) != 0) ||
-      (!prefill && (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0) || (tree && (reinterpret_cast<uintptr_t>(tree->tree_mask) & 3u) != 0))
+      (!prefill && (reinterpret_cast<uintptr_t>(a->workspace) & 3u) != 0) || (tree && (reinterpret_cast<uintptr_t>(tree->tree_mask) & (wide ? 7u : 3u)) != 0))
     return SQLLM_E_ALIGN;
   float scale = a->scale;
   if (kv_scales) {
@@ -1668,7 +1695,7 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   c.block_size = a->block_size;
   c.table_stride = a->table_stride;
   c.capacity = (int)attn_capacity(a->max_blocks, a->block_size);
-  c.n_parts = prefill ? 1 : (int)(window ? attn_window_parts(a->max_blocks, a->block_size, *window) : attn_parts(a->max_blocks, a->block_size));
+  c.n_parts = prefill ? 1 : wide ? (int)attn_tree64_parts(a->max_blocks, a->block_size) : (int)(window ? attn_window_parts(a->max_blocks, a->block_size, *window) : attn_parts(a->max_blocks, a->block_size));
   c.slot_stride = a->slot_stride;
   c.head_stride = a->head_stride;
   c.q_stride = a->q_stride;
@@ -1686,6 +1713,7 @@ static int launch_attn(const sqllm_attn_decode& lead, sqllm_stream_t stream, boo
   const sqllm::AttnLauncher launch = prefill && window ? sqllm::g_launch_attn_prefill_window[c.fp8 ? 1 : 0]
                                      : prefill         ? (c.fp8 ? sqllm::g_launch_attn_prefill_fp8 : sqllm::g_launch_attn_prefill)
                                      : window          ? sqllm::g_launch_attn_window[c.fp8 ? 1 : 0]
+                                     : wide            ? sqllm::g_launch_attn_tree64[c.fp8 ? 1 : 0]
                                      : tree            ? sqllm::g_launch_attn_tree[c.fp8 ? 1 : 0]
                                                        : sqllm::g_launch_attn[sqllm::attn_kind(c)];
   return static_cast<int>(launch ? launch(c, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
@@ -1767,19 +1795,36 @@ int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t st
 static int launch_attn_tree(const sqllm_attn_tree* a, sqllm_stream_t stream, bool bf16) {
   if (!a) return SQLLM_E_NULL;
   const AttnTokensTail t = attn_tokens(a);
-  const AttnTreeTail m = {a->tree_mask, a->mask_stride};
+  const AttnTreeTail m = {a->tree_mask, a->mask_stride, false};
   return launch_attn(attn_lead(a), stream, bf16, nullptr, &t, nullptr, false, &m);
 }
 static int launch_attn_tree_fp8(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream, bool bf16) {
   if (!a) return SQLLM_E_NULL;
   const AttnTokensTail t = attn_tokens(a);
-  const AttnTreeTail m = {a->tree_mask, a->mask_stride};
+  const AttnTreeTail m = {a->tree_mask, a->mask_stride, false};
   return launch_attn_fp8(a, stream, bf16, &t, nullptr, false, &m);
 }
 int sqllm_attn_tree_f16(const sqllm_attn_tree* a, sqllm_stream_t stream) { return launch_attn_tree(a, stream, false); }
 int sqllm_attn_tree_bf16(const sqllm_attn_tree* a, sqllm_stream_t stream) { return launch_attn_tree(a, stream, true); }
 int sqllm_attn_tree_fp8_f16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream) { return launch_attn_tree_fp8(a, stream, false); }
 int sqllm_attn_tree_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream) { return launch_attn_tree_fp8(a, stream, true); }
+// (the wide tree: the tree entries' descriptors, the mask read as int32 pairs)
+static int launch_attn_tree64(const sqllm_attn_tree* a, sqllm_stream_t stream, bool bf16) {
+  if (!a) return SQLLM_E_NULL;
+  const AttnTokensTail t = attn_tokens(a);
+  const AttnTreeTail m = {a->tree_mask, a->mask_stride, true};
+  return launch_attn(attn_lead(a), stream, bf16, nullptr, &t, nullptr, false, &m);
+}
+static int launch_attn_tree64_fp8(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream, bool bf16) {
+  if (!a) return SQLLM_E_NULL;
+  const AttnTokensTail t = attn_tokens(a);
+  const AttnTreeTail m = {a->tree_mask, a->mask_stride, true};
+  return launch_attn_fp8(a, stream, bf16, &t, nullptr, false, &m);
+}
+int sqllm_attn_tree64_f16(const sqllm_attn_tree* a, sqllm_stream_t stream) { return launch_attn_tree64(a, stream, false); }
+int sqllm_attn_tree64_bf16(const sqllm_attn_tree* a, sqllm_stream_t stream) { return launch_attn_tree64(a, stream, true); }
+int sqllm_attn_tree64_fp8_f16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream) { return launch_attn_tree64_fp8(a, stream, false); }
+int sqllm_attn_tree64_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream) { return launch_attn_tree64_fp8(a, stream, true); }
 static int launch_attn_prefill(const sqllm_attn_append* a, sqllm_stream_t stream, bool bf16, const int32_t* window = nullptr) {
   if (!a) return SQLLM_E_NULL;
   const AttnTokensTail t = attn_tokens(a);

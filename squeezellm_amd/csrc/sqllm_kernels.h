@@ -361,6 +361,15 @@ extern hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int h
 // linked in: hipErrorNotSupported, never the append kernels (they would compute the chain).
 extern AttnLauncher g_launch_attn_tree[2];
 extern hipError_t (*g_launch_attn_tree_combine)(const AttnTreeArgs& k, int head_dim, bool bf16, hipStream_t stream);
+// The wide-tree entries (sqllm_attn_tree64_*, up to 64 nodes per sequence on the matrix cores, the keys split): a table of their own,
+// [0] the 16-bit caches (sqllm_attn_tree64.hip), [1] the byte caches (sqllm_attn_tree64_fp8.hip), and the combine both reach through
+// its hook (the argument: sqllm_attn_tree64.h).  The call carries q_len 1 to 64, tree_mask as int32 PAIRS (mask_stride >= 2 q_len),
+// a workspace and n_parts = ceil(capacity / kTree64Partition).  Null until the file is linked in: hipErrorNotSupported, never the
+// 16-node tree kernels and never the prefill kernels.
+constexpr int kTree64Partition = 256;  // keys per partition (SQLLM_ATTN_TREE64_PARTITION of include/sqllm_hip.h): whole key tiles of 64
+struct AttnTree64Args;
+extern AttnLauncher g_launch_attn_tree64[2];
+extern hipError_t (*g_launch_attn_tree64_combine)(const AttnTree64Args& k, int head_dim, bool bf16, hipStream_t stream);
 // The prefill entries (sqllm_attn_prefill_*, sqllm_attn_prefill.hip): a slot of its own, NOT a kind of g_launch_attn -- the call
 // carries q_len up to 65536 and no workspace (AttnCall::workspace is null, n_parts 1).  Null until the file is linked in:
 // hipErrorNotSupported, never the append kernels.

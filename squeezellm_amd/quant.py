@@ -1093,17 +1093,23 @@ def append_as_decode_rows(block_table: torch.Tensor, seq_lens: torch.Tensor, q_l
     return table, lens.reshape(-1).to(seq_lens.dtype)
 
 
-def tree_masks(parents, q_lens=None):
+ATTN_TREE64_PARTITION = _lib.ATTN_TREE64_PARTITION  # keys per partition of the wide-tree kernels (SQLLM_ATTN_TREE64_PARTITION)
+ATTN_TREE64_MAX_Q_LEN = 64  # nodes per sequence the wide-tree kernels serve: the bits of a row's word
+
+
+def tree_masks(parents, q_lens=None, wide=False):
     """(mask, depth), both int32 [batch, T] on the device of `parents`, for DecodeAttention(..., q_len=T, tree_mask=mask):
     `parents` is [batch, T] (a tensor, or nested lists) with the index of each node's parent among the sequence's new tokens and
     -1 for a root; a parent stands in front of its children (parents[b, t] < t: the order every drafter emits), T <= 16.
     mask[b, t] is the ancestor closure of node t, its own bit included -- bit j set: row (b, t) attends new token j.  depth[b, t]
     counts the node's ancestors, so that the caller's rotary positions are C_b + depth and its cache slots those of the keys
     C_b + t (C_b: the context length).  `q_lens` ([batch], or None: T everywhere): nodes t >= q_lens[b] are padding, mask and
-    depth 0; their parent entries are not looked at.  A ValueError for anything else."""
+    depth 0; their parent entries are not looked at.  A ValueError for anything else.  `wide=True`: T <= 64, and the mask is int64
+    (bit 63 is the sign), for PrefillAttention(..., q_len=T, tree_mask=mask); the depth stays int32."""
     par = torch.as_tensor(parents)
-    if par.dim() != 2 or par.dtype not in (torch.int32, torch.int64) or not 1 <= par.shape[1] <= ATTN_APPEND_MAX_Q_LEN:
-        raise ValueError(f"parents must be int32 (or int64) [batch, T] with T in [1, {ATTN_APPEND_MAX_Q_LEN}], got {tuple(par.shape)} {par.dtype}")
+    most = ATTN_TREE64_MAX_Q_LEN if wide else ATTN_APPEND_MAX_Q_LEN
+    if par.dim() != 2 or par.dtype not in (torch.int32, torch.int64) or not 1 <= par.shape[1] <= most:
+        raise ValueError(f"parents must be int32 (or int64) [batch, T] with T in [1, {most}], got {tuple(par.shape)} {par.dtype}")
     B, T = par.shape
     par = par.long()
     t = torch.arange(T, device=par.device)
@@ -1121,27 +1127,28 @@ def tree_masks(parents, q_lens=None):
         at = par[:, i].clamp(min=0)[:, None]
         root = par[:, i] < 0
         up = torch.where(root, torch.zeros_like(root, dtype=torch.int64), mask.gather(1, at)[:, 0])
-        mask[:, i] = torch.where(real[:, i], up | (1 << i), torch.zeros_like(up))
+        mask[:, i] = torch.where(real[:, i], up | (1 << i if i < 63 else -1 << 63), torch.zeros_like(up))
         depth[:, i] = torch.where(real[:, i] & ~root, depth.gather(1, at)[:, 0] + 1, torch.zeros_like(up))
-    return mask.to(torch.int32), depth.to(torch.int32)
+    return (mask if wide else mask.to(torch.int32)), depth.to(torch.int32)
 
 
 def tree_as_decode_rows(block_table: torch.Tensor, seq_lens: torch.Tensor, q_len: int, q_lens, tree_mask: torch.Tensor, block_size: int,
-                        n_slots: int):
+                        n_slots: int, nodes: int = 16):
     """The one-query call that sqllm_attn_tree (include/sqllm_hip.h) is defined by, through a boolean mask over the keys:
     (table [batch * q_len, S], lengths [batch * q_len]) for DecodeAttention without q_len at BLOCK SIZE 1 -- row b * q_len + t
     carries the slots of the keys row (b, t) attends, ascending, and their number.  The +0 rows become length 0; the NaN rows (the
     contract's, a table entry outside [0, n_slots) below Leff among them) length S + 1.  The torch fallback of
-    DecodeAttention(..., tree_mask=) runs on it: correct, slow, and the kernels' reference."""
+    DecodeAttention(..., tree_mask=) runs on it: correct, slow, and the kernels' reference.  `nodes`: the bits of a mask word that
+    count, 16 (sqllm_attn_tree) or up to 64 (sqllm_attn_tree64, int64 words: PrefillAttention(..., tree_mask=))."""
+    N = int(nodes)
     T, (B, max_blocks) = int(q_len), block_table.shape
     bs, dev = int(block_size), seq_lens.device
     seq = seq_lens.reshape(-1).long()
     n = torch.full_like(seq, T) if q_lens is None else q_lens.reshape(-1).long()
     ctx = seq - n
     t = torch.arange(T, device=dev)[None, :]
-    j = torch.arange(16, device=dev)
-    word = tree_mask[:, :T].long() & ((1 << n.clamp(min=0, max=16)) - 1)[:, None]
-    bits = ((word[:, :, None] >> j) & 1).bool()  # [B, T, 16]
+    j = torch.arange(N, device=dev)
+    bits = ((tree_mask[:, :T].long()[:, :, None] >> j) & 1).bool() & (j[None, None, :] < n[:, None, None])  # [B, T, N]: the real nodes' bits
     leff = ctx[:, None] + (bits * (j + 1)).amax(dim=2)
     cap = max_blocks * bs
     seq_nan = (n > T) | ((n > 0) & (seq < n))
@@ -1150,8 +1157,8 @@ def tree_as_decode_rows(block_table: torch.Tensor, seq_lens: torch.Tensor, q_len
     S = max(int(torch.where(live, leff, torch.zeros_like(leff)).max().item()), 1)
     p = torch.arange(S, device=dev)
     node = p[None, :] - ctx[:, None]  # [B, S]: the key as a node of its sequence
-    is_node = (node >= 0) & (node < 16)
-    attend = (p[None, None, :] < ctx[:, None, None]) | (is_node[:, None, :] & bits.gather(2, node.clamp(0, 15)[:, None, :].expand(B, T, S)))
+    is_node = (node >= 0) & (node < N)
+    attend = (p[None, None, :] < ctx[:, None, None]) | (is_node[:, None, :] & bits.gather(2, node.clamp(0, N - 1)[:, None, :].expand(B, T, S)))
     below = p[None, None, :] < leff[:, :, None]
     attend = attend & below & live[:, :, None]
     slot = block_table.long()[:, (p // bs).clamp(max=max_blocks - 1)] * bs + (p % bs)[None, :]  # [B, S]
@@ -1567,6 +1574,9 @@ _ATTN_PREFILL_ENTRIES = {torch.float16: "sqllm_attn_prefill_f16", torch.bfloat16
 _ATTN_PREFILL_FP8_ENTRIES = {torch.float16: "sqllm_attn_prefill_fp8_f16", torch.bfloat16: "sqllm_attn_prefill_fp8_bf16"}
 _ATTN_PREFILL_WINDOW_ENTRIES = {torch.float16: "sqllm_attn_prefill_window_f16", torch.bfloat16: "sqllm_attn_prefill_window_bf16"}
 _ATTN_PREFILL_WINDOW_FP8_ENTRIES = {torch.float16: "sqllm_attn_prefill_window_fp8_f16", torch.bfloat16: "sqllm_attn_prefill_window_fp8_bf16"}
+# ... and under a tree mask of up to 64 nodes (PrefillAttention.forward(..., tree_mask=)): [fp8 cache]
+_ATTN_TREE64_ENTRIES = ({torch.float16: "sqllm_attn_tree64_f16", torch.bfloat16: "sqllm_attn_tree64_bf16"},
+                        {torch.float16: "sqllm_attn_tree64_fp8_f16", torch.bfloat16: "sqllm_attn_tree64_fp8_bf16"})
 
 
 class PrefillAttention(DecodeAttention):
@@ -1621,18 +1631,30 @@ class PrefillAttention(DecodeAttention):
     earliest window are never read and the slots of those keys never loaded: the caller may free or reuse them, and
     ring_block_table(..., q_len=T) is the table of a rolling buffer for chunks of T tokens.  A table entry outside the cache
     makes NaN exactly the tokens that attend its keys.  Everything else takes the torch fallback with the same window.  Speed:
-    tools/attn_prefill_bench.py --window, DESIGN.md 4.4."""
+    tools/attn_prefill_bench.py --window, DESIGN.md 4.4.
+
+    forward(..., q_len=T, tree_mask=mask): the new tokens are a TREE of up to 64 draft tokens (EAGLE-2, Medusa) verified in one
+    call (sqllm_attn_tree64_f16 / _bf16 / _fp8_f16 / _fp8_bf16; include/sqllm_hip.h, tree verification up to 64 nodes;
+    `last_route` "attn_tree64").  `tree_mask`: int64 [batch, T] on q's device, bit j of word (b, t) = row (b, t) attends node j of
+    its sequence (tree_masks(parents, wide=True) builds it), read by the kernel as int32 pairs without a copy; a captured graph
+    follows it updated in place.  The semantics are DecodeAttention(..., tree_mask=)'s -- the context [0, seq_lens[b] - n_b) and
+    the nodes by bit, the same corner rows -- on the matrix cores, the keys split across workgroups in partitions of
+    ATTN_TREE64_PARTITION keys and combined in ascending order: two kernel nodes, one when the table holds one partition, a
+    workspace per (device, stream) as DecodeAttention keeps it.  Values inside the fp32-class bound, not DecodeAttention's bits;
+    isolation as above (a non-finite v at a key staged for a query tile may reach the tile's other rows).  T > 64, a module with
+    `window=` or a mask that is not int64 [batch, T] on q's device is a ValueError; CPU tensors and unserved shapes compute the same
+    function in torch (tree_as_decode_rows(..., nodes=64)).  Speed: tools/attn_tree_bench.py --nodes, DESIGN.md 4.4."""
 
     def __init__(self, n_heads: int, n_kv_heads: int, head_dim: int, scale=None, block_size=None, window=None):
         super().__init__(n_heads, n_kv_heads, head_dim, scale=scale, block_size=block_size, window=window)
 
     @property
     def last_route(self):
-        """"attn_prefill", "attn_prefill_window" or "fallback": the way the most recent forward went (None before the first)."""
+        """"attn_prefill", "attn_prefill_window", "attn_tree64" or "fallback": the way the most recent forward went (None before the first)."""
         return self.__dict__.get("_last_route")
 
     def forward(self, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor,
-                q_len: int, q_lens=None, out=None, block_size=None, k_scale=None, v_scale=None) -> torch.Tensor:
+                q_len: int, q_lens=None, out=None, block_size=None, k_scale=None, v_scale=None, tree_mask=None) -> torch.Tensor:
         D, H, HQ = self.head_dim, self.n_kv_heads, self.n_heads
         W = HQ * D
         T = int(q_len)
@@ -1641,24 +1663,62 @@ class PrefillAttention(DecodeAttention):
         q2, rows, bs, fp8, k_scale, v_scale = self._check_operands(q, k_cache, v_cache, block_table, seq_lens, out, block_size,
                                                                    k_scale, v_scale, T, q_lens)
         batch = rows // T
+        tree = tree_mask is not None
+        if tree:
+            if T > ATTN_TREE64_MAX_Q_LEN:
+                raise ValueError(f"tree_mask serves at most {ATTN_TREE64_MAX_Q_LEN} rows per sequence, got {q_len}")
+            if self.window is not None:
+                raise ValueError("tree_mask with a sliding window is not defined")
+            if (not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64 or tree_mask.device != q.device
+                    or tree_mask.shape != (batch, T)):
+                raise ValueError(f"tree_mask must be int64 [{batch}, {T}] on {q.device}")
         kernel = (q.dtype in _ATTN_DTYPES and q.is_cuda and D in (64, 128) and HQ // H <= 8 and HQ <= 65535
                   and T <= ATTN_PREFILL_MAX_Q_LEN and batch <= ATTN_PREFILL_MAX_BATCH)
         if not kernel:
             self.__dict__["_last_route"] = "fallback"
-            table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
-            o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale, self.window)
+            if tree:  # (block size 1: the table rows are the attended slots themselves)
+                table, lens = tree_as_decode_rows(block_table, seq_lens, T, q_lens, tree_mask, bs, k_cache.shape[0], nodes=ATTN_TREE64_MAX_Q_LEN)
+                o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, 1, HQ, H, D, self.scale, q.dtype, k_scale, v_scale)
+            else:
+                table, lens = append_as_decode_rows(block_table, seq_lens, T, q_lens, bs)
+                o = _torch_attn_decode(q2, k_cache, v_cache, table, lens, bs, HQ, H, D, self.scale, q.dtype, k_scale, v_scale, self.window)
             if out is not None:
                 out.copy_(o)
                 return out
             return o.reshape(*q.shape[:-1], W)
         bt, sl, ql = self._int32_operands(block_table, seq_lens, q_lens)
         window = self.window
-        self.__dict__["_last_route"] = "attn_prefill" if window is None else "attn_prefill_window"
+        self.__dict__["_last_route"] = "attn_tree64" if tree else "attn_prefill" if window is None else "attn_prefill_window"
         max_blocks = bt.shape[1]
         dev = q2.get_device()
         o = out if out is not None else torch.empty((rows, W), dtype=q2.dtype, device=q2.device)
         stream = quant_cuda._raw_stream(dev)
         descs = self.__dict__.setdefault("_desc", {})
+        if tree:  # (kernels of their own: a missing one is an error, never the kernels without a mask)
+            tm = tree_mask if tree_mask.stride(1) == 1 and (batch == 1 or tree_mask.stride(0) >= T) else tree_mask.contiguous()
+            ws = _workspace_of(self, _lib.attn_tree64_workspace_bytes, (batch, T, HQ, D, max_blocks, bs), q2.device)
+            key = ("tree64_fp8" if fp8 else "tree64", dev, stream)
+            hit = descs.get(key)
+            if hit is None:
+                a = _lib.SqllmAttnTreeFp8() if fp8 else _lib.SqllmAttnTree()
+                hit = descs[key] = (a, ctypes.byref(a))
+            a, ref = hit
+            a.q, a.out, a.k_cache, a.v_cache = q2.data_ptr(), o.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr()
+            a.block_table, a.seq_lens = bt.data_ptr(), sl.data_ptr()
+            a.batch, a.n_q_heads, a.n_kv_heads, a.head_dim = batch, HQ, H, D
+            a.n_slots, a.block_size, a.max_blocks = k_cache.shape[0], bs, max_blocks
+            a.table_stride = bt.stride(0) if batch > 1 else max_blocks
+            a.slot_stride = k_cache.stride(0)  # (an fp8 cache has 1-byte elements: its strides count bytes)
+            a.head_stride = k_cache.stride(1) if H > 1 else D
+            a.q_stride = q2.stride(0) if rows > 1 else W
+            a.out_stride = o.stride(0) if rows > 1 else W
+            a.scale, a.workspace = self.scale, ws.data_ptr()
+            a.q_lens, a.q_len = (None if ql is None else ql.data_ptr()), T
+            a.tree_mask, a.mask_stride = tm.data_ptr(), 2 * (tm.stride(0) if batch > 1 else T)  # (int64 words as int32 pairs, no copy)
+            if fp8:
+                a.k_scale, a.v_scale = k_scale, v_scale
+            quant_cuda._launch(quant_cuda._fn(_ATTN_TREE64_ENTRIES[fp8][q2.dtype]), dev, (ref,))
+            return o if out is not None else o.reshape(*q.shape[:-1], W)
         key = ("prefill_fp8" if fp8 else "prefill", dev, stream)  # (a descriptor per cache type: the structs differ)
         hit = descs.get(key)
         if hit is None:
