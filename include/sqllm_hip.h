@@ -728,7 +728,8 @@ int sqllm_attn_append_fp8_bf16(const sqllm_attn_append_fp8* a, sqllm_stream_t st
  * workspace overlapping the mask among the overlaps (SQLLM_E_SHAPE); a mask not aligned to 4 bytes among the alignments
  * (SQLLM_E_ALIGN).  A library without the tree kernels answers hipErrorNotSupported, never with the append kernels.
  * Not covered: more than 16 nodes per sequence or 64 rows (sqllm_attn_tree64_*, below, serves up to 64 nodes and any number of
- * rows), a sliding window together with a tree, accepting a path and compacting the cache afterwards (the caller's).
+ * rows), a sliding window together with a tree.  Accepting a path and compacting the cache afterwards: sqllm_tree_accept and
+ * sqllm_kv_compact, below.
  * ------------------------------------------------------------------------------------------- */
 typedef struct sqllm_attn_tree {
   const void* q;            /* 16-bit [batch * q_len, n_q_heads * head_dim], row stride q_stride elements */
@@ -810,8 +811,8 @@ int sqllm_attn_tree_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream
  * batch * q_len); mask_stride < 2 * q_len among the strides; the mask's extent is (batch - 1) * mask_stride + 2 * q_len words; a
  * workspace of 2^62 bytes or more is SQLLM_E_SHAPE, in front of the overlaps; the mask must be aligned to 8 bytes (SQLLM_E_ALIGN).
  * A library without these kernels answers hipErrorNotSupported, never with the 16-node tree kernels or the prefill kernels.
- * Not covered: more than 64 nodes per sequence, a sliding window together with a tree, accepting a path and compacting the cache
- * afterwards (the caller's).
+ * Not covered: more than 64 nodes per sequence, a sliding window together with a tree.  Accepting a path and compacting the cache
+ * afterwards: sqllm_tree_accept and sqllm_kv_compact, below.
  * ------------------------------------------------------------------------------------------- */
 #define SQLLM_ATTN_TREE64_PARTITION 256 /* keys per partition of the wide-tree entries: a multiple of 64 */
 int64_t sqllm_attn_tree64_workspace_bytes(int32_t batch, int32_t q_len, int32_t n_q_heads, int32_t head_dim, int32_t max_blocks, int32_t block_size);
@@ -820,6 +821,109 @@ int sqllm_attn_tree64_bf16(const sqllm_attn_tree* a, sqllm_stream_t stream);
 /* the suffix names the type of q and out */
 int sqllm_attn_tree64_fp8_f16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
 int sqllm_attn_tree64_fp8_bf16(const sqllm_attn_tree_fp8* a, sqllm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Accepting a verified draft tree and compacting the KV cache: the two steps behind sqllm_attn_tree_* / sqllm_attn_tree64_* that
+ * close a speculative-decoding step, ONE kernel node each per step, for all layers at once.  Every operand that changes from step to
+ * step is DEVICE memory, used without a copy: a captured graph follows it updated in place.  No workspace, no allocation.
+ *
+ * sqllm_tree_accept -- greedy acceptance.  n_b = q_lens ? q_lens[b] : q_len nodes per sequence, as in the tree entries.
+ *   - parents: int32 [batch, stride]; -1 (any negative value) is a root, otherwise parents[b, t] < t.
+ *   - tree_mask: the 64-bit ancestor closures as int32 PAIRS, the low word first, as sqllm_attn_tree64_* reads them: row (b, t)'s
+ *     are tree_mask[b * mask_stride + 2 t] and [... + 2 t + 1]; mask_stride counts int32 words.  Trees of 16 nodes pass this wide
+ *     form too.  w(t) is row t's word with its own bit ORed in and the bits at and above n_b cleared.
+ *   - draft_tokens: int32 [batch, stride], the token id of node t.  target_tokens: int32 [batch, stride], the target model's greedy
+ *     token AFTER node t, from row (b, t) of the verification; the argmax over the logits stays the caller's.
+ *   - match(t) holds when parents[b, t] < 0 (roots are tokens the caller already sampled), or when 0 <= parents[b, t] < t and
+ *     draft_tokens[b, t] == target_tokens[b, parents[b, t]].  Any other parent value gives no match.  M is the word of match bits.
+ *   - Node t < n_b is ACCEPTED iff w(t) & ~M == 0.  The BEST node is the accepted node with the most bits in w; ties go to the
+ *     lowest t.  The kernel applies these formulas; it does not check that the words are a closure.
+ *   - accept_len[b] = popcount(w(best)).  path[b, j] = the index of the j-th set bit of w(best) for j < accept_len[b], and -1 for
+ *     accept_len[b] <= j < q_len; path[b, q_len .. stride) is not written.  next_token[b] = target_tokens[b, best].
+ *   - seq_lens_in / seq_lens_out: both NULL or both given; seq_lens_out[b] = seq_lens_in[b] - n_b + accept_len[b].  The two may be
+ *     the SAME array: each sequence reads its own word before it writes it.
+ *   - n_b <= 0, n_b > q_len, or no accepted node: accept_len = 0, path all -1, next_token = -1; seq_lens_out = seq_lens_in -
+ *     max(n_b, 0) where n_b <= q_len, and seq_lens_in unchanged where n_b > q_len.
+ *   - A sequence's results depend on its own operands only.
+ * Served: q_len 1 to 64, batch 1 to 65535.  Rejected before the device is touched, in this order:
+ *   a NULL descriptor, parents, tree_mask, draft_tokens, target_tokens, accept_len, path or next_token; one of seq_lens_in and
+ *   seq_lens_out without the other                                                          SQLLM_E_NULL
+ *   q_len outside [1, 64], batch outside [1, 65535]                                         SQLLM_E_SHAPE
+ *   stride < q_len, mask_stride < 2 * q_len, an extent of 2^60 words or more                SQLLM_E_SHAPE
+ *   an output overlapping an input or another output (seq_lens_out == seq_lens_in excepted)  SQLLM_E_SHAPE
+ *   tree_mask not aligned to 8 bytes, any other array not to 4                               SQLLM_E_ALIGN
+ *
+ * sqllm_kv_compact -- move the accepted rows.  Node t was stored as key C_b + t (C_b = seq_lens[b] - n_b) but rotated as position
+ * C_b + depth: the accepted path belongs in the keys C_b .. C_b + a - 1, a = accept_len[b], in the k and the v cache of every layer.
+ *   - caches: a HOST array of n_caches device pointers, 1 to SQLLM_KV_COMPACT_MAX_CACHES; all caches share one geometry, that of
+ *     sqllm_kv_cache (elem_bytes = 2) or sqllm_kv_cache_fp8 (elem_bytes = 1): element (slot, kv head h, d) at slot * slot_stride +
+ *     h * head_stride + d, the strides in elements of elem_bytes.  The entry passes the pointers to the kernel BY VALUE: the array
+ *     may go away behind the call, and a captured graph node owns them.
+ *   - block_table, seq_lens, q_lens (or NULL), q_len as in the tree call that was verified: seq_lens are the lengths THAT call had,
+ *     the nodes included -- NOT sqllm_tree_accept's seq_lens_out.  path: int32 [batch, path_stride] and accept_len: int32 [batch],
+ *     as sqllm_tree_accept left them.  A key p lies in slot block_table[b, p / block_size] * block_size + p % block_size; offsets
+ *     are 64-bit, under the stride rules of sqllm_kv_cache.
+ *   - A sequence is left untouched when n_b <= 0, n_b > q_len, C_b < 0, a <= 0 or a > n_b.  Otherwise, for j in [0, a) with
+ *     s = path[b, j]: the row at key C_b + j receives the OLD bytes of the row at key C_b + s, in every cache, for every kv head, all
+ *     head_dim elements -- AS IF every source of the sequence were read before any destination is written: the chain
+ *     path = [1, 2, 3, ...] is legal.
+ *   - Element j is skipped, nothing read and nothing written, when s == j, when s is outside [j, n_b), when either key is at or
+ *     beyond max_blocks * block_size, or when either table entry puts the slot outside [0, n_slots).
+ *   - Bytes are copied as bytes: NaN patterns survive.  No byte outside the destination rows changes; nothing outside the caches'
+ *     extents is read.  The result does not depend on the other sequences.  seq_lens is not written.
+ *   - The access width is the largest of 16, 4, 2 and 1 bytes that divides every cache pointer and both strides in bytes: fp8
+ *     caches keep their any-alignment contract (head_stride = head_dim + 3 included), 16-bit caches their 2-byte contract.
+ * Served: head_dim 64 or 128; q_len 1 to 64; batch 1 to 65535; n_kv_heads 1 to 65535.  Rejected before the device is touched, in
+ * this order:
+ *   a NULL descriptor, caches, cache pointer, block_table, seq_lens, path or accept_len       SQLLM_E_NULL
+ *   n_caches outside [1, SQLLM_KV_COMPACT_MAX_CACHES]; a count < 1 (n_kv_heads, n_slots, block_size, max_blocks, table_stride);
+ *   a head_dim, q_len, batch or n_kv_heads that is not served; max_blocks > table_stride      SQLLM_E_SHAPE
+ *   an elem_bytes that is neither 1 nor 2                                                    SQLLM_E_OPTION
+ *   slot_stride or head_stride < head_dim, path_stride < q_len; a stride at or above 2^32 that is ever multiplied, or an extent
+ *   at or above 2^62 elements, as for sqllm_kv_cache                                         SQLLM_E_SHAPE
+ *   a cache extent that overlaps another cache's or block_table, seq_lens, q_lens, path or accept_len
+ *                                                                                           SQLLM_E_SHAPE
+ *   a 16-bit cache not aligned to 2 bytes, an index array not to 4                           SQLLM_E_ALIGN
+ * A library without these kernels answers hipErrorNotSupported.
+ * Not covered: stochastic (rejection-sampling) acceptance, the argmax over the logits, gathering hidden states of the accepted
+ * path, more than 64 nodes, freeing the blocks behind the new length.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sqllm_tree_accept_desc {
+  const int32_t* parents;       /* int32 [batch, stride], DEVICE memory: -1 a root, otherwise an earlier node */
+  const int32_t* tree_mask;     /* int32 pairs [batch, mask_stride], DEVICE memory: tree_masks(wide=True), as sqllm_attn_tree64_* */
+  const int32_t* draft_tokens;  /* int32 [batch, stride], DEVICE memory: the token of node t */
+  const int32_t* target_tokens; /* int32 [batch, stride], DEVICE memory: the target's greedy token after node t */
+  const int32_t* q_lens;        /* int32 [batch], DEVICE memory, or NULL: q_len nodes in every sequence */
+  const int32_t* seq_lens_in;   /* int32 [batch], DEVICE memory, or NULL (then seq_lens_out is NULL too) */
+  int32_t* accept_len;          /* int32 [batch]; OVERWRITTEN */
+  int32_t* path;                /* int32 [batch, stride]; words [b, 0 .. q_len) OVERWRITTEN */
+  int32_t* next_token;          /* int32 [batch]; OVERWRITTEN */
+  int32_t* seq_lens_out;        /* int32 [batch], or NULL; may be seq_lens_in */
+  int64_t stride;               /* words between the sequences' rows of parents, the tokens and path, >= q_len */
+  int64_t mask_stride;          /* words between the sequences' rows of tree_mask, >= 2 * q_len */
+  int32_t q_len;                /* nodes per sequence, 1 to 64 */
+  int32_t batch;                /* sequences, 1 to 65535 */
+} sqllm_tree_accept_desc;
+int sqllm_tree_accept(const sqllm_tree_accept_desc* a, sqllm_stream_t stream);
+
+#define SQLLM_KV_COMPACT_MAX_CACHES 256 /* cache pointers of one sqllm_kv_compact call: k and v of 128 layers */
+typedef struct sqllm_kv_compact_desc {
+  void* const* caches;          /* HOST array of n_caches device pointers: the k and the v cache of every layer */
+  const int32_t* block_table;   /* int32 [batch, table_stride], DEVICE memory */
+  const int32_t* seq_lens;      /* int32 [batch], DEVICE memory: the lengths of the tree call, its nodes included */
+  const int32_t* q_lens;        /* int32 [batch], DEVICE memory, or NULL */
+  const int32_t* path;          /* int32 [batch, path_stride], DEVICE memory */
+  const int32_t* accept_len;    /* int32 [batch], DEVICE memory */
+  int32_t n_caches;             /* 1 to SQLLM_KV_COMPACT_MAX_CACHES */
+  int32_t elem_bytes;           /* 2: 16-bit caches; 1: e4m3fn caches */
+  int32_t n_kv_heads, head_dim; /* head_dim 64 or 128 */
+  int32_t n_slots, block_size, max_blocks, table_stride;   /* max_blocks <= table_stride */
+  int32_t q_len;                /* nodes per sequence, 1 to 64 */
+  int32_t batch;                /* sequences, 1 to 65535 */
+  int64_t slot_stride, head_stride; /* in elements of elem_bytes, as sqllm_kv_cache / sqllm_kv_cache_fp8 count them */
+  int64_t path_stride;          /* words between the sequences' rows of path, >= q_len */
+} sqllm_kv_compact_desc;
+int sqllm_kv_compact(const sqllm_kv_compact_desc* c, sqllm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sliding-window decode attention: ONE new query per sequence, attending the LAST `window` keys the cache holds for that

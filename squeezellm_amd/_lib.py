@@ -134,6 +134,28 @@ class SqllmAttnTreeFp8(ctypes.Structure):
     _fields_ = SqllmAttnAppendFp8._fields_ + [("tree_mask", c_void_p), ("mask_stride", ctypes.c_int64)]
 
 
+class SqllmTreeAccept(ctypes.Structure):
+    """struct sqllm_tree_accept_desc (include/sqllm_hip.h): greedy acceptance of a verified draft tree -- every pointer device
+    memory, the mask as int32 pairs (tree_masks(wide=True))."""
+
+    _fields_ = [("parents", c_void_p), ("tree_mask", c_void_p), ("draft_tokens", c_void_p), ("target_tokens", c_void_p), ("q_lens", c_void_p),
+                ("seq_lens_in", c_void_p), ("accept_len", c_void_p), ("path", c_void_p), ("next_token", c_void_p), ("seq_lens_out", c_void_p),
+                ("stride", ctypes.c_int64), ("mask_stride", ctypes.c_int64), ("q_len", c_int32), ("batch", c_int32)]
+
+
+KV_COMPACT_MAX_CACHES = 256  # SQLLM_KV_COMPACT_MAX_CACHES: cache pointers of one sqllm_kv_compact call
+
+
+class SqllmKvCompact(ctypes.Structure):
+    """struct sqllm_kv_compact_desc (include/sqllm_hip.h): move the accepted path's rows to the front of the tree's keys in
+    `n_caches` caches of one geometry -- `caches` a HOST array of device pointers, the strides in elements of elem_bytes."""
+
+    _fields_ = [("caches", ctypes.POINTER(c_void_p)), ("block_table", c_void_p), ("seq_lens", c_void_p), ("q_lens", c_void_p), ("path", c_void_p),
+                ("accept_len", c_void_p), ("n_caches", c_int32), ("elem_bytes", c_int32), ("n_kv_heads", c_int32), ("head_dim", c_int32),
+                ("n_slots", c_int32), ("block_size", c_int32), ("max_blocks", c_int32), ("table_stride", c_int32), ("q_len", c_int32),
+                ("batch", c_int32), ("slot_stride", ctypes.c_int64), ("head_stride", ctypes.c_int64), ("path_stride", ctypes.c_int64)]
+
+
 class SqllmQkvRope(ctypes.Structure):
     """struct sqllm_qkv_rope (include/sqllm_hip.h): q, k and v share op.vec (fp16 / bf16); their op.mul stay NULL."""
 
@@ -256,6 +278,8 @@ SIGNATURES = {
     "sqllm_attn_tree64_bf16": [POINTER(SqllmAttnTree), P],
     "sqllm_attn_tree64_fp8_f16": [POINTER(SqllmAttnTreeFp8), P],
     "sqllm_attn_tree64_fp8_bf16": [POINTER(SqllmAttnTreeFp8), P],
+    "sqllm_tree_accept": [POINTER(SqllmTreeAccept), P],
+    "sqllm_kv_compact": [POINTER(SqllmKvCompact), P],
     "sqllm_attn_prefill_f16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_prefill_bf16": [POINTER(SqllmAttnAppend), P],
     "sqllm_attn_prefill_fp8_f16": [POINTER(SqllmAttnAppendFp8), P],

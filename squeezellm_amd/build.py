@@ -28,6 +28,7 @@ SOURCES = ["sqllm_kernels.hip", "sqllm_mfma_split.hip", "sqllm_mfma_wide.hip", "
            "sqllm_attn_tree.hip", "sqllm_attn_tree_fp8.hip",
            "sqllm_attn_prefill.hip", "sqllm_attn_prefill_fp8.hip", "sqllm_attn_prefill_window.hip", "sqllm_attn_prefill_window_fp8.hip",
            "sqllm_attn_tree64.hip", "sqllm_attn_tree64_fp8.hip",
+           "sqllm_tree_accept.hip", "sqllm_kv_compact.hip",
            "sqllm_capi.hip"]
 # measured-and-not-adopted kernels (round 3: the streaming batch-1 kernel, the column-pair-table kernel; round 4: the
 # dependency-gated persistent pass) and the host code that routes to them: csrc/experimental/, part of the MEASUREMENT
@@ -36,7 +37,7 @@ EXPERIMENTAL = os.path.join(CSRC, "experimental")
 EXPERIMENT_SOURCES = ["experimental/sqllm_ablation.hip", "experimental/sqllm_stream.hip", "experimental/sqllm_pair.hip",
                       "experimental/sqllm_pass.hip", "experimental/sqllm_experimental.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("sqllm_kernels.h", "sqllm_decode.h", "sqllm_roles.h", "sqllm_fused.h", "sqllm_ranges.h", "sqllm_split_common.h", "sqllm_host.h", "sqllm_probe.h",
-                                              "sqllm_pair_finish.h", "sqllm_rope_finish.h", "sqllm_norm_front.h", "sqllm_cache_finish.h", "sqllm_cache_fp8_finish.h", "sqllm_attn.h", "sqllm_attn_prefill.h", "sqllm_attn_tree64.h")] + [os.path.join(INCLUDE, "sqllm_hip.h")]
+                                              "sqllm_pair_finish.h", "sqllm_rope_finish.h", "sqllm_norm_front.h", "sqllm_cache_finish.h", "sqllm_cache_fp8_finish.h", "sqllm_attn.h", "sqllm_attn_prefill.h", "sqllm_attn_tree64.h", "sqllm_tree_accept.h")] + [os.path.join(INCLUDE, "sqllm_hip.h")]
 EXPERIMENT_HEADERS = [os.path.join(EXPERIMENTAL, h) for h in ("sqllm_pass.h", "sqllm_pass_api.h", "sqllm_stream_api.h")]
 ARCH = "gfx950"
 # -amdgpu-kernarg-preload-count: the kernels' leading explicit arguments (the vec pointer) arrive in SGPRs instead of

@@ -9,11 +9,13 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 
 #include "sqllm_hip.h"
 #include "sqllm_host.h"
 #include "sqllm_kernels.h"
+#include "sqllm_tree_accept.h"
 
 namespace sqllm {
 FrontLauncher g_launch_front[kFrontKinds] = {};  // each slot set by its kernel file (sqllm_linear_gated.hip ... sqllm_linear_qkv_norm_cache_fp8.hip)
@@ -29,6 +31,8 @@ hipError_t (*g_launch_attn_window_combine)(const AttnWindowArgs& k, int head_dim
 AttnLauncher g_launch_attn_prefill = nullptr;  // set by sqllm_attn_prefill.hip
 AttnLauncher g_launch_attn_prefill_fp8 = nullptr;  // set by sqllm_attn_prefill_fp8.hip
 AttnLauncher g_launch_attn_prefill_window[2] = {};  // [0] set by sqllm_attn_prefill_window.hip, [1] by sqllm_attn_prefill_window_fp8.hip
+hipError_t (*g_launch_tree_accept)(const TreeAcceptArgs& k, hipStream_t stream) = nullptr;  // set by sqllm_tree_accept.hip
+hipError_t (*g_launch_kv_compact)(const KvCompactArgs& k, int row_bytes, int vec, int n_kv_heads, int n_caches, int batch, hipStream_t stream) = nullptr;  // set by sqllm_kv_compact.hip
 }
 
 namespace sqllm_host {
@@ -1846,6 +1850,115 @@ int sqllm_attn_prefill_window_fp8_f16(const sqllm_attn_append_fp8* a, int32_t wi
 }
 int sqllm_attn_prefill_window_fp8_bf16(const sqllm_attn_append_fp8* a, int32_t window, sqllm_stream_t stream) {
   return launch_attn_prefill_fp8(a, stream, true, &window);
+}
+
+// sqllm_tree_accept: the descriptor is judged here -- NULLs, shapes, strides, overlaps, alignments -- and handed to the kernel file
+// through its hook
+int sqllm_tree_accept(const sqllm_tree_accept_desc* a, sqllm_stream_t stream) {
+  if (!a || !a->parents || !a->tree_mask || !a->draft_tokens || !a->target_tokens || !a->accept_len || !a->path || !a->next_token ||
+      !a->seq_lens_in != !a->seq_lens_out)
+    return SQLLM_E_NULL;
+  if (a->q_len < 1 || a->q_len > 64 || a->batch < 1 || a->batch > 65535) return SQLLM_E_SHAPE;
+  if (a->stride < a->q_len || a->mask_stride < 2 * (int64_t)a->q_len) return SQLLM_E_SHAPE;
+  const unsigned __int128 row_extent = (unsigned __int128)(a->batch - 1) * (uint64_t)a->stride + (uint64_t)a->q_len;  // words
+  const unsigned __int128 mask_extent = (unsigned __int128)(a->batch - 1) * (uint64_t)a->mask_stride + 2 * (uint64_t)a->q_len;
+  if (row_extent >= ((unsigned __int128)1 << 60) || mask_extent >= ((unsigned __int128)1 << 60)) return SQLLM_E_SHAPE;
+  const int64_t rows = 4 * (int64_t)row_extent, vec = 4 * (int64_t)a->batch;
+  const void* const in[6] = {a->parents, a->tree_mask, a->draft_tokens, a->target_tokens, a->q_lens, a->seq_lens_in};
+  const int64_t in_bytes[6] = {rows, 4 * (int64_t)mask_extent, rows, rows, vec, vec};
+  const void* const out[4] = {a->accept_len, a->path, a->next_token, a->seq_lens_out};
+  const int64_t out_bytes[4] = {vec, rows, vec, vec};
+  for (int i = 0; i < 4; ++i) {
+    if (!out[i]) continue;  // (no seq_lens_out)
+    for (int j = 0; j < 6; ++j)
+      if (in[j] && !(i == 3 && j == 5 && out[i] == in[j]) && ranges_overlap(out[i], out_bytes[i], in[j], in_bytes[j])) return SQLLM_E_SHAPE;
+    for (int j = i + 1; j < 4; ++j)
+      if (out[j] && ranges_overlap(out[i], out_bytes[i], out[j], out_bytes[j])) return SQLLM_E_SHAPE;
+  }
+  uintptr_t bits = 0;
+  for (int j = 0; j < 6; ++j) bits |= reinterpret_cast<uintptr_t>(in[j]);
+  for (int i = 0; i < 4; ++i) bits |= reinterpret_cast<uintptr_t>(out[i]);
+  if ((bits & 3u) != 0 || (reinterpret_cast<uintptr_t>(a->tree_mask) & 7u) != 0) return SQLLM_E_ALIGN;
+  sqllm::TreeAcceptArgs k;
+  k.parents = a->parents;
+  k.tree_mask = a->tree_mask;
+  k.draft = a->draft_tokens;
+  k.target = a->target_tokens;
+  k.q_lens = a->q_lens;
+  k.seq_in = a->seq_lens_in;
+  k.accept_len = a->accept_len;
+  k.path = a->path;
+  k.next_token = a->next_token;
+  k.seq_out = a->seq_lens_out;
+  k.stride = a->stride;
+  k.mask_stride = a->mask_stride;
+  k.q_len = a->q_len;
+  k.batch = a->batch;
+  return static_cast<int>(sqllm::g_launch_tree_accept ? sqllm::g_launch_tree_accept(k, static_cast<hipStream_t>(stream)) : hipErrorNotSupported);
+}
+
+// sqllm_kv_compact: as above.  The caches' extents are compared after a sort of their base addresses (256 caches: no n^2 walk on the
+// path of every decoding step); the access width is the largest of 16 / 4 / 2 / 1 bytes that every base and both strides allow.
+static_assert(SQLLM_KV_COMPACT_MAX_CACHES == sqllm::kKvCompactMaxCaches, "the kernel's argument block holds the header's maximum");
+int sqllm_kv_compact(const sqllm_kv_compact_desc* c, sqllm_stream_t stream) {
+  if (!c || !c->caches || !c->block_table || !c->seq_lens || !c->path || !c->accept_len) return SQLLM_E_NULL;
+  if (c->n_caches < 1 || c->n_caches > SQLLM_KV_COMPACT_MAX_CACHES) return SQLLM_E_SHAPE;  // (before the array is walked)
+  for (int i = 0; i < c->n_caches; ++i)
+    if (!c->caches[i]) return SQLLM_E_NULL;
+  const int64_t D = c->head_dim, H = c->n_kv_heads;
+  if (H < 1 || c->n_slots < 1 || c->block_size < 1 || c->max_blocks < 1 || c->table_stride < 1 || (D != 64 && D != 128) || c->q_len < 1 ||
+      c->q_len > 64 || c->batch < 1 || c->batch > 65535 || H > 65535 || c->max_blocks > c->table_stride)
+    return SQLLM_E_SHAPE;
+  if (c->elem_bytes != 1 && c->elem_bytes != 2) return SQLLM_E_OPTION;
+  if (c->slot_stride < D || c->head_stride < D || c->path_stride < c->q_len) return SQLLM_E_SHAPE;
+  if ((c->n_slots > 1 && c->slot_stride >= (1ll << 32)) || (H > 1 && c->head_stride >= (1ll << 32))) return SQLLM_E_SHAPE;
+  const unsigned __int128 extent = (unsigned __int128)(c->n_slots - 1) * (uint64_t)c->slot_stride + (unsigned __int128)(H - 1) * (uint64_t)c->head_stride + (uint64_t)D;
+  const unsigned __int128 path_extent = (unsigned __int128)(c->batch - 1) * (uint64_t)c->path_stride + (uint64_t)c->q_len;
+  if (extent >= ((unsigned __int128)1 << 62) || path_extent >= ((unsigned __int128)1 << 60)) return SQLLM_E_SHAPE;
+  const int64_t bytes = c->elem_bytes * (int64_t)extent;
+  sqllm::KvCompactArgs k;
+  uintptr_t base[SQLLM_KV_COMPACT_MAX_CACHES];
+  uintptr_t low = 0;  // the OR of what the access width must divide
+  for (int i = 0; i < c->n_caches; ++i) {
+    k.caches[i] = static_cast<unsigned char*>(c->caches[i]);
+    base[i] = reinterpret_cast<uintptr_t>(c->caches[i]);
+    low |= base[i] & 15u;
+  }
+  for (int i = c->n_caches; i < SQLLM_KV_COMPACT_MAX_CACHES; ++i) k.caches[i] = nullptr;
+  std::sort(base, base + c->n_caches);
+  for (int i = 0; i + 1 < c->n_caches; ++i)
+    if (base[i + 1] - base[i] < (uintptr_t)bytes) return SQLLM_E_SHAPE;
+  const void* const idx[5] = {c->block_table, c->seq_lens, c->q_lens, c->path, c->accept_len};
+  const int64_t idx_bytes[5] = {4 * ((int64_t)(c->batch - 1) * c->table_stride + c->max_blocks), 4 * (int64_t)c->batch, 4 * (int64_t)c->batch,
+                                4 * (int64_t)path_extent, 4 * (int64_t)c->batch};
+  for (int j = 0; j < 5; ++j) {
+    if (!idx[j]) continue;  // (no q_lens)
+    // the caches that can reach the array: the last one that begins below its end, and by the sort no other begins closer
+    const uintptr_t end = reinterpret_cast<uintptr_t>(idx[j]) + (uintptr_t)idx_bytes[j];
+    const uintptr_t* const above = std::lower_bound(base, base + c->n_caches, end);
+    if (above != base && ranges_overlap(reinterpret_cast<const void*>(above[-1]), bytes, idx[j], idx_bytes[j])) return SQLLM_E_SHAPE;
+  }
+  uintptr_t ibits = 0;
+  for (int j = 0; j < 5; ++j) ibits |= reinterpret_cast<uintptr_t>(idx[j]);
+  if ((c->elem_bytes == 2 && (low & 1u) != 0) || (ibits & 3u) != 0) return SQLLM_E_ALIGN;
+  k.slot_bytes = (uint64_t)c->slot_stride * (uint64_t)c->elem_bytes;
+  k.head_bytes = (uint64_t)c->head_stride * (uint64_t)c->elem_bytes;
+  if (c->n_slots > 1) low |= k.slot_bytes & 15u;
+  if (H > 1) low |= k.head_bytes & 15u;
+  const int vec = (low & 1u) ? 1 : (low & 2u) ? 2 : (low & 12u) ? 4 : 16;
+  k.block_table = c->block_table;
+  k.seq_lens = c->seq_lens;
+  k.q_lens = c->q_lens;
+  k.path = c->path;
+  k.accept_len = c->accept_len;
+  k.path_stride = c->path_stride;
+  k.capacity = (int64_t)c->max_blocks * c->block_size;
+  k.n_slots = c->n_slots;
+  k.block_size = c->block_size;
+  k.table_stride = c->table_stride;
+  k.q_len = c->q_len;
+  return static_cast<int>(sqllm::g_launch_kv_compact ? sqllm::g_launch_kv_compact(k, (int)(D * c->elem_bytes), vec, (int)H, c->n_caches, c->batch, static_cast<hipStream_t>(stream))
+                                                     : hipErrorNotSupported);
 }
 
 int sqllm_launch(const sqllm_op* op, sqllm_stream_t stream) {

@@ -1172,6 +1172,195 @@ def tree_as_decode_rows(block_table: torch.Tensor, seq_lens: torch.Tensor, q_len
     return table.reshape(B * T, S), lens.reshape(-1).to(seq_lens.dtype)
 
 
+def _check_route(route):
+    if route not in (None, "kernel", "torch"):
+        raise ValueError(f"route must be None, 'kernel' or 'torch', got {route!r}")
+
+
+def _int32_rows(t: torch.Tensor, shape, name: str) -> torch.Tensor:
+    """`t` as a contiguous int32 [batch, T]; what already is one is returned as it is, so that a captured graph follows it."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be an int32 (or int64) tensor of shape {tuple(shape)}")
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)  # (a kernel)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _torch_tree_accept(par, mask, draft, target, n, seq):
+    """sqllm_tree_accept's formulas (include/sqllm_hip.h) in torch, vectorised; all operands int64, `seq` or None."""
+    B, T = par.shape
+    dev = par.device
+    t = torch.arange(T, device=dev)
+    j = torch.arange(64, device=dev)
+    served = (n > 0) & (n <= T)
+    node = served[:, None] & (t[None, :] < n[:, None])
+    bits = (((mask[:, :, None] >> j) & 1).bool() | (t[:, None] == j[None, :])[None]) & (j[None, None, :] < n[:, None, None])  # w(t), [B, T, 64]
+    earlier = (par >= 0) & (par < t[None, :])
+    match = node & ((par < 0) | (earlier & (draft == target.gather(1, par.clamp(0, T - 1)))))
+    M = torch.zeros((B, 64), dtype=torch.bool, device=dev)
+    M[:, :T] = match
+    accepted = node & ~(bits & ~M[:, None, :]).any(dim=2)
+    key = torch.where(accepted, bits.sum(dim=2) * 64 + 63 - t[None, :], torch.full((B, T), -1, dtype=torch.int64, device=dev)).amax(dim=1)
+    found = key >= 0
+    best = torch.where(found, 63 - key % 64, torch.zeros_like(key))
+    accept_len = torch.where(found, key // 64, torch.zeros_like(key))
+    W = bits[torch.arange(B, device=dev), best] & found[:, None]  # [B, 64]
+    rank = torch.where(W, W.cumsum(dim=1) - 1, torch.full_like(key, max(T, 64))[:, None])  # (the rest lands in a column that is cut off)
+    path = torch.full((B, max(T, 64) + 1), -1, dtype=torch.int64, device=dev).scatter_(1, rank, j[None, :].expand(B, 64))[:, :T]
+    next_token = torch.where(found, target.gather(1, best[:, None])[:, 0], torch.full_like(key, -1))
+    new_seq = None if seq is None else torch.where(n > T, seq, seq - n.clamp(min=0) + accept_len)
+    return accept_len, path, next_token, new_seq
+
+
+def tree_accept(parents, tree_mask, draft_tokens, target_tokens, q_lens=None, seq_lens=None, route=None):
+    """Greedy acceptance of a verified draft tree (include/sqllm_hip.h, sqllm_tree_accept): (accept_len [batch], path [batch, T],
+    next_token [batch], new_seq_lens [batch] or None), all int32 on the operands' device.  `parents`, `draft_tokens` and
+    `target_tokens` are int32 [batch, T], T <= 64: the parent of node t (-1: a root), its token, and the target model's greedy
+    token AFTER node t (the argmax of row (b, t) of the verification, which stays the caller's).  `tree_mask` is the int64
+    [batch, T] of tree_masks(parents, wide=True) -- an int32 mask of a 16-node tree is widened (a kernel).  A node is accepted
+    when every node of its closure matched (a root always; a child when its token is the target's token after its parent); the
+    accepted node with the longest closure wins, the lowest index among equals.  path[b, :accept_len[b]] are its closure's nodes,
+    ascending, the rest -1; next_token[b] is the target's token after it (-1 when nothing is accepted, as for q_lens[b] <= 0 or
+    > T); new_seq_lens = seq_lens - q_lens + accept_len when `seq_lens` (the lengths the tree call had) is given.  compact_kv
+    moves the path's rows.  `route`: None takes the kernel for GPU operands and torch otherwise; "kernel" raises instead of falling
+    back; "torch" forces the torch form.  One kernel node, device operands only: a captured graph follows them updated in place."""
+    _check_route(route)
+    par = torch.as_tensor(parents)
+    if par.dim() != 2 or not 1 <= par.shape[1] <= ATTN_TREE64_MAX_Q_LEN:
+        raise ValueError(f"parents must be [batch, T] with T in [1, {ATTN_TREE64_MAX_Q_LEN}], got {tuple(par.shape)}")
+    B, T = par.shape
+    par = _int32_rows(par, (B, T), "parents")
+    draft = _int32_rows(draft_tokens, (B, T), "draft_tokens")
+    target = _int32_rows(target_tokens, (B, T), "target_tokens")
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype not in (torch.int32, torch.int64) or tuple(tree_mask.shape) != (B, T):
+        raise ValueError(f"tree_mask must be int64 (or int32) [{B}, {T}]")
+    mask = tree_mask if tree_mask.dtype == torch.int64 else tree_mask.long() & 0xFFFFFFFF
+    mask = mask if mask.is_contiguous() else mask.contiguous()
+    ql = None if q_lens is None else _int32_rows(q_lens.reshape(-1), (B,), "q_lens")
+    sl = None if seq_lens is None else _int32_rows(seq_lens.reshape(-1), (B,), "seq_lens")
+    operands = [par, mask, draft, target] + [x for x in (ql, sl) if x is not None]
+    on_gpu = all(x.is_cuda for x in operands)
+    if any(x.device != par.device for x in operands):
+        raise ValueError("tree_accept: the operands must live on one device")
+    if route == "kernel" and not on_gpu:
+        raise RuntimeError("tree_accept(route='kernel') needs GPU tensors: there is no CPU kernel")
+    if route == "torch" or not on_gpu:
+        n = torch.full((B,), T, dtype=torch.int64, device=par.device) if ql is None else ql.long()
+        res = _torch_tree_accept(par.long(), mask, draft.long(), target.long(), n, None if sl is None else sl.long())
+        return tuple(None if r is None else r.to(torch.int32) for r in res)
+    dev = par.get_device()
+    accept_len = torch.empty((B,), dtype=torch.int32, device=par.device)
+    path = torch.empty((B, T), dtype=torch.int32, device=par.device)
+    next_token = torch.empty((B,), dtype=torch.int32, device=par.device)
+    new_seq = None if sl is None else torch.empty((B,), dtype=torch.int32, device=par.device)
+    a = _lib.SqllmTreeAccept()
+    a.parents, a.tree_mask, a.draft_tokens, a.target_tokens = par.data_ptr(), mask.data_ptr(), draft.data_ptr(), target.data_ptr()
+    a.q_lens = None if ql is None else ql.data_ptr()
+    a.seq_lens_in = None if sl is None else sl.data_ptr()
+    a.accept_len, a.path, a.next_token = accept_len.data_ptr(), path.data_ptr(), next_token.data_ptr()
+    a.seq_lens_out = None if new_seq is None else new_seq.data_ptr()
+    a.stride, a.mask_stride, a.q_len, a.batch = T, 2 * T, T, B
+    quant_cuda._launch(quant_cuda._fn("sqllm_tree_accept"), dev, (ctypes.byref(a),))
+    return accept_len, path, next_token, new_seq
+
+
+def _torch_compact_kv(caches, table, seq, n, path, alen, T, bs):
+    """sqllm_kv_compact's semantics in torch, vectorised and of fixed shapes (no host synchronisation: capturable): all T
+    elements of every sequence are gathered into a temporary -- a moving element its source row, any other its own row -- and
+    scattered back; an element without a slot of its own repeats the first element that has one (equal values at equal places)."""
+    B, max_blocks = table.shape
+    n_slots, H, D = caches[0].shape
+    dev = seq.device
+    j = torch.arange(T, device=dev)[None, :]
+    ctx = seq - n
+    live = (n > 0) & (n <= T) & (ctx >= 0) & (alen > 0) & (alen <= n)
+    s = path[:, :T]
+    ks, kd = ctx[:, None] + s, ctx[:, None] + j
+    cap = max_blocks * bs
+
+    def slots(k):
+        inside = (k >= 0) & (k < cap)
+        kk = torch.where(inside, k, torch.zeros_like(k))
+        sl = table.gather(1, kk // bs) * bs + kk % bs
+        ok = inside & (sl >= 0) & (sl < n_slots)
+        return torch.where(ok, sl, torch.zeros_like(sl)), ok
+
+    slot_s, ok_s = slots(ks)
+    slot_d, ok_d = slots(kd)
+    move = (live[:, None] & (j < alen[:, None]) & (s > j) & (s < n[:, None]) & ok_s & ok_d).reshape(-1)
+    ok_d = ok_d.reshape(-1)
+    first = ok_d.to(torch.int8).argmax().reshape(1)  # (0 where no element has a slot: every element then rewrites slot 0 with its bytes)
+    src = torch.where(move, slot_s.reshape(-1), slot_d.reshape(-1))
+    dst = slot_d.reshape(-1)
+    src = torch.where(ok_d, src, src.index_select(0, first))  # (index_select: no host synchronisation)
+    dst = torch.where(ok_d, dst, dst.index_select(0, first))
+    ss, hs = caches[0].stride(0), caches[0].stride(1)
+    inner = (torch.arange(H, device=dev)[:, None] * hs + torch.arange(D, device=dev)[None, :]).reshape(-1)
+    at_src = (src[:, None] * ss + inner[None, :]).reshape(-1)
+    at_dst = (dst[:, None] * ss + inner[None, :]).reshape(-1)
+    for c in caches:
+        raw = c.view(torch.uint8) if c.element_size() == 1 else c.view(torch.int16)  # (bytes as bytes)
+        flat = raw.as_strided(((n_slots - 1) * ss + (H - 1) * hs + D,), (1,), raw.storage_offset())
+        flat.index_put_((at_dst,), flat[at_src])  # (the gather is a temporary: every source is read before a destination is written)
+
+
+def compact_kv(caches, block_table, seq_lens, q_len, path, accept_len, *, block_size, q_lens=None, route=None):
+    """Move the K and V rows of the accepted path to the front of the tree's keys, IN PLACE, in every cache of `caches` at once
+    (include/sqllm_hip.h, sqllm_kv_compact): node t of the verified tree was stored as key C_b + t, C_b = seq_lens[b] - q_lens[b];
+    afterwards the keys C_b .. C_b + accept_len[b] - 1 hold the rows of the nodes path[b, :accept_len[b]], and seq_lens may become
+    tree_accept's new_seq_lens.  `caches`: a list of up to 256 [n_slots, H, D] views (kv_cache_view) -- the k and the v cache of
+    every layer -- of ONE shape, strides and dtype, 16-bit or float8_e4m3fn.  `block_table` [batch, max_blocks], `seq_lens` (the
+    lengths the tree call had, its nodes included -- not new_seq_lens), `q_len` = T, `q_lens` as in that call; `path` int32
+    [batch, >= T] and `accept_len` int32 [batch] as tree_accept returned them.  Every source row of a sequence is read before any
+    of its destinations is written; a path that is its own prefix moves nothing.  `route` as in tree_accept.  One kernel node for
+    all caches, device operands only: a captured graph follows tables, lengths and paths updated in place."""
+    _check_route(route)
+    caches = list(caches)
+    T = int(q_len)
+    if not 1 <= len(caches) <= _lib.KV_COMPACT_MAX_CACHES:
+        raise ValueError(f"compact_kv takes 1 to {_lib.KV_COMPACT_MAX_CACHES} caches, got {len(caches)}")
+    c0 = caches[0]
+    if c0.dim() != 3 or c0.stride(2) != 1 or c0.element_size() not in (1, 2) or (c0.element_size() == 1 and c0.dtype != torch.float8_e4m3fn):
+        raise ValueError("a cache must be a [n_slots, H, D] view (kv_cache_view) of a 16-bit type or float8_e4m3fn")
+    for c in caches:
+        if c.shape != c0.shape or c.stride() != c0.stride() or c.dtype != c0.dtype or c.device != c0.device:
+            raise ValueError("compact_kv: all caches must share one shape, strides, dtype and device")
+    if not 1 <= T <= ATTN_TREE64_MAX_Q_LEN:
+        raise ValueError(f"q_len must lie in [1, {ATTN_TREE64_MAX_Q_LEN}], got {q_len}")
+    B = block_table.shape[0]
+    if block_table.dim() != 2 or path.dim() != 2 or path.shape[0] != B or path.shape[1] < T:
+        raise ValueError(f"block_table must be [batch, max_blocks] and path [batch, >= {T}]")
+    bt = block_table if block_table.dtype == torch.int32 and block_table.stride(1) == 1 else block_table.to(torch.int32).contiguous()
+    pt = path if path.dtype == torch.int32 and path.stride(1) == 1 else path.to(torch.int32).contiguous()
+    sl, al = _int32_rows(seq_lens.reshape(-1), (B,), "seq_lens"), _int32_rows(accept_len.reshape(-1), (B,), "accept_len")
+    ql = None if q_lens is None else _int32_rows(q_lens.reshape(-1), (B,), "q_lens")
+    operands = [c0, bt, pt, sl, al] + ([] if ql is None else [ql])
+    if any(x.device != c0.device for x in operands):
+        raise ValueError("compact_kv: the operands must live on one device")
+    on_gpu = c0.is_cuda
+    if route == "kernel" and not on_gpu:
+        raise RuntimeError("compact_kv(route='kernel') needs GPU tensors: there is no CPU kernel")
+    bs = int(block_size)
+    n_slots, H, D = c0.shape
+    if route == "torch" or not on_gpu:
+        n = torch.full((B,), T, dtype=torch.int64, device=c0.device) if ql is None else ql.long()
+        _torch_compact_kv(caches, bt.long(), sl.long(), n, pt.long(), al.long(), T, bs)
+        return
+    a = _lib.SqllmKvCompact()
+    ptrs = (ctypes.c_void_p * len(caches))(*[c.data_ptr() for c in caches])
+    a.caches = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
+    a.block_table, a.seq_lens, a.path, a.accept_len = bt.data_ptr(), sl.data_ptr(), pt.data_ptr(), al.data_ptr()
+    a.q_lens = None if ql is None else ql.data_ptr()
+    a.n_caches, a.elem_bytes, a.n_kv_heads, a.head_dim = len(caches), c0.element_size(), H, D
+    a.n_slots, a.block_size, a.max_blocks = n_slots, bs, bt.shape[1]
+    a.table_stride = bt.stride(0) if B > 1 else bt.shape[1]
+    a.q_len, a.batch = T, B
+    a.slot_stride = c0.stride(0) if n_slots > 1 else H * max(c0.stride(1), D)
+    a.head_stride = c0.stride(1) if H > 1 else D
+    a.path_stride = pt.stride(0) if B > 1 else pt.shape[1]
+    quant_cuda._launch(quant_cuda._fn("sqllm_kv_compact"), c0.get_device(), (ctypes.byref(a),))
+
+
 def static_cache_blocks(batch: int, n_kv_heads: int, device=None) -> torch.Tensor:
     """The int32 block table [batch, 1] of a head-major static cache [B, H, S, D] seen through kv_cache_view(cache, "bhsd"),
     for DecodeAttention with block_size = S: block_table[b, 0] = b * H, so that key p of row b lies in slot b * H * S + p --
